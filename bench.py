@@ -7,7 +7,13 @@ synthetic keypoints that is already resident in HBM.  Workload = BASELINE.json c
 23 keypoints, 10 000 synthetic frames, q_phase only, on every GPU (weak scaling: clips are
 independent, each rank fits its own shard; no collective on the data path).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames 10000] [--frames-per-clip 1]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames 10000] [--frames-per-clip 1] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line (value, ms_per_step, the roofline of the timed steps).
+--full adds what takes work of its own: the marker-space error of the result, the 250-frame-clip and LM legs, the CPU baseline
+(the oracle) and, for N > 1, the offset-phase exchange probe.  --dump-outputs DIR writes what the last timed step returned as
+DIR/<name>.npy (rank 0's share; float32 or float64; a seeded sample of rows above 60 MiB in all), so that two builds can be
+compared output for output on the same seeded inputs.
 
 For N > 1 either launch it under torch.distributed.run yourself (one rank per GPU) or just pass --gpus N: without
 WORLD_SIZE in the environment the script starts `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a
@@ -79,6 +85,44 @@ def gather_rank_records(rec: dict, dist) -> list:
     out = [None] * dist.get_world_size()
     dist.all_gather_object(out, rec)
     return sorted(out, key=lambda r: r["rank"])
+
+
+DUMP_BUDGET_BYTES = 60 << 20  # --dump-outputs stays under 64 MB in all
+
+
+def dump_outputs(dirpath, arrays: dict, budget: int = DUMP_BUDGET_BYTES, seed: int = 0) -> dict:
+    """--dump-outputs: the numeric arrays a caller of the timed path receives, as DIR/<name>.npy -- float32 as float32, everything
+    else (int32 counters, float64) as float64; None, non-numeric fields and keys starting with "_" are left out.  Above `budget` bytes
+    in all, every array keeps a seeded sample of its leading-axis rows (the same rows for arrays of the same length, the same rows
+    from run to run), taken on the device before the copy.  Returns {name: shape written}."""
+    items = {}
+    for name, v in arrays.items():
+        if v is None or name.startswith("_"):
+            continue
+        if torch.is_tensor(v):
+            if v.is_complex() or v.dtype == torch.bool:
+                continue
+            items[name] = (v.detach(), 4 if v.dtype == torch.float32 else 8)
+        else:
+            a = np.asarray(v)
+            if a.dtype.kind not in "biuf":
+                continue
+            items[name] = (a, 4 if a.dtype == np.float32 else 8)
+    total = sum(a.numel() * sz if torch.is_tensor(a) else a.size * sz for a, sz in items.values())
+    frac = budget / total if total > budget else 1.0
+    out = Path(dirpath)
+    out.mkdir(parents=True, exist_ok=True)
+    written = {}
+    for name, (a, sz) in items.items():
+        if frac < 1.0 and a.ndim > 0:
+            n = a.shape[0]
+            idx = np.sort(np.random.default_rng(seed).choice(n, max(int(n * frac), 1), replace=False))
+            a = a[torch.as_tensor(idx, device=a.device)] if torch.is_tensor(a) else a[idx]
+        h = a.cpu().numpy() if torch.is_tensor(a) else a
+        h = np.ascontiguousarray(h, dtype=np.float32 if sz == 4 else np.float64)
+        np.save(out / f"{name}.npy", h)
+        written[name] = list(h.shape)
+    return written
 
 
 def predicted_value(model: str, shape: dict, world: int, table_path=None):
@@ -178,6 +222,8 @@ def run_fit_mode(args, rank, local_rank, world, dist):
         tmax = torch.tensor([elapsed], device=eng.device)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, data.as_dict())
     solves = world * C * F * n_pass * args.steps
     d_off = float(np.linalg.norm(data.offsets - synth_offsets(fs), axis=-1).mean() * 1e3)
     line = {
@@ -251,6 +297,8 @@ def run_run_mode(args, rank, local_rank, world, dist):
         for k, v in stac.timings.items():
             phases[k] = phases.get(k, 0.0) + v / args.steps
         stac.timings = None
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, data.as_dict())
     with tempfile.TemporaryDirectory() as td:
         t0 = time.perf_counter()
         out = sio.save_data_to_h5(cfg, data.kp_names, data.names_qpos, data.names_xpos, data.kp_data, data.marker_sites, data.offsets,
@@ -356,8 +404,13 @@ def main():
                          "split over the ranks (BASELINE configs[3]: --scaling strong --frames 1000000 --frames-per-clip 250)")
     ap.add_argument("--frames-per-clip", type=int, default=1)
     ap.add_argument("--lanes", type=int, default=0, help="lanes of a wavefront per chain (0 = auto)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the clips250 and LM legs (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what a plain run leaves out: marker-space error, the clips250 and LM legs, the CPU "
+                         "baseline, the offset-phase exchange for N > 1 (default mode)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (rank 0's share)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the clips250 and LM legs (profiling runs)")
     ap.add_argument("--mode", default="ik", choices=["ik", "fit", "run"],
                     help="ik = q_phase only (the BASELINE metric); fit = offset/pose alternation on clips sharded over the "
                          "ranks with the offset-phase all-reduce over RCCL (stac.fit_frames_per_clip), reported as frame-solves/s; "
@@ -460,6 +513,8 @@ def main():
         tmax = torch.tensor([elapsed], device=eng.device)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    if rank == 0 and args.dump_outputs and C > 0:
+        dump_outputs(args.dump_outputs, out)
     kern_ms = float(np.mean([a.elapsed_time(b) for a, b in ev])) if C > 0 else 0.0
     import ctypes
 
@@ -469,12 +524,7 @@ def main():
 
     frames_step = C * F  # this rank's frames per step
     value = job_value(shape, args.steps, elapsed)  # whole-job frames over the slowest rank's time
-    if C > 0:
-        cnt = out["counters"].to(torch.float64).sum(dim=(0, 1)).cpu().numpy()
-        err = torch.linalg.norm((eng.fk(out["qpos"].reshape(-1, fs.tables.nq), want=("site_xpos",))["site_xpos"]
-                                 - kp.reshape(-1, fs.tables.nsite, 3)), dim=-1)
-    else:
-        cnt, err = np.zeros(4), torch.zeros(1, device=eng.device)
+    cnt = out["counters"].to(torch.float64).sum(dim=(0, 1)).cpu().numpy() if C > 0 else np.zeros(4)
     # algorithmic bytes of the q_phase kernel: keypoints in, qpos + residual out (576 B/frame)
     bytes_frame = 12 * fs.tables.nsite + 4 * fs.tables.nq + 4
     kern_ms = max(kern_ms, 1e-9)
@@ -513,7 +563,6 @@ def main():
             "per_rank": per_rank, "predicted_value": predicted_value(args.model, shape, world) if args.solver == "pg" else None,
             "iters_per_frame": cnt[0] / max(frames_step, 1), "ls_evals_per_frame": cnt[1] / max(frames_step, 1),
             "grad_evals_per_frame": cnt[2] / max(frames_step, 1),
-            "marker_rmse_mm": float(torch.sqrt((err ** 2).mean()).item() * 1e3),
             "valu_tflops_algorithmic": flops / (kern_ms * 1e-3) / 1e12,
             "valu_frac_of_fp32_peak": flops / (kern_ms * 1e-3) / 1e12 / FP32_VALU_PEAK_TFLOPS,
         },
@@ -551,7 +600,14 @@ def main():
                             "VALU back to back from several wavefronts"}
     except (FileNotFoundError, KeyError):
         pass
-    if world > 1 and args.solver == "pg":
+    if args.full:  # marker-space error of the last step's result: one FK launch of its own
+        if C > 0:
+            err = torch.linalg.norm((eng.fk(out["qpos"].reshape(-1, fs.tables.nq), want=("site_xpos",))["site_xpos"]
+                                     - kp.reshape(-1, fs.tables.nsite, 3)), dim=-1)
+        else:
+            err = torch.zeros(1, device=eng.device)
+        line["config"]["marker_rmse_mm"] = float(torch.sqrt((err ** 2).mean()).item() * 1e3)
+    if args.full and world > 1 and args.solver == "pg":
         # The q_phase shards without a collective, so a scaling line of this mode would prove only the timing barrier.  The one
         # data-path exchange of the engine -- the offset phase's 3K + 2 partial sums -- is therefore exercised
         # on the same ranks: this rank's sums over its own first frames, all-reduced and finished on every rank.  Never `value`.
@@ -565,7 +621,8 @@ def main():
         probe = offset_phase_exchange_probe(part, lambda red: eng.m_finish(red, off_now, is_reg, 1.0)[0])
         line["config"]["offset_phase_exchange"] = dict(probe, note="one all-reduce (all-gather + fixed-order sum) of the offset "
                                                        "phase's partial sums per calibration iteration; --mode fit runs the whole calibration")
-    if rank == 0 and world == 1 and args.solver == "pg" and args.model == "rodent" and F == 1 and not args.no_extras and not strong:
+    extras = args.full and not args.no_extras
+    if rank == 0 and world == 1 and args.solver == "pg" and args.model == "rodent" and F == 1 and extras and not strong:
         # BASELINE configs[1] with the reference's DEFAULT chaining (configs/stac/stac.yaml:9, n_frames_per_clip = 250):
         # the same number of frames as 40 warm-started clips -- latency mode, one chain per workgroup.  Never `value`.
         Fc = 250
@@ -592,7 +649,7 @@ def main():
             "iters_per_frame": ccnt[0] / (Cc * Fc), "us_per_pg_iteration": c_ms * 1e3 / (ccnt[0] / Cc),
             "marker_rmse_mm": float(torch.sqrt((cerr ** 2).mean()).item() * 1e3),
             "note": "each clip is one serial chain of 250 x ~410 PG iterations: speculative latency mode, 4 wavefronts per chain"}
-    if rank == 0 and world == 1 and args.solver == "pg" and args.model == "rodent" and not args.no_extras and not strong:
+    if rank == 0 and world == 1 and args.solver == "pg" and args.model == "rodent" and extras and not strong:
         # the north star words the q_phase as a Levenberg-Marquardt update; the reference runs projected gradient (the
         # `value` above, parity mode).  The optional LM solver on the same resident batch, for the record -- never `value`.
         lm = Engine(fs.tables, fs.lb, fs.ub, tol=float(cfg["FTOL"]), maxiter=int(cfg["N_ITER_Q"]), device=f"cuda:{local_rank}",
@@ -616,7 +673,7 @@ def main():
             "marker_rmse_mm": float(torch.sqrt((lerr ** 2).mean()).item() * 1e3),
             "lm_maxiter": args.lm_maxiter,
             "note": "stac_q_params.solver = STAC_SOLVER_LM; not the reference's algorithm, judged in marker space only"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.solver == "pg" and C > 0:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and args.solver == "pg" and C > 0:
         line["cpu_baseline"] = cpu_baseline(fs, cfg, kp_host)
     if rank == 0:
         print(json.dumps(line))

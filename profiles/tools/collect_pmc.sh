@@ -8,7 +8,7 @@ OUT=$R/gpurun_out/prof_$tag
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/rp_${tag}_stats
-rocprofv3 --kernel-trace --stats -d /tmp/rp_${tag}_stats --output-format csv -- python3 $R/bench.py --no-cpu-baseline "$@" > $OUT/bench.json 2> $OUT/bench.err
+rocprofv3 --kernel-trace --stats -d /tmp/rp_${tag}_stats --output-format csv -- python3 $R/bench.py --full --no-cpu-baseline "$@" > $OUT/bench.json 2> $OUT/bench.err
 f=$(find /tmp/rp_${tag}_stats -name "*kernel_stats.csv" | head -1)
 [ -n "$f" ] && cp $f $OUT/kernel_stats.csv
 i=0

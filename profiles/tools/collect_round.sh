@@ -20,7 +20,7 @@ done
   first=1
   run() {  # label, args...
     label=$1; shift
-    line=$(python3 bench.py --no-cpu-baseline --no-extras "$@" 2>/dev/null | tail -1)
+    line=$(python3 bench.py --full --no-cpu-baseline --no-extras "$@" 2>/dev/null | tail -1)
     [ -z "$line" ] && line='null'
     [ $first = 1 ] || echo ","
     first=0

@@ -9,8 +9,8 @@ echo "# library build $(cut -c1-16 stac_mjx_amd/csrc/libstac_hip.so.stamp)" >> $
 echo "== python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 bench.py --gpus 1 --steps 20 --warmup 5 (RCCL init, barrier, max over ranks)" >> $out
 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --steps 20 --warmup 5 2>/dev/null | tail -1 | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('value', round(d['value']), 'ms_per_step', round(d['ms_per_step'],3), 'collective_backend', d['config']['collective_backend'], 'per_rank', d['config']['per_rank'], 'predicted_value', round(d['config']['predicted_value']) if d['config'].get('predicted_value') else None)" >> $out
-echo "== consecutive default runs: python bench.py --gpus 1 --steps 20 --warmup 5" >> $out
-for i in 1 2 3 4 5 6; do python bench.py --gpus 1 --steps 20 --warmup 5 2>/dev/null | tail -1 | python -c "
+echo "== consecutive default runs: python bench.py --gpus 1 --steps 20 --warmup 5 --full" >> $out
+for i in 1 2 3 4 5 6; do python bench.py --gpus 1 --steps 20 --warmup 5 --full 2>/dev/null | tail -1 | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('run $i value', round(d['value']), 'ms_per_step', round(d['ms_per_step'],3), 'clips250', round(d['config']['clips250']['frames_per_s']), 'us/iter', round(d['config']['clips250']['us_per_pg_iteration'],3), 'lm', round(d['config']['lm_solver_same_batch']['frames_per_s']), 'traffic', d['roofline']['traffic'], 'valu_busy', round(d['roofline_valu']['valu_issue_busy_frac'],3) if 'roofline_valu' in d and 'valu_issue_busy_frac' in d['roofline_valu'] else None, 'cpu', round(d['cpu_baseline']['value']))" >> $out; done
 python bench.py --gpus 1 --steps 20 --warmup 5 2>/dev/null | tail -1 > $OUT/${tag}_bench_plain.json
 echo "== __graft_entry__.smoke()" >> $out

@@ -16,7 +16,6 @@ if str(ROOT) not in sys.path:
     sys.path.insert(0, str(ROOT))
 
 GOLDEN = ROOT / "tests" / "golden"
-REFERENCE = Path("/root/reference")
 
 
 def pytest_configure(config):
@@ -67,6 +66,20 @@ def _install_scratch_poison():
 @pytest.fixture(scope="session")
 def golden_dir():
     return GOLDEN
+
+
+@pytest.fixture(scope="session")
+def reference_dir(tmp_path_factory):
+    """The reference's files that the tests read, in its own layout, unpacked from tests/golden/reference_fixtures.tar.xz:
+    models/{rodent,synth_model}.xml and one model each of mouse/, fruitfly/, celegans/; configs/ and tests/configs/ (the
+    default and the test config with their model and stac files); its LICENSE; and tests/data/test_{rodent,mouse}_mocap_200_frames.*:
+    the first 200 frames of its rodent .mat / .nwb and mouse .h5 recordings, in the same file layouts."""
+    import tarfile
+
+    dest = tmp_path_factory.mktemp("reference")
+    with tarfile.open(GOLDEN / "reference_fixtures.tar.xz") as tf:
+        tf.extractall(dest, **({"filter": "data"} if hasattr(tarfile, "data_filter") else {}))
+    return dest
 
 
 @pytest.fixture(scope="session")

@@ -352,7 +352,8 @@ def test_fit_and_ik_two_ranks_over_rccl(tmp_path, rodent_setup, rodent_cfg, rode
     ["--mode", "run", "--steps", "1", "--warmup", "0", "--frames", "500", "--frames-per-clip", "250"],
     ["--solver", "lm", "--steps", "1", "--warmup", "0", "--frames", "200", "--no-cpu-baseline"],
     ["--model", "fly", "--steps", "1", "--warmup", "0", "--frames", "200", "--no-cpu-baseline", "--no-extras"],
-], ids=["ik", "clips", "strong", "fit", "run", "lm", "fly"])
+    ["--full", "--steps", "1", "--warmup", "0", "--frames", "500"],
+], ids=["ik", "clips", "strong", "fit", "run", "lm", "fly", "full"])
 def test_every_bench_mode_prints_its_line(args):
     """Round 6 (a fit-mode line once named a field of the default mode and only failed on the GPU box, inside the round's collection):
     every mode of bench.py runs at a small size as its own process and prints ONE JSON line with the contract's keys."""
@@ -371,6 +372,42 @@ def test_every_bench_mode_prints_its_line(args):
     if "--mode" not in args:
         assert d["roofline"]["frac"] > 0 and d["config"]["per_rank"][0]["clips"] > 0
         assert ("predicted_value" in d["config"])
+    if "--full" in args:  # what a plain run leaves out
+        assert d["config"]["marker_rmse_mm"] > 0 and d["cpu_baseline"]["value"] > 0
+        assert d["config"]["clips250"]["frames_per_s"] > 0 and d["config"]["lm_solver_same_batch"]["frames_per_s"] > 0
+    elif "--mode" not in args:
+        assert "cpu_baseline" not in d and not {"marker_rmse_mm", "clips250", "lm_solver_same_batch"} & set(d["config"])
+
+
+def test_bench_dump_outputs_are_the_timed_path_and_repeat(tmp_path, rodent_setup, rodent_cfg):
+    """`--dump-outputs DIR`: two runs with the same arguments write the same arrays, and they are what `Engine.q_phase` returns on the
+    bench's seeded batch (rebuilt here the way bench.py builds it)."""
+    import subprocess
+    import sys
+
+    from stac_mjx_amd.engine import Engine
+    from stac_mjx_amd.synth import synth_keypoints, synth_offsets
+
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--frames", "300",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        dumps.append({p.stem: np.load(p) for p in sorted(d.glob("*.npy"))})
+    a, b = dumps
+    assert set(a) == {"qpos", "frame_error", "counters"}
+    assert a["qpos"].shape == (300, 1, 74) and a["qpos"].dtype == np.float32 and a["counters"].dtype == np.float64
+    for k in a:
+        np.testing.assert_array_equal(a[k], b[k], err_msg=k)
+    fs = rodent_setup
+    eng = Engine(fs.tables, fs.lb, fs.ub, tol=float(rodent_cfg["FTOL"]), maxiter=int(rodent_cfg["N_ITER_Q"]))
+    eng.set_site_pos(synth_offsets(fs))
+    kp, _ = synth_keypoints(fs, lambda q: eng.fk(q, want=("site_xpos",))["site_xpos"].cpu().numpy(), 300, 1, seed=0, noise_seed=1)
+    res = eng.q_phase(kp, part_masks=fs.part_masks, trunk_kps=fs.trunk_kps, root_kp_idx=fs.root_kp_idx, root_dims=fs.root_dims,
+                      do_root_opt=fs.do_root_opt, want_bodies=False, want_markers=False, want_carry=False)
+    np.testing.assert_array_equal(a["qpos"], res["qpos"].cpu().numpy())
+    np.testing.assert_array_equal(a["counters"], res["counters"].cpu().numpy().astype(np.float64))
 
 
 @pytest.mark.parametrize("args,clips", [
@@ -390,7 +427,7 @@ def test_bench_two_ranks_on_one_gpu(args, clips):
     env = dict(os.environ, STAC_BENCH_BACKEND="gloo", STAC_BENCH_SHARE_GPU="1")
     port = 29800 + int(torch.randint(0, 150, (1,)).item())
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), str(ROOT / "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", *args]
+           "--master-port", str(port), str(ROOT / "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline", *args]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -9,7 +9,7 @@ import pytest
 import torch
 import yaml
 
-from conftest import REFERENCE, ROOT
+from conftest import ROOT
 
 
 # ---- C ABI -----------------------------------------------------------------------------------------------
@@ -105,13 +105,12 @@ def test_compose_config_defaults_overrides_and_schema(tmp_path, rodent_cfg):
     assert rt["model"]["SCALE_FACTOR"] == 0.9
 
 
-@pytest.mark.skipif(not REFERENCE.exists(), reason="reference checkout not present")
-def test_reference_config_dirs_load():
+def test_reference_config_dirs_load(reference_dir):
     from stac_mjx_amd.config import compose_config
 
-    cfg = compose_config(REFERENCE / "configs", "config")
+    cfg = compose_config(reference_dir / "configs", "config")
     assert cfg.stac.n_fit_frames == 10 and cfg.model.MJCF_PATH == "models/rodent.xml"
-    cfgt = compose_config(REFERENCE / "tests" / "configs", "config")
+    cfgt = compose_config(reference_dir / "tests" / "configs", "config")
     assert cfgt.stac.n_fit_frames == 42 and cfgt.stac.n_frames_per_clip == 1  # tests/unit/test_config.py
 
 
@@ -144,15 +143,14 @@ def test_load_data_mat_ordering_and_scaling(tmp_path, rodent_cfg):
         load_data(cfg, base_path=tmp_path)
 
 
-def test_committed_mocap_fixture_matches_reference_mat(rodent_mocap):
-    if not REFERENCE.exists():
-        pytest.skip("reference checkout not present")
+def test_committed_mocap_fixture_matches_reference_mat(rodent_mocap, reference_dir):
     import scipy.io as spio
 
-    pred = spio.loadmat(REFERENCE / "tests/data/test_rodent_mocap_1000_frames.mat")["pred"]
+    pred = spio.loadmat(reference_dir / "tests/data/test_rodent_mocap_200_frames.mat")["pred"]
     assert rodent_mocap.shape == (1000, 69)
     # column 0..2 = AnkleL = index 17 of KP_NAMES
     np.testing.assert_allclose(rodent_mocap[5, :3], (pred[5, :, 17] * 1e-3).astype(np.float32))
+    np.testing.assert_allclose(rodent_mocap[:len(pred), :3], (pred[:, :, 17] * 1e-3).astype(np.float32))  # every stored frame
 
 
 def test_save_and_load_stac_data_roundtrip(tmp_path, rodent_cfg):
@@ -676,37 +674,37 @@ def cfg_for(model_json, data_path):
     return m, validate_config({"model": m, "stac": dict(fit_offsets_path="fit.h5", ik_only_path="ik.h5", data_path=data_path,
         continuous=False, n_fit_frames=3, skip_fit_offsets=False, skip_ik_only=False, infer_qvels=True, n_frames_per_clip=3,
         mujoco=dict(solver="newton", iterations=1, ls_iterations=4))})
-m, c = cfg_for("rodent_model_cfg.json", "tests/data/test_rodent_mocap_1000_frames.nwb")
+m, c = cfg_for("rodent_model_cfg.json", "tests/data/test_rodent_mocap_200_frames.nwb")
 nwb, names_nwb = io.load_data(c, ref)
-_, c = cfg_for("rodent_model_cfg.json", "tests/data/test_rodent_mocap_1000_frames.mat")
+_, c = cfg_for("rodent_model_cfg.json", "tests/data/test_rodent_mocap_200_frames.mat")
 mat, names_mat = io.load_data(c, ref)
-mm, c = cfg_for("mouse_model_cfg.json", "tests/data/test_mouse_mocap_3600_frames.h5")
+mm, c = cfg_for("mouse_model_cfg.json", "tests/data/test_mouse_mocap_200_frames.h5")
 h5, names_h5 = io.load_data(c, ref)
 golden = np.load(sys.argv[1] + "/tests/golden/rodent_mocap_1000.npy")
 mouse_golden = np.load(sys.argv[1] + "/tests/golden/mouse_mocap_200.npy")
 print(json.dumps(dict(
     nwb_shape=list(nwb.shape), mat_shape=list(mat.shape), h5_shape=list(h5.shape), nwb_names=names_nwb, h5_names=names_h5,
     rodent_pairs=list(m["KEYPOINT_MODEL_PAIRS"].keys()), mouse_pairs=list(mm["KEYPOINT_MODEL_PAIRS"].keys()),
-    nwb_equals_mat=bool(np.array_equal(nwb, mat)), mat_equals_fixture=bool(np.array_equal(mat, golden)),
-    h5_equals_fixture=bool(np.array_equal(h5[:200], mouse_golden)), dtypes=[str(nwb.dtype), str(h5.dtype)],
+    nwb_equals_mat=bool(np.array_equal(nwb, mat)), mat_equals_fixture=bool(np.array_equal(mat, golden[:len(mat)])),
+    h5_equals_fixture=bool(np.array_equal(h5, mouse_golden)), dtypes=[str(nwb.dtype), str(h5.dtype)],
     h5_finite=bool(np.isfinite(h5).all()))))
 """
 
 
-@pytest.mark.skipif(not os.path.exists(_H5_PY) or not REFERENCE.exists(),
-                    reason="needs the image's h5py interpreter and the reference's test data (build container only)")
-def test_nwb_and_h5_input_loaders_on_the_reference_data(tmp_path):
-    """N1: `load_nwb` / `load_h5` through `load_data`, on tests/data/test_rodent_mocap_1000_frames.nwb and
-    test_mouse_mocap_3600_frames.h5, with the expectations of the reference's tests/test_io.py:93-173: shapes
-    (1000, 69) and (3600, 102), keypoint order == KEYPOINT_MODEL_PAIRS key order; and the .nwb result equals the
-    .mat one, which equals the committed fixture."""
+@pytest.mark.skipif(not os.path.exists(_H5_PY), reason="no interpreter with h5py in this image")
+def test_nwb_and_h5_input_loaders_on_the_reference_data(reference_dir):
+    """N1: `load_nwb` / `load_h5` through `load_data`, on the first 200 frames of the reference's
+    tests/data/test_rodent_mocap_1000_frames.nwb / .mat and test_mouse_mocap_3600_frames.h5 in their own file layouts (the
+    reference_dir fixture), with the expectations of the reference's tests/test_io.py:93-173: every frame of the file, 69 and 102
+    columns, keypoint order == KEYPOINT_MODEL_PAIRS key order; and the .nwb result equals the .mat one, which equals the
+    committed fixture's frames, and the .h5 result equals the committed mouse fixture."""
     import json
     import subprocess
 
-    r = subprocess.run([_H5_PY, "-c", _LOADER_SCRIPT, str(ROOT), str(REFERENCE)], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([_H5_PY, "-c", _LOADER_SCRIPT, str(ROOT), str(reference_dir)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads(r.stdout.strip().splitlines()[-1])
-    assert d["nwb_shape"] == [1000, 69] and d["mat_shape"] == [1000, 69] and d["h5_shape"] == [3600, 102]
+    assert d["nwb_shape"] == [200, 69] and d["mat_shape"] == [200, 69] and d["h5_shape"] == [200, 102]
     assert d["nwb_names"] == d["rodent_pairs"] and d["nwb_names"][:5] == ["AnkleL", "AnkleR", "EarL", "EarR", "ElbowL"]
     assert d["h5_names"] == d["mouse_pairs"] and d["h5_names"][:5] == ["Nose", "Ear_R", "Ear_L", "TTI", "Head"]
     assert d["nwb_equals_mat"] and d["mat_equals_fixture"] and d["h5_equals_fixture"] and d["h5_finite"]
@@ -749,3 +747,31 @@ def test_bench_gpus_2_without_two_gpus_exits_2_and_never_imports_hip_state(tmp_p
     src = (ROOT / "bench.py").read_text()
     launch = src[src.index("def self_launch"):src.index("def lib_digest")]
     assert "torch.cuda" not in launch and "device_count" not in launch
+
+
+def test_bench_dump_outputs_dtypes_budget_and_sample(tmp_path):
+    """bench.py --dump-outputs: float32 stays float32, integers and float64 are written as float64, non-numeric and private fields are
+    left out; above the budget every array keeps the same seeded rows, the same from call to call."""
+    import bench
+
+    rng = np.random.default_rng(5)
+    arrays = {"qpos": torch.as_tensor(rng.normal(size=(400, 1, 74)).astype(np.float32)),
+              "counters": torch.as_tensor(rng.integers(0, 900, (400, 1, 4)).astype(np.int32)),
+              "offsets": rng.normal(size=(23, 3)), "carry_qpos": None, "_keepalive": (1, 2), "kp_names": ["a", "b"]}
+    shapes = bench.dump_outputs(tmp_path / "all", arrays)
+    assert shapes == {"qpos": [400, 1, 74], "counters": [400, 1, 4], "offsets": [23, 3]}
+    q, c = np.load(tmp_path / "all" / "qpos.npy"), np.load(tmp_path / "all" / "counters.npy")
+    assert q.dtype == np.float32 and c.dtype == np.float64 and np.load(tmp_path / "all" / "offsets.npy").dtype == np.float64
+    np.testing.assert_array_equal(q, arrays["qpos"].numpy())
+    np.testing.assert_array_equal(c, arrays["counters"].numpy())
+    budget = 30_000  # about a quarter of the 400 x (74 x 4 + 4 x 8) + 23 x 3 x 8 bytes
+    s1 = bench.dump_outputs(tmp_path / "s1", arrays, budget=budget)
+    bench.dump_outputs(tmp_path / "s2", arrays, budget=budget)
+    written = sum((tmp_path / "s1" / f"{k}.npy").stat().st_size for k in s1)
+    assert s1["qpos"][0] == s1["counters"][0] < 400 and written <= budget + 3 * 128  # (+ the .npy headers)
+    qs, cs = np.load(tmp_path / "s1" / "qpos.npy"), np.load(tmp_path / "s1" / "counters.npy")
+    rows = [int(np.flatnonzero((arrays["qpos"].numpy() == r).all(axis=(1, 2)))[0]) for r in qs]
+    assert rows == sorted(rows)
+    np.testing.assert_array_equal(cs, arrays["counters"].numpy()[rows])  # the same rows in every array of that length
+    for k in s1:
+        np.testing.assert_array_equal(np.load(tmp_path / "s1" / f"{k}.npy"), np.load(tmp_path / "s2" / f"{k}.npy"))

@@ -3,7 +3,6 @@
 import numpy as np
 import pytest
 
-from conftest import REFERENCE
 from stac_mjx_amd.mjcf import (JNT_BALL, JNT_FREE, JNT_HINGE, JNT_SLIDE, MjcfError, ModelTables,
                                align_joint_dims, compile_mjcf)
 
@@ -125,20 +124,18 @@ def test_fly_facts(fly_setup):
     assert fly_setup.part_masks.shape == (6, 43)
 
 
-@pytest.mark.skipif(not REFERENCE.exists(), reason="reference checkout not present")
-def test_compile_matches_committed_fixture(rodent_setup, rodent_cfg):
+def test_compile_matches_committed_fixture(rodent_setup, rodent_cfg, reference_dir):
     from stac_mjx_amd.fit_model import build_fit_setup
 
-    fs = build_fit_setup(REFERENCE / "models" / "rodent.xml", rodent_cfg, rodent_setup.kp_names)
+    fs = build_fit_setup(reference_dir / "models" / "rodent.xml", rodent_cfg, rodent_setup.kp_names)
     for k, v in rodent_setup.tables.__dict__.items():
         if isinstance(v, np.ndarray):
             np.testing.assert_array_equal(v, getattr(fs.tables, k), err_msg=k)
 
 
-@pytest.mark.skipif(not REFERENCE.exists(), reason="reference checkout not present")
 @pytest.mark.parametrize("rel", ["models/synth_model.xml", "models/mouse/mouse_with_meshes.xml",
                                  "models/fruitfly/fruitfly_force_ball.xml", "models/celegans/celegans.xml"])
-def test_other_reference_models_compile(rel):
-    t = compile_mjcf(REFERENCE / rel)
+def test_other_reference_models_compile(rel, reference_dir):
+    t = compile_mjcf(reference_dir / rel)
     assert t.nq > 0 and t.nbody > 1
     assert t.nq == sum({JNT_FREE: 7, JNT_BALL: 4}.get(int(x), 1) for x in t.jnt_type)

@@ -93,6 +93,8 @@ typedef struct stac_model stac_model; /* opaque */
 
 /* Thread-local description of the last error returned on this thread ("" if none). */
 const char *stac_last_error(void);
+/* Its status code (STAC_ERR_*; 0 if none): what a NULL from stac_model_create does not carry. */
+int32_t stac_last_error_code(void);
 int32_t stac_abi_version(void);
 /* Number of visible GPUs (0 if none); does not initialise a device. */
 int32_t stac_device_count(void);

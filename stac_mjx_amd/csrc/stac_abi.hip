@@ -40,8 +40,10 @@ hipError_t launch_chain_order(const float *kp, int C, int F, int K, const float 
 using namespace stac;
 
 static thread_local std::string g_err;
+static thread_local int32_t g_err_code = 0;
 static int fail(int code, const std::string &msg) {
     g_err = msg;
+    g_err_code = code;
     return code;
 }
 #define HIP_TRY(expr)                                                                              \
@@ -231,6 +233,7 @@ static int ensure_scratch(stac_model *m, size_t floats) {
 }
 
 extern "C" const char *stac_last_error(void) { return g_err.c_str(); }
+extern "C" int32_t stac_last_error_code(void) { return g_err_code; }
 extern "C" int32_t stac_abi_version(void) { return STAC_HIP_ABI_VERSION; }
 extern "C" int32_t stac_device_count(void) {
     int n = 0;
@@ -1111,6 +1114,7 @@ extern "C" stac_model *stac_model_create(const stac_model_tables *t) {
         return nullptr;
     }
     g_err.clear();
+    g_err_code = 0;
     return m;
 }
 

@@ -50,7 +50,7 @@ _LIB = None
 
 # every symbol include/stac_hip.h declares
 ABI_SYMBOLS = (
-    "stac_last_error", "stac_abi_version", "stac_device_count", "stac_model_create", "stac_model_destroy",
+    "stac_last_error", "stac_last_error_code", "stac_abi_version", "stac_device_count", "stac_model_create", "stac_model_destroy",
     "stac_model_info", "stac_set_site_pos", "stac_get_site_pos", "stac_fk", "stac_q_solve", "stac_q_phase",
     "stac_m_phase_workspace_floats", "stac_m_phase_partial", "stac_m_phase_finish",
 )  # fmt: skip
@@ -76,6 +76,7 @@ def load_library(path: Path | None = None):
         raise StacHipError(f"{p} exports ABI version {got}, this binding needs {ABI_VERSION}: rebuild with "
                            "`python -m stac_mjx_amd.build`")
     lib.stac_last_error.restype = C.c_char_p
+    lib.stac_last_error_code.restype = C.c_int32
     lib.stac_model_create.restype = C.c_void_p
     lib.stac_model_create.argtypes = [C.POINTER(StacModelTables)]
     lib.stac_model_destroy.argtypes = [C.c_void_p]
@@ -147,7 +148,7 @@ class Engine:
             setattr(t, name, arr.ctypes.data_as(ctype))
         self._h = self.lib.stac_model_create(C.byref(t))
         if not self._h:
-            raise StacHipError("stac_model_create failed: " + self._err())
+            raise StacHipError(f"stac_model_create failed: libstac_hip error {self.lib.stac_last_error_code()}: {self._err()}")
         info = (C.c_int32 * 8)()
         self._check(self.lib.stac_model_info(self._h, info))
         self.info = dict(zip(("nbody", "njnt", "nq", "K", "n_active_bodies", "n_active_joints", "n_levels", "max_level_width"), info))

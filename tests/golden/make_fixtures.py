@@ -27,14 +27,23 @@ Fixtures are DATA only (inputs / expected outputs / compiled model tables), no r
                             under /opt/conda/bin/python3.9 (the interpreter of this image that has h5py).
   oracle_regress.npz        outputs of THIS repo's oracle on a few real frames (regression pin of the
                             oracle itself; not a reference pin).
+  synth_tables.npz / synth_model_cfg.json / synth_kp_1.npy
+                            the reference's CI smoke case (stac=stac_synth_data model=synth_data): synth_model.xml (one
+                            body, a free joint) with the keypoint site of configs/model/synth_data.yaml; the model group
+                            under "model" and the stac group of configs/stac/stac_synth_data.yaml under "stac"; the one
+                            frame of tests/data/test_synth_1_frames.nwb through load_data semantics, float32 [1, 3] (read
+                            under /opt/conda/bin/python3.9 like the mouse mocap).  Written deterministically (fixed zip
+                            timestamps), so that `--only synth` reproduces them byte for byte.
 """
 
 from __future__ import annotations
 
 import argparse
+import io
 import json
 import pickle
 import sys
+import zipfile
 from pathlib import Path
 
 import numpy as np
@@ -63,11 +72,54 @@ class _JaxFreeUnpickler(pickle.Unpickler):
         return super().find_class(module, name)
 
 
+def _save_npz_deterministic(path, arrays):
+    """np.savez_compressed with a fixed member timestamp: the same arrays give the same bytes."""
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_DEFLATED) as zf:
+        for k, v in arrays.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(v), allow_pickle=False)
+            zi = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            zi.compress_type = zipfile.ZIP_DEFLATED
+            zf.writestr(zi, buf.getvalue())
+
+
+def synth_fixtures(ref: Path):
+    """The reference's CI smoke case: one body with a free joint (nq = 7), one keypoint, one frame."""
+    import subprocess
+
+    import yaml
+
+    model = yaml.safe_load(open(ref / "configs" / "model" / "synth_data.yaml"))
+    stac = yaml.safe_load(open(ref / "configs" / "stac" / "stac_synth_data.yaml"))
+    names = list(model["KEYPOINT_MODEL_PAIRS"].keys())
+    fs = build_fit_setup(ref / model["MJCF_PATH"], model, names)
+    assert (fs.tables.nq, fs.tables.nsite) == (7, 1)
+    _save_npz_deterministic(HERE / "synth_tables.npz", fs.tables.to_npz_dict())
+    with open(HERE / "synth_model_cfg.json", "w") as fh:
+        json.dump({"model": model, "stac": stac}, fh, indent=1)
+        fh.write("\n")
+    code = (
+        "import sys, json; sys.path.insert(0, sys.argv[1]); import numpy as np\n"
+        "from stac_mjx_amd import io; from stac_mjx_amd.config import validate_config\n"
+        "c = json.load(open(sys.argv[1] + '/tests/golden/synth_model_cfg.json'))\n"
+        "cfg = validate_config({'model': c['model'], 'stac': dict(c['stac'], continuous=False)})\n"
+        "kp, names = io.load_data(cfg, sys.argv[2])\n"
+        "assert kp.shape == (1, 3) and kp.dtype == np.float32 and names == list(c['model']['KEYPOINT_MODEL_PAIRS'].keys())\n"
+        "np.save(sys.argv[3], kp)\n")
+    subprocess.run(["/opt/conda/bin/python3.9", "-c", code, str(ROOT), str(ref), str(HERE / "synth_kp_1.npy")], check=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reference", default="/root/reference")
+    ap.add_argument("--only", choices=("all", "synth"), default="all",
+                    help="synth: write only the three synth fixtures (the others carry zip timestamps)")
     args = ap.parse_args()
     ref = Path(args.reference)
+    if args.only == "synth":
+        synth_fixtures(ref)
+        print("synth fixtures written to", HERE)
+        return
 
     # 1. stored reference output -------------------------------------------------------------
     with open(ref / "demos" / "demo_viz.p", "rb") as fh:
@@ -140,6 +192,9 @@ def main():
     out = orc.ik_clips(clips, fsr.lb, fsr.ub, fsr.part_masks, fsr.trunk_kps, fsr.root_kp_idx, fsr.root_dims)
     np.savez_compressed(HERE / "oracle_regress.npz", kp=clips, qpos=out["qpos"], marker_sites=out["marker_sites"],
                         frame_error=out["frame_error"], counters=out["counters"])
+
+    # 6. the reference's CI smoke case (synth) ----------------------------------------------------
+    synth_fixtures(ref)
     print("fixtures written to", HERE)
 
 

@@ -724,11 +724,12 @@ def test_lm_chain_queue_same_as_static_assignment(rodent_setup, rodent_mocap, mo
 
 
 # ---- random models: the plan builder (levels, positions, stored transforms, step program) on arbitrary trees ------------
-def _random_tables(rng, nbody, free_root, p_slide=0.1, p_ball=0.0, max_children_bias=0.6, lean=False, k_max=12, p_oriented=None):
+def _random_tables(rng, nbody, free_root, p_slide=0.1, p_ball=0.0, max_children_bias=0.6, lean=False, k_max=12, p_oriented=None, k_min=3):
     """A random kinematic tree as ModelTables: depth-first body order, 0-3 joints per body (mostly hinges, some with
     jnt_pos == 0, some slides / balls), random body orientations (some identity), sites on random bodies.
     lean: what the lean kernels' split kinematics take -- only hinges below the (free) root; some bodies with body_pos == 0;
-    oriented bodies only on request (p_oriented: round 6 -- one more product of the quaternion pass each)."""
+    oriented bodies only on request (p_oriented: round 6 -- one more product of the quaternion pass each).
+    nbody >= 2 (nbody = 2: the root body alone); k_min .. k_max - 1 sites."""
     from stac_mjx_amd.mjcf import JNT_BALL, JNT_FREE, JNT_HINGE, JNT_SLIDE, ModelTables
 
     parent = [0] * nbody
@@ -784,7 +785,7 @@ def _random_tables(rng, nbody, free_root, p_slide=0.1, p_ball=0.0, max_children_
                 qpos0.append(float(rng.normal(0, 0.05)) if rng.random() < 0.3 else 0.0)
                 jrange.append([-1.0, 1.2] if ty == JNT_HINGE else [-0.05, 0.05])
                 nq += 1
-    K = int(rng.integers(3, k_max))
+    K = int(rng.integers(k_min, k_max))
     site_body = np.sort(rng.integers(1, nbody, K)).astype(np.int32)
     return ModelTables(
         nbody=nbody, njnt=len(jt), nq=nq, nsite=K, body_parentid=np.array(parent, np.int32),
@@ -937,20 +938,12 @@ def test_random_oriented_lean_models_do_take_the_lean_kernels():
     assert sum(_random_lean_case(s, p_oriented=0.4) for s in (100, 101, 102)) >= 6  # (three launches per model)
 
 
-def _random_model_case(seed, nbody_lo, nbody_hi, chains, frames, lanes_list, maxiter=10, q_init=False):
-    """One random model through the q_phase at the given lane widths, each launched twice, against the oracle."""
-    from oracle import Oracle
-    from stac_mjx_amd.engine import Engine, StacHipError
-    from stac_mjx_amd.mjcf import JNT_BALL, JNT_FREE, JNT_QPOS_DIMS
+def _box(t):
+    """The box of the random-model tests: free-root and ball quaternions in [-1, 1], hinges / slides their range widened to
+    include 0, the free root's position unbounded."""
+    from stac_mjx_amd.mjcf import JNT_BALL, JNT_FREE
 
-    rng = np.random.default_rng(50000 + seed)
-    free_root = bool(rng.integers(2))
-    t = _random_tables(rng, int(rng.integers(nbody_lo, nbody_hi + 1)), free_root, p_ball=float(rng.choice([0.0, 0.1])),
-                       max_children_bias=float(rng.choice([0.05, 0.3, 0.6, 0.9, 0.97])))
-    nq, K = t.nq, t.nsite
-    if nq == 0:
-        pytest.skip("no joints drawn")
-    lb, ub = np.full(nq, -np.inf, np.float32), np.full(nq, np.inf, np.float32)
+    lb, ub = np.full(t.nq, -np.inf, np.float32), np.full(t.nq, np.inf, np.float32)
     for j in range(t.njnt):
         a, ty = int(t.jnt_qposadr[j]), int(t.jnt_type[j])
         if ty == JNT_FREE:
@@ -959,6 +952,23 @@ def _random_model_case(seed, nbody_lo, nbody_hi, chains, frames, lanes_list, max
             lb[a:a + 4], ub[a:a + 4] = -1, 1
         else:
             lb[a], ub[a] = min(t.jnt_range[j, 0], 0.0), t.jnt_range[j, 1]
+    return lb, ub
+
+
+def _random_model_case(seed, nbody_lo, nbody_hi, chains, frames, lanes_list, maxiter=10, q_init=False, k_min=3, k_max=12, seed0=50000):
+    """One random model through the q_phase at the given lane widths, each launched twice, against the oracle."""
+    from oracle import Oracle
+    from stac_mjx_amd.engine import Engine, StacHipError
+    from stac_mjx_amd.mjcf import JNT_QPOS_DIMS
+
+    rng = np.random.default_rng(seed0 + seed)
+    free_root = bool(rng.integers(2))
+    t = _random_tables(rng, int(rng.integers(nbody_lo, nbody_hi + 1)), free_root, p_ball=float(rng.choice([0.0, 0.1])),
+                       max_children_bias=float(rng.choice([0.05, 0.3, 0.6, 0.9, 0.97])), k_min=k_min, k_max=k_max)
+    nq, K = t.nq, t.nsite
+    if nq == 0:
+        pytest.skip("no joints drawn")
+    lb, ub = _box(t)
     tol = float(rng.choice([1e-5, 1e-3]))
     orc = Oracle(t, tol=tol, maxiter=maxiter)
     n = chains * frames
@@ -1008,6 +1018,20 @@ def test_random_models_large_trees_many_chains(seed):
     """Larger random trees (40-110 bodies: nq up to ~200, the wide instantiations), 70 chains x 2 frames (more chains than a
     workgroup holds; with a carried start pose on odd seeds), every lane width, each launch repeated: HIP == oracle bit for bit."""
     _random_model_case(seed, 40, 110, 70, 2, (8, 16, 32, 64, 0), q_init=bool(seed % 2))
+
+
+# seeds of the small flavour below: ten draws of distinct shapes (free root alone, free root + hinges, one / two / three hinges,
+# ball + slide + hinge, a slide) with one or two sites.  Only seeds 0 and 2 of 0 .. 13 are ruled out (no joint drawn: nothing to
+# solve); 8 and 10 .. 13 repeat shapes already in the list.
+_TINY_SEEDS = [1, 3, 4, 5, 6, 7, 9, 14, 22, 34]
+
+
+@pytest.mark.parametrize("seed", _TINY_SEEDS)
+def test_random_tiny_models_one_or_two_sites(seed):
+    """The smallest models: two or three bodies (the root body alone, or a root with one or two children) and one or two fit
+    sites -- the shapes no other generator draws (K = 1: a one-site loss tree, a one-entry trunk mask; naj == 1) -- at every lane
+    width, each launch repeated, plus the q_solve seam: HIP == oracle bit for bit."""
+    _random_model_case(seed, 2, 3, 5, 2, (4, 8, 16, 32, 64, 0), k_min=1, k_max=3, seed0=70000)
 
 
 # ---- boundary details ---------------------------------------------------------------------------------------------------

@@ -464,3 +464,65 @@ def test_bench_fit_and_run_modes_two_ranks_on_one_gpu(args):
     assert d["n_gpus"] == 2 and d["value"] > 0
     if args[1] == "fit":
         assert d["config"]["collective_backend"] == "gloo" and d["config"]["collective_world_size"] == 2
+
+
+# ---- the reference's CI smoke case (stac=stac_synth_data model=synth_data) ---------------------------------------------------
+_SYNTH_WIDTHS = [(4, {}), (8, {}), (16, {}), (32, {}), (64, {}), (0, {}),
+                 (0, {"STAC_HIP_SPEC": "1", "STAC_HIP_SPECG": "8"}), (0, {"STAC_HIP_SPEC": "1", "STAC_HIP_SPECG": "16"}),
+                 (0, {"STAC_HIP_SPEC": "1", "STAC_HIP_SPECG": "32"}), (0, {"STAC_HIP_SPEC": "1", "STAC_HIP_SPECG": "64"})]
+
+
+@pytest.mark.parametrize("lanes,env", _SYNTH_WIDTHS, ids=lambda v: str(v) if not isinstance(v, dict) else
+                         "-".join(f"{k[9:]}{x}" for k, x in v.items()) or "auto")
+def test_synth_data_ci_case(monkeypatch, lanes, env):
+    """The reference CI's smoke run: one body with a free joint (nq = 7), one keypoint, one frame, N_ITERS = 1 and
+    N_SAMPLE_FRAMES = 1, a part list that matches no joint (one all-false part mask).  fit_offsets against the oracle-driven
+    restatement, and ik_only on the same frame with PG and with LM (K = 1, nq = 7: rank-deficient normal equations) against their
+    oracle statements -- bit for bit, at every lane width and latency mode the host accepts."""
+    import json
+
+    from oracle import Oracle
+    from stac_mjx_amd.config import validate_config
+    from stac_mjx_amd.fit_model import finish_fit_setup
+    from stac_mjx_amd.mjcf import ModelTables
+    from stac_mjx_amd.stac import Stac
+
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    c = json.load(open(GOLDEN / "synth_model_cfg.json"))
+    cfgm = c["model"]
+    names = list(cfgm["KEYPOINT_MODEL_PAIRS"].keys())
+    fs = finish_fit_setup(ModelTables.load(GOLDEN / "synth_tables.npz"), cfgm, names)
+    kp = np.load(GOLDEN / "synth_kp_1.npy")
+    # the preconditions that make this the CI case
+    assert (fs.tables.nq, fs.tables.nsite, kp.shape) == (7, 1, (1, 3))
+    assert fs.part_masks.shape == (1, 7) and not fs.part_masks.any()
+    assert fs.root_kp_idx == 0 and fs.do_root_opt and fs.root_dims == 7
+    assert int(cfgm["N_ITERS"]) == 1 and int(cfgm["N_SAMPLE_FRAMES"]) == 1
+    for solver in ("pg", "lm"):
+        stac_cfg = dict(c["stac"], continuous=False, skip_ik_only=False, lanes_per_chain=lanes, solver=solver, lm_maxiter=20)
+        cfg = validate_config({"model": dict(cfgm), "stac": stac_cfg})
+        stac = Stac(None, cfg, names, setup=fs, verbose=False)
+        if solver == "pg":
+            data = stac.fit_offsets(kp)
+            ref_off, ref = _oracle_fit_offsets(fs, cfgm, kp, 1)
+            np.testing.assert_array_equal(data.offsets, ref_off)
+            np.testing.assert_array_equal(data.qpos, ref["qpos"])
+            np.testing.assert_array_equal(data.marker_sites, ref["marker_sites"])
+            np.testing.assert_array_equal(data.xpos, ref["xpos"])
+            np.testing.assert_array_equal(data.xquat, ref["xquat"])
+            off = data.offsets
+        ik = stac.ik_only(kp, off)
+        orc = Oracle(fs.tables, tol=float(cfgm["FTOL"]), maxiter=int(cfgm["N_ITER_Q"]))
+        orc.set_site_pos(off)
+        args = (kp.reshape(1, 1, 3), fs.lb, fs.ub, fs.part_masks, fs.trunk_kps, fs.root_kp_idx, fs.root_dims)
+        if solver == "lm":  # (the bound the engine runs with: the validated config's, not a copy of its default)
+            assert stac.engine.phase_params.maxiter == int(cfg.stac.lm_maxiter) == 20
+        r = orc.ik_clips(*args) if solver == "pg" else orc.ik_clips_lm(*args, maxiter=int(cfg.stac.lm_maxiter))
+        np.testing.assert_array_equal(ik.qpos, r["qpos"].reshape(1, 7))
+        np.testing.assert_array_equal(ik.marker_sites, r["marker_sites"].reshape(1, 1, 3))
+        np.testing.assert_array_equal(ik.xpos, r["xpos"].reshape(1, 2, 3))
+        np.testing.assert_array_equal(ik.offsets, off)
+        stac.engine.close()
+    # the fit puts the marker on the target (what the oracle does on this case)
+    assert np.abs(ik.marker_sites.reshape(3) - kp.reshape(3)).max() < 1e-3

@@ -70,9 +70,53 @@ def _fd_grad(o64, q, kp, qs, ks, h=1e-4):
     return g
 
 
-@pytest.mark.parametrize("which", ["all", "part", "trunk"])
-def test_gradient_matches_finite_differences(rodent_setup_legacy, demo_viz, which):
-    fs = rodent_setup_legacy
+def _small_fd_case(which):
+    """The smallest models, with a pose and targets: the reference CI's synth model (one body, a free joint, one site), one hinge
+    under a fixed root, a slide root (three slides and a hinge), and the ball / slide tree with one or two sites."""
+    from conftest import GOLDEN
+    from helpers import _edge_tables
+    from stac_mjx_amd.mjcf import ModelTables, compile_mjcf
+
+    rng = np.random.default_rng(len(which))
+    if which == "synth":
+        t = ModelTables.load(GOLDEN / "synth_tables.npz")
+        kp = np.load(GOLDEN / "synth_kp_1.npy")[0]
+    elif which == "hinge1":
+        t = _edge_tables(1, 1, free_root=False)
+    elif which == "slide_root":
+        t = _edge_tables(4, 2, free_root=False, slide_root=True)
+    else:
+        K = int(which[-1])
+        sites = "".join(f'<site name="s{i}" pos="0.05 {0.02 * i} 0.1"/>' for i in range(K))
+        t = compile_mjcf(f"""
+        <mujoco><compiler angle="radian"/><worldbody>
+          <body name="r" pos="0 0 0.5"><freejoint/>
+            <body name="a" pos="0.2 0 0" quat="0.9 0.1 0.2 0.3"><joint name="ball" type="ball" pos="0.01 0.02 0"/>
+              <body name="b" pos="0 0.2 0"><joint name="sl" type="slide" axis="1 1 0"/><joint name="h" axis="0 1 1" pos="0 0 .1"/>
+                {sites}</body></body></body>
+        </worldbody></mujoco>""", from_string=True)
+        assert (t.nq, t.nsite) == (13, K)
+    q = t.qpos0 + rng.normal(0, 0.2, t.nq).astype(np.float32)
+    if which != "synth":
+        kp = rng.normal(0, 0.3, 3 * t.nsite).astype(np.float32)
+    return t, q, kp
+
+
+@pytest.mark.parametrize("which", ["all", "part", "trunk", "synth", "hinge1", "slide_root", "ball_slide_K1", "ball_slide_K2"])
+def test_gradient_matches_finite_differences(request, which):
+    if which not in ("all", "part", "trunk"):
+        # the f64 oracle's analytic gradient against central differences at the smallest shapes (K = 1 / 2, nq = 1 / 4 / 7)
+        t, q, kp = _small_fd_case(which)
+        o64, o32 = Oracle(t, precision="f64"), Oracle(t)
+        qs, ks = np.ones(t.nq, bool), np.ones(3 * t.nsite, bool)
+        loss, g = o64.q_loss(q, kp, qs, ks, q)
+        gfd = _fd_grad(o64, q, kp, qs, ks)
+        assert np.any(g != 0)
+        assert np.abs(g - gfd).max() <= 5e-6 * max(1.0, np.abs(g).max()), np.abs(g - gfd)
+        l32, g32 = o32.q_loss(q, kp, qs, ks, q)
+        assert abs(l32 - loss) <= 1e-6 * max(1.0, loss) and np.abs(g32 - g).max() <= 5e-6 * max(1.0, np.abs(g).max())
+        return
+    fs, demo_viz = request.getfixturevalue("rodent_setup_legacy"), request.getfixturevalue("demo_viz")
     o64, o32 = Oracle(fs.tables, precision="f64"), Oracle(fs.tables)
     for o in (o64, o32):
         o.set_site_pos(demo_viz["offsets"])

@@ -31,6 +31,7 @@
 
 #include "stac_plan.hpp"
 #include "stac_device.hpp"
+#include "stac_shapes.hpp"
 
 #ifndef STAC_RT
 #define STAC_RT 12  // sites per trip of a latency kernel's range sum (measured 6 / 8 / 12 / 16 / 24: 19.24 / 19.20 / 19.33 / 18.72 / 17.62 k frames/s on 40 x 250)
@@ -63,7 +64,7 @@ namespace stac {
 // SPECP = SPEC | 1: the LEAN kernels -- the same kernel with the launch-wide choices of the common case (phase mode, not a single
 // solve; a free root joint at qpos 0 .. 6; the uniform four-lanes-per-position FK program with 12-word records; every site in
 // registers; no developer flags) as compile-time constants inside the trip loop: the other paths drop out of the loop body
-// (10 % fewer instructions, no scalar spills).  The host takes it when all of that holds (launch_q_phase); same bits.
+// (10 % fewer instructions, no scalar spills).  The host takes it when all of that holds (plan_q); same bits.
 template <int G, int NQR, int WPE, int SPECP>
 __global__ __launch_bounds__(WPE == 3 ? 768 : 512) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 void q_phase_kernel(const QArgs a_in) {
@@ -84,7 +85,7 @@ void q_phase_kernel(const QArgs a_in) {
 
     // ---- stage the plan into LDS (shared by the block's wavefronts) ------------------------------------
     // The launch stages the words [plan_skip, total_words) of the blob; the host has rebased every off_* of this launch's
-    // header to the first staged word (run_q), so P is the LDS base itself -- never a pointer in front of it: a lambda
+    // header to the first staged word (plan_q), so P is the LDS base itself -- never a pointer in front of it: a lambda
     // that the compiler does not inline reads through a flat pointer, and below the LDS aperture that is a fault.
     float *P = lds;
     for (int i = threadIdx.x; i < H.total_words - H.plan_skip; i += blockDim.x) {
@@ -491,7 +492,7 @@ void q_phase_kernel(const QArgs a_in) {
 #ifndef STAC_NO_PIN
         TripArgs a_t = trip_args<kVPin>(hot_a, *ak_t);
         TripHeader H_t = trip_header<kVPin>(hot_h, ak_t->h);
-        if constexpr (LEAN) {  // (what the host has checked for this launch: launch_q_phase)
+        if constexpr (LEAN) {  // (what the host has checked for this launch: plan_q)
             a_t.single = 0; a_t.flags = 0; a_t.free0p = 1;
             H_t.fk_uniform = 1; H_t.fk_rec_words = 12;
             __builtin_assume(4 * H_t.max_width <= G);
@@ -1038,7 +1039,7 @@ void q_phase_kernel(const QArgs a_in) {
         };
         // (B) one joint: its range's wrench, then the joint formulas; crefx = the root position the moments refer to
         // (lean kernels: the joints this is called for -- all but the free root, which has its own path -- are hinges: the host has
-        //  checked that the model has no ball joint and that its FK program is uniform, launch_q_phase)
+        //  checked that the model has no ball joint and that its FK program is uniform, plan_q)
         constexpr bool LEAN_HINGES = LEAN && SPEC == 0;  // (the latency kernels pass the free root through here as well)
         auto joint_gradient = [&](const int j, float *CBx, const V3 crefx, float *ggx, const bool pinned = false) {
             const float *jax_ = CBx + H.c_ja, *qsvx = CBx + H.c_qsv, *jnx = CBx + H.c_jn;
@@ -1953,122 +1954,24 @@ static hipError_t launch_q(const QArgs &a, int wpb, size_t lds_bytes, hipStream_
     return hipGetLastError();
 }
 
-// ---- the instantiations that ship -------------------------------------------------------------------------------------------
-// (lanes per chain G, solver registers per lane NQR: nq <= G * NQR, register cap WPE).  Every shape here passes the resource
-// gate of tests/test_isa_hazards.py (scratch <= 64 B per lane, <= 40 scalars spilled into vector lanes; table:
-// profiles/r04/resource_usage.txt).  What does not is not built: the 128-VGPR variants of the 8- and 16-lane kernels (74 to 750
-// spilled vector registers) and of the 32- / 64-lane kernels with four or more solver registers per lane (17 to 80), 32 solver registers per lane at 4 or 8 lanes and the 4-lane kernels altogether (160 B to 1.3 KB of
-// scratch; never chosen automatically, slower than 16 lanes at every batch size) -- a request for them runs on the next wider
-// group, results are the same bit for bit.  Latency kernels stop at 10 solver registers per lane at 8 lanes and 8 at 16 or 32
-// (round 3: the wider ones, 300+ B of scratch, read spill slots before writing them); wider models take more lanes per role.
-#ifdef STAC_INST_SUBSET  // developer builds (experiments): only the shapes of the default bench and of its 250-frame-clip leg
-#define STAC_Q_SHAPES(X) X(16, 5, 2) X(16, 5, 3)
-#define STAC_Q_LEAN_SHAPES(X) X(16, 5, 3)
-#define STAC_Q_SPEC_LEAN_SHAPES(X) X(16, 5, 4) X(16, 5, 8) X(32, 3, 8)
-#define STAC_Q_SPEC_SHAPES(X) X(16, 5, 4) X(32, 3, 8)
-#else
-// lean kernels (SPECP bit 0): the shapes that rodent-sized models run in -- large batches, the straggler hand-off, few long clips
-// (the first shape of a width that holds nq is taken: narrower ones first.  Three solver registers per lane at 16 lanes, two at 32: models of
-//  up to 48 / 64 coordinates -- the fruit fly's 43 --, whose nq-sums and staging then run over three registers instead of five)
-#define STAC_Q_LEAN_SHAPES(X) X(16, 3, 3) X(16, 5, 2) X(16, 5, 3) X(32, 3, 2) X(32, 8, 2)
-#define STAC_Q_SPEC_LEAN_SHAPES(X) X(16, 3, 4) X(16, 5, 4) X(16, 5, 8) X(32, 2, 8) X(32, 3, 8) X(32, 8, 8)
-#define STAC_Q_SHAPES(X)                                                        \
-    X(8, 10, 2) X(8, 16, 2)                                                      \
-    X(16, 5, 2) X(16, 5, 3) X(16, 8, 2) X(16, 8, 3) X(16, 16, 2)                 \
-    X(32, 3, 2) X(32, 3, 4) X(32, 4, 2) X(32, 8, 2)                              \
-    X(64, 2, 2) X(64, 2, 4) X(64, 4, 2)
-// (G lanes per role, NQR, roles per chain)
-#define STAC_Q_SPEC_SHAPES(X)                                                   \
-    X(8, 10, 4) X(8, 10, 8) X(16, 5, 4) X(16, 8, 4) X(32, 3, 8) X(32, 8, 8) X(64, 2, 8) X(64, 4, 8)
-#endif
-
-// Is there a throughput instantiation with G lanes per chain and register cap wpe that holds nq coordinates?
-bool q_phase_has_variant(int G, int nq, int wpe) {
-#define STAC_HAS(GG, RR, WW) if (G == GG && wpe == WW && nq <= GG * RR) return true;
-    STAC_Q_SHAPES(STAC_HAS)
-#undef STAC_HAS
-    return false;
-}
-
-// Is there a lean instantiation (SPECP bit 0) for this shape?  spec = 0: throughput kernel with register cap wpe; else the latency
-// kernel with `spec` roles of G lanes.
-bool q_phase_has_lean_variant(int G, int nq, int wpe, int spec) {
-    if (spec) {
-#define STAC_HAS(GG, RR, NRR) if (G == GG && spec == NRR && nq <= GG * RR) return true;
-        STAC_Q_SPEC_LEAN_SHAPES(STAC_HAS)
-#undef STAC_HAS
-        return false;
-    }
-#define STAC_HAS(GG, RR, WW) if (G == GG && wpe == WW && nq <= GG * RR) return true;
-    STAC_Q_LEAN_SHAPES(STAC_HAS)
-#undef STAC_HAS
-    return false;
-}
-// The launch-wide choices the lean kernels have compiled in (q_phase_kernel, SPECP bit 0): phase mode with the model's own box, only
-// hinges below a free root at qpos 0 .. 6 (QArgs::flags == 16: set_hinges_flag, no developer flag), the split kinematics
-// (PlanHeader::fk3: stac_plan.hpp), every site in registers at this group width.  The host decides with it which chain layout
-// the launch gets (run_q) and passes its decision to launch_q_phase.
-// solver registers per lane of the lean instantiation that holds nq at this width (the same for every register cap / role count); 0: none
-int q_phase_lean_nqr(int G, int nq) {
-    int nqr = 0;
-#define STAC_NQR(GG, RR, WW) if (G == GG && nq <= GG * RR && (nqr == 0 || RR < nqr)) nqr = RR;
-    STAC_Q_LEAN_SHAPES(STAC_NQR)
-    STAC_Q_SPEC_LEAN_SHAPES(STAC_NQR)
-#undef STAC_NQR
-    return nqr;
-}
-// ... and does it hold the model's K sites in registers?  (what the width heuristics of the host need to know before a launch exists)
-bool q_phase_lean_holds(int G, int nq, int K) {
-    const int nqr = q_phase_lean_nqr(G, nq);
-    return nqr > 0 && K <= lean_site_rounds(G, nqr) * G;
-}
-bool q_phase_lean_conditions(const QArgs &a, int G) {
-    const int nqr = q_phase_lean_nqr(G, a.h.nq);
-    return !a.single && !a.bounds && a.flags == 16 && a.free0p == 1 && a.h.fk3 == 1 && nqr > 0 && a.h.K <= lean_site_rounds(G, nqr) * G &&
-           a.h.nqj == 1 && !a.h.has_ball && G >= 16;
-}
-
-// wpb = wavefronts per workgroup (they share the plan copy), wpe = register-cap variant (2, 3 or 4 wavefronts per SIMD; the
-// nearest one that exists for G is taken), spec = evaluation roles per chain in latency mode (0 = throughput mode).
-// lean: the launch carries the lean chain layout (the host has checked q_phase_lean_conditions and that the shape exists).
-// *capacity_out = G * NQR of the instantiation that ran, 0 if none holds nq at this G.
-hipError_t launch_q_phase(const QArgs &a, int G, int wpb, int wpe, int spec, size_t lds_bytes, hipStream_t s,
-                          int *capacity_out, bool lean) {
-    const int nq = a.h.nq;
-    *capacity_out = 0;
-    if (lean && !(q_phase_lean_conditions(a, G) && q_phase_has_lean_variant(G, nq, wpe, spec))) return hipErrorInvalidValue;
-    if (spec) {
-#define STAC_TRY_SPEC_LEAN(GG, RR, NRR)                             \
-    if (lean && G == GG && spec == NRR && nq <= GG * RR) {          \
-        *capacity_out = GG * RR;                                    \
-        return launch_q<GG, RR, 2, NRR | 1>(a, wpb, lds_bytes, s);  \
-    }
-        STAC_Q_SPEC_LEAN_SHAPES(STAC_TRY_SPEC_LEAN)
-#undef STAC_TRY_SPEC_LEAN
-#define STAC_TRY_SPEC(GG, RR, NRR)                                  \
-    if (G == GG && spec == NRR && nq <= GG * RR) {                  \
-        *capacity_out = GG * RR;                                    \
-        return launch_q<GG, RR, 2, NRR>(a, wpb, lds_bytes, s);      \
-    }
-        STAC_Q_SPEC_SHAPES(STAC_TRY_SPEC)
-#undef STAC_TRY_SPEC
-        return hipErrorInvalidValue;
-    }
-    if (!lean && !q_phase_has_variant(G, nq, wpe)) wpe = 2;  // (every G has its 2-per-SIMD variants)
-#define STAC_TRY_LEAN(GG, RR, WW)                                   \
-    if (lean && G == GG && wpe == WW && nq <= GG * RR) {            \
-        *capacity_out = GG * RR;                                    \
-        return launch_q<GG, RR, WW, 1>(a, wpb, lds_bytes, s);       \
-    }
-    STAC_Q_LEAN_SHAPES(STAC_TRY_LEAN)
-#undef STAC_TRY_LEAN
-#define STAC_TRY(GG, RR, WW)                                        \
-    if (G == GG && wpe == WW && nq <= GG * RR) {                    \
-        *capacity_out = GG * RR;                                    \
-        return launch_q<GG, RR, WW, 0>(a, wpb, lds_bytes, s);       \
-    }
-    STAC_Q_SHAPES(STAC_TRY)
-#undef STAC_TRY
+// Launches exactly the instantiation `i` (stac_shapes.hpp: the host plans it, stac_abi.hip, plan_q); anything else is refused.
+// wpb = wavefronts per workgroup (they share the plan copy).
+hipError_t launch_q_phase(const QArgs &a, const QInst &i, int wpb, size_t lds_bytes, hipStream_t s) {
+#define STAC_INST(GG, RR, WW, SP) \
+    if (i.G == GG && i.nqr == RR && i.wpe == WW && i.specp == (SP)) return launch_q<GG, RR, WW, SP>(a, wpb, lds_bytes, s);
+#define STAC_SPEC_LEAN(GG, RR, NRR) STAC_INST(GG, RR, 2, NRR | 1)
+#define STAC_SPEC(GG, RR, NRR) STAC_INST(GG, RR, 2, NRR)
+#define STAC_LEAN(GG, RR, WW) STAC_INST(GG, RR, WW, 1)
+#define STAC_GENERIC(GG, RR, WW) STAC_INST(GG, RR, WW, 0)
+    STAC_Q_SPEC_LEAN_SHAPES(STAC_SPEC_LEAN)
+    STAC_Q_SPEC_SHAPES(STAC_SPEC)
+    STAC_Q_LEAN_SHAPES(STAC_LEAN)
+    STAC_Q_SHAPES(STAC_GENERIC)
+#undef STAC_GENERIC
+#undef STAC_LEAN
+#undef STAC_SPEC
+#undef STAC_SPEC_LEAN
+#undef STAC_INST
     return hipErrorInvalidValue;
 }
 

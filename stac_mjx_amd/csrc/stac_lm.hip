@@ -17,6 +17,7 @@
 
 #include "stac_device.hpp"
 #include "stac_plan.hpp"
+#include "stac_shapes.hpp"
 
 namespace stac {
 
@@ -624,23 +625,13 @@ static hipError_t launch_lm(const QArgs &a, const LmArgs &L, int wpb, size_t lds
     return hipGetLastError();
 }
 
-// Register caps: the 64-lane instantiations fit 168 VGPRs (3 waves per SIMD), the narrower ones need 2 per SIMD.
-hipError_t launch_q_phase_lm(const QArgs &a, const LmArgs &L, int G, int wpb, size_t lds_bytes, hipStream_t s,
-                             int *capacity_out) {
-    const int nq = a.h.nq;
-    *capacity_out = 0;
-#define STAC_TRY(GG, RR, WW)                                    \
-    if (G == GG && nq <= GG * RR) {                             \
-        *capacity_out = GG * RR;                                \
-        return launch_lm<GG, RR, WW>(a, L, wpb, lds_bytes, s);  \
-    }
-    STAC_TRY(16, 5, 2) STAC_TRY(16, 8, 2) STAC_TRY(16, 16, 2)
-    STAC_TRY(32, 3, 2) STAC_TRY(32, 8, 2)
-    STAC_TRY(64, 2, 3) STAC_TRY(64, 4, 2)
+// Launches exactly the instantiation `i` = {G, NQR, waves per SIMD} of STAC_LM_SHAPES (stac_shapes.hpp); anything else is refused.
+hipError_t launch_q_phase_lm(const QArgs &a, const LmArgs &L, const QInst &i, int wpb, size_t lds_bytes, hipStream_t s) {
+#define STAC_TRY(GG, RR, WW) \
+    if (i.G == GG && i.nqr == RR && i.wpe == WW && i.specp == 0) return launch_lm<GG, RR, WW>(a, L, wpb, lds_bytes, s);
+    STAC_LM_SHAPES(STAC_TRY)
 #undef STAC_TRY
     return hipErrorInvalidValue;
 }
-
-int lm_waves_per_simd(int G, int nq) { return (G == 64 && nq <= 128) ? 3 : 2; }
 
 }  // namespace stac

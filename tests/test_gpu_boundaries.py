@@ -4,7 +4,7 @@ kernels' arithmetic.
 
 Each case names a model (`_edge_tables`: exactly nq coordinates and K fit sites), the lane width / developer switches of the
 launch, and what must happen: the instantiation `stac_debug_last_q_kernel` reports after the q_phase (G, NQR, WPE, SPECP), or a
-refusal with STAC_ERR_CAPACITY (-3) -- at model creation or at the launch.  The edges (stac_kernels.hip, the STAC_Q_*SHAPES
+refusal with STAC_ERR_CAPACITY (-3) -- at model creation or at the launch.  The edges (stac_shapes.hpp, the STAC_Q_*SHAPES
 tables: a shape holds nq <= G * NQR; the lean kernels hold K <= lean_site_rounds(G, NQR) * G sites in registers; stac_abi.hip:
 K <= 4096, P + 3 <= kMaxKinds, LM n <= 192, latency roles of 8 lanes up to nq = 80 and of 16 up to 128) are listed with the
 cases; test_every_shape_edge_has_cases (CPU) fails when a shape is added to the tables without cases on both sides of its edge.
@@ -138,7 +138,7 @@ _EDGE_CASES = [
     ("lean16-K33", 40, 33, FREE, 16, THR2, None, (16, 5, 2, 0)),
     ("lean32-K32", 40, 32, FREE, 32, THR2, None, (32, 3, 2, 1)),
     ("lean32-K33", 40, 33, FREE, 32, THR2, None, (32, 3, 2, 0)),
-    ("lat32lean-K32", 40, 32, FREE, 0, _lat(32), None, (32, 2, 2, 9)),   # q_phase_lean_nqr(32, 40) = 2: the advisor's note
+    ("lat32lean-K32", 40, 32, FREE, 0, _lat(32), None, (32, 2, 2, 9)),   # (32, 2, 8) of the latency lean table holds 40: NQR 2
     ("lat32lean-K33", 40, 33, FREE, 0, _lat(32), None, (32, 3, 2, 8)),
     ("lean32wide-K64", 120, 64, FREE, 32, THR2, None, (32, 8, 2, 1)),
     ("lean32wide-K65", 120, 65, FREE, 32, THR2, None, (32, 4, 2, 0)),    # (generic: <32,4,*> holds 120)
@@ -470,8 +470,8 @@ def test_edge_builder_has_the_requested_shape(case):
 
 
 def _shape_tables():
-    """The shipped (not STAC_INST_SUBSET) STAC_Q_*SHAPES tables of stac_kernels.hip: {list name: [(G, NQR, third), ...]}."""
-    src = (ROOT / "stac_mjx_amd" / "csrc" / "stac_kernels.hip").read_text()
+    """The shipped (not STAC_INST_SUBSET) STAC_Q_*SHAPES tables of stac_shapes.hpp: {list name: [(G, NQR, third), ...]}."""
+    src = (ROOT / "stac_mjx_amd" / "csrc" / "stac_shapes.hpp").read_text()
     shipped = src.split("#ifdef STAC_INST_SUBSET", 1)[1].split("#else", 1)[1].split("#endif", 1)[0]
     out = {}
     for m in re.finditer(r"#define (STAC_Q_\w*SHAPES)\(X\)((?:[^\n]*\\\n)*[^\n]*)", shipped):

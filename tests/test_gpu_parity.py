@@ -1215,7 +1215,7 @@ def test_chain_order_and_placement_by_simd_load(rodent_setup, rodent_mocap, monk
 
 
 # ---- round 4: every shipped instantiation, twice -------------------------------------------------------------------------------
-# stac_kernels.hip, STAC_Q_SHAPES / STAC_Q_SPEC_SHAPES and stac_lm.hip: (lanes, registers per lane, register cap / roles).  Each
+# stac_shapes.hpp, STAC_Q_SHAPES / STAC_Q_SPEC_SHAPES and STAC_LM_SHAPES: (lanes, registers per lane, register cap / roles).  Each
 # case forces one instantiation through the developer switches, launches it twice on the same engine and compares with the
 # oracle (PG: bit for bit; LM: finite, repeatable, inside the box, marker error no worse than the PG answer).  The list of
 # kernels this suite launches on a GPU is committed as profiles/r04/gpu_suite_kernels.txt; tests/test_isa_hazards.py checks on

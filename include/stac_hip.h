@@ -157,6 +157,56 @@ int32_t stac_m_phase_finish(const stac_model *m, const float *partial, const flo
                             const float *is_regularized, float reg_coef, float *offsets_out,
                             float *err_out, void *stream);
 
+/* ---- Rendering (DESIGN.md "Rendering"): a ray caster over primitive geoms, keypoints and markers. ------------------
+ * Static primitives (P: the visible model geoms, then the visible model sites) are posed by their body's xpos / xquat;
+ * per frame there are also K keypoint spheres, K marker spheres and, with show_error, K keypoint-to-marker capsules.
+ * Primitive ids: static 0..P-1, keypoint k -> P+k, marker k -> P+K+k, segment k -> P+2K+k.  P + 3K must not exceed
+ * STAC_RENDER_MAX_PRIMS (STAC_ERR_CAPACITY otherwise). */
+#define STAC_RENDER_MAX_PRIMS 512
+#define STAC_RENDER_LAYERS 8 /* transparent hits composited per pixel (the nearest ones) */
+enum { STAC_RENDER_TRANSPARENT = 1, STAC_RENDER_CHECKER = 2, STAC_RENDER_TEXUNIFORM = 4 };
+
+/* HOST pointers, copied at stac_render_scene_create.  prim_type uses mjtGeom values: 0 plane, 2 sphere, 3 capsule,
+ * 4 ellipsoid, 5 cylinder, 6 box. */
+typedef struct stac_render_tables {
+    int32_t nprim;               /* P */
+    const int32_t *prim_type;    /* [P] */
+    const int32_t *prim_body;    /* [P] body id (< nbody of the model) */
+    const int32_t *prim_flags;   /* [P] STAC_RENDER_* bits */
+    const float *prim_size;      /* [P,3] MuJoCo geom size */
+    const float *prim_pos;       /* [P,3] in the body frame */
+    const float *prim_quat;      /* [P,4] in the body frame, w,x,y,z */
+    const float *prim_rgba;      /* [P,4] colour (rgb1 of a checker plane) */
+    const float *prim_rgb2;      /* [P,3] second checker colour */
+    const float *prim_texrepeat; /* [P,2] checker repeat */
+    int32_t nkp;                 /* K: keypoints, markers and segments per frame */
+    const float *kp_rgba;        /* [K,4] */
+    float marker_rgba[4], segment_rgba[4];
+    float marker_radius, segment_radius;
+    int32_t nlight;
+    const float *light_dir;      /* [nlight,3] world direction the light shines along (unit) */
+    const float *light_diffuse;  /* [nlight,3] */
+    float head_ambient[3], head_diffuse[3]; /* headlight (zero when it is off) */
+    float alpha;                 /* opacity of STAC_RENDER_TRANSPARENT primitives */
+    float background[3];
+} stac_render_tables;
+
+typedef struct stac_render_scene stac_render_scene; /* opaque */
+
+/* Uploads the tables to the model's device.  Returns NULL on failure (see stac_last_error / stac_last_error_code). */
+stac_render_scene *stac_render_scene_create(const stac_model *m, const stac_render_tables *t);
+void stac_render_scene_destroy(stac_render_scene *s);
+
+/* Renders N frames of width x height pixels, row 0 at the top.
+ *   xpos[N,nbody,3], xquat[N,nbody,4]: body poses (stac_fk); kp[N,K,3] and markers[N,K,3] may be NULL (not drawn);
+ *   show_error != 0 draws the segments (needs both).  cam[N,12] = {position[3], R[3,3] row-major whose columns are
+ *   the camera's x, y, z axes in world}: the camera looks along -z with y up; tan_half_fovy = tan(fovy / 2), vertical.
+ *   Outputs (each may be NULL): rgb_out[N,H,W,3] uint8, seg_out[N,H,W] int32 (id of the nearest opaque hit or -1),
+ *   depth_out[N,H,W] float (distance along the ray to that hit, +inf for none). */
+int32_t stac_render(const stac_render_scene *s, int32_t N, const float *xpos, const float *xquat, const float *kp,
+                    const float *markers, int32_t show_error, const float *cam, float tan_half_fovy, int32_t width,
+                    int32_t height, uint8_t *rgb_out, int32_t *seg_out, float *depth_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

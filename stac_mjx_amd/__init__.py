@@ -1,7 +1,7 @@
 """stac_mjx_amd -- MI355X-native STAC pose-fitting engine (hot path of talmolab/stac-mjx).
 
 Public API mirrors ``stac_mjx/__init__.py:3-6`` for the hot path: ``load_configs``, ``load_data``,
-``run_stac``; plus ``Stac`` / ``StacCore`` / ``Engine`` for direct use.
+``run_stac``, ``viz_stac``; plus ``Stac`` / ``StacCore`` / ``Engine`` for direct use.
 """
 
 from .config import compose_config, load_configs  # noqa: F401
@@ -23,6 +23,10 @@ def __getattr__(name):  # lazy: these import torch / need the HIP extension
         from . import stac_core
 
         return getattr(stac_core, name)
+    if name in ("viz_stac",):
+        from . import viz
+
+        return viz.viz_stac
     if name in ("run_stac",):
         from . import main
 

@@ -15,6 +15,7 @@
 #include "../../include/stac_hip.h"
 #include "stac_plan.hpp"
 #include "stac_shapes.hpp"
+#include "stac_render.hpp"
 
 namespace stac {
 hipError_t launch_q_phase(const QArgs &a, const QInst &inst, int wpb, size_t lds_bytes, hipStream_t s);
@@ -1934,5 +1935,114 @@ extern "C" int32_t stac_m_phase_finish(const stac_model *m, const float *partial
     DeviceGuard dg(m);
     HIP_TRY(launch_m_finish(m->h.K, partial, initial_offsets, is_regularized, reg_coef, offsets_out, err_out,
                             (hipStream_t)stream));
+    return STAC_OK;
+}
+
+// ---- rendering (stac_render.hip) ------------------------------------------------------------------------------------
+namespace stac { hipError_t launch_render(const RenderScene *S, const RenderCall &C, hipStream_t s); }
+
+struct stac_render_scene {
+    int device = 0;
+    RenderScene S{};               // what d_scene holds (device pointers into d_int / d_float)
+    RenderScene *d_scene = nullptr;
+    int32_t *d_int = nullptr;
+    float *d_float = nullptr;
+};
+
+extern "C" stac_render_scene *stac_render_scene_create(const stac_model *m, const stac_render_tables *t) {
+    if (!m || !t || t->nprim < 0 || t->nkp < 0 || t->nlight < 0 || (t->nprim && (!t->prim_type || !t->prim_body || !t->prim_flags
+        || !t->prim_size || !t->prim_pos || !t->prim_quat || !t->prim_rgba || !t->prim_rgb2 || !t->prim_texrepeat))
+        || (t->nkp && !t->kp_rgba) || (t->nlight && (!t->light_dir || !t->light_diffuse))) {
+        fail(STAC_ERR_INVALID, "stac_render_scene_create: bad argument");
+        return nullptr;
+    }
+    const long total = (long)t->nprim + 3L * t->nkp;
+    if (total > STAC_RENDER_MAX_PRIMS) {
+        fail(STAC_ERR_CAPACITY, "stac_render_scene_create: " + std::to_string(total) + " primitives (P + 3K) exceed STAC_RENDER_MAX_PRIMS = " +
+                                    std::to_string(STAC_RENDER_MAX_PRIMS));
+        return nullptr;
+    }
+    const int P = t->nprim, K = t->nkp, NL = t->nlight;
+    for (int i = 0; i < P; ++i) {
+        const int ty = t->prim_type[i];
+        if (t->prim_body[i] < 0 || t->prim_body[i] >= m->h.nbody || !(ty == 0 || (ty >= 2 && ty <= 6))) {
+            fail(STAC_ERR_INVALID, "stac_render_scene_create: primitive " + std::to_string(i) + " has a bad type or body");
+            return nullptr;
+        }
+    }
+    // int block: type[P] body[P] flags[P]; float block: size[3P] pos[3P] quat[4P] rgba[4P] rgb2[3P] tex[2P] kp_rgba[4K]
+    // light_dir[3NL] light_diff[3NL]
+    std::vector<int32_t> hi;
+    hi.insert(hi.end(), t->prim_type, t->prim_type + P);
+    hi.insert(hi.end(), t->prim_body, t->prim_body + P);
+    hi.insert(hi.end(), t->prim_flags, t->prim_flags + P);
+    std::vector<float> hf;
+    size_t off[8];
+    auto put = [&](int k, const float *p, size_t n) { off[k] = hf.size(); if (n) hf.insert(hf.end(), p, p + n); };
+    put(0, t->prim_size, 3 * (size_t)P); put(1, t->prim_pos, 3 * (size_t)P); put(2, t->prim_quat, 4 * (size_t)P);
+    put(3, t->prim_rgba, 4 * (size_t)P); put(4, t->prim_rgb2, 3 * (size_t)P); put(5, t->prim_texrepeat, 2 * (size_t)P);
+    put(6, t->kp_rgba, 4 * (size_t)K);
+    const size_t off_ld = hf.size();
+    if (NL) hf.insert(hf.end(), t->light_dir, t->light_dir + 3 * (size_t)NL);
+    const size_t off_lc = hf.size();
+    if (NL) hf.insert(hf.end(), t->light_diffuse, t->light_diffuse + 3 * (size_t)NL);
+    DeviceGuard dg(m);
+    auto *sc = new stac_render_scene;
+    sc->device = m->device;
+    auto bail = [&](hipError_t e) {
+        fail(STAC_ERR_HIP, std::string("stac_render_scene_create: ") + hipGetErrorString(e));
+        if (sc->d_int) (void)hipFree(sc->d_int);
+        if (sc->d_float) (void)hipFree(sc->d_float);
+        if (sc->d_scene) (void)hipFree(sc->d_scene);
+        delete sc;
+        return nullptr;
+    };
+    hipError_t e = upload(&sc->d_int, hi.data(), hi.size());
+    if (e != hipSuccess) return bail(e);
+    e = upload(&sc->d_float, hf.data(), hf.size());
+    if (e != hipSuccess) return bail(e);
+    RenderScene &S = sc->S;
+    S.P = P; S.K = K; S.nbody = m->h.nbody; S.nlight = NL;
+    S.prim_type = sc->d_int; S.prim_body = sc->d_int + P; S.prim_flags = sc->d_int + 2 * P;
+    S.prim_size = sc->d_float + off[0]; S.prim_pos = sc->d_float + off[1]; S.prim_quat = sc->d_float + off[2];
+    S.prim_rgba = sc->d_float + off[3]; S.prim_rgb2 = sc->d_float + off[4]; S.prim_tex = sc->d_float + off[5];
+    S.kp_rgba = sc->d_float + off[6]; S.light_dir = sc->d_float + off_ld; S.light_diff = sc->d_float + off_lc;
+    for (int q = 0; q < 4; ++q) { S.marker_rgba[q] = t->marker_rgba[q]; S.seg_rgba[q] = t->segment_rgba[q]; }
+    S.marker_r = t->marker_radius; S.seg_r = t->segment_radius;
+    for (int q = 0; q < 3; ++q) { S.head_amb[q] = t->head_ambient[q]; S.head_diff[q] = t->head_diffuse[q]; S.bg[q] = t->background[q]; }
+    S.alpha = t->alpha;
+    e = upload(&sc->d_scene, &sc->S, 1);
+    if (e != hipSuccess) return bail(e);
+    g_err.clear();
+    g_err_code = 0;
+    return sc;
+}
+
+extern "C" void stac_render_scene_destroy(stac_render_scene *sc) {
+    if (!sc) return;
+    int prev = -1;
+    const bool sw = hipGetDevice(&prev) == hipSuccess && prev != sc->device && hipSetDevice(sc->device) == hipSuccess;
+    (void)hipFree(sc->d_int);
+    (void)hipFree(sc->d_float);
+    (void)hipFree(sc->d_scene);
+    if (sw) (void)hipSetDevice(prev);
+    delete sc;
+}
+
+extern "C" int32_t stac_render(const stac_render_scene *sc, int32_t N, const float *xpos, const float *xquat, const float *kp,
+                               const float *markers, int32_t show_error, const float *cam, float tan_half_fovy, int32_t width,
+                               int32_t height, uint8_t *rgb_out, int32_t *seg_out, float *depth_out, void *stream) {
+    if (!sc || N < 0 || width < 1 || height < 1 || width > 32768 || height > 32768 || !(tan_half_fovy > 0.0f) ||
+        !(tan_half_fovy < INFINITY) || (N > 0 && (!xpos || !xquat || !cam)))
+        return fail(STAC_ERR_INVALID, "stac_render: bad argument");
+    int prev = -1;
+    const bool sw = hipGetDevice(&prev) == hipSuccess && prev != sc->device && hipSetDevice(sc->device) == hipSuccess;
+    RenderCall C{};
+    C.N = N; C.W = width; C.H = height; C.show_error = show_error ? 1 : 0;
+    C.xpos = xpos; C.xquat = xquat; C.kp = kp; C.markers = markers; C.cam = cam; C.tanh = tan_half_fovy;
+    C.rgb = rgb_out; C.seg = seg_out; C.depth = depth_out;
+    const hipError_t e = launch_render(sc->d_scene, C, (hipStream_t)stream);
+    if (sw) (void)hipSetDevice(prev);
+    if (e != hipSuccess) return fail(STAC_ERR_HIP, std::string("stac_render: ") + hipGetErrorString(e));
     return STAC_OK;
 }

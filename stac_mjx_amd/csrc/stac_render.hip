@@ -1,0 +1,460 @@
+// Ray caster of primitive-geom scenes: the hot path of Renderer / Stac.render (DESIGN.md "Rendering").
+//
+// One workgroup = one 16 x 16 tile of one frame (grid z strides over the frames).  Per frame the workgroup
+//   1. builds the frame's primitive records in LDS (the primitive pass: world pose and bounding sphere of every
+//      static primitive from xpos / xquat, the keypoint and marker spheres and the error segments);
+//   2. culls them against the tile's frustum into a compact list (wave ballot + prefix count);
+//   3. casts one ray per pixel centre against the list, keeps the nearest opaque hit and the kRenderLayers nearest
+//      transparent hits in registers, shades and composites them, and writes rgb / seg / depth.
+// The arithmetic is written operation by operation (no FMA: -ffp-contract=off) so that tests/tools/render_ref.c,
+// built with float, reproduces every output bit for bit.
+#include <hip/hip_runtime.h>
+
+#include <math.h>
+
+#include "../../include/stac_hip.h"
+#include "stac_render.hpp"
+
+namespace stac {
+namespace {
+
+enum { T_NONE = -1, T_PLANE = 0, T_SPHERE = 2, T_CAPSULE = 3, T_ELLIPSOID = 4, T_CYLINDER = 5, T_BOX = 6 };
+
+__device__ inline float dot3(const float *a, const float *b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
+
+// w,x,y,z -> row-major rotation matrix (columns = the rotated frame's axes)
+__device__ inline void quat_mat(const float *q, float *R) {
+    const float w = q[0], x = q[1], y = q[2], z = q[3];
+    const float ww = w * w, xx = x * x, yy = y * y, zz = z * z;
+    const float wx = w * x, wy = w * y, wz = w * z, xy = x * y, xz = x * z, yz = y * z;
+    R[0] = ww + xx - yy - zz; R[1] = 2.0f * (xy - wz);     R[2] = 2.0f * (xz + wy);
+    R[3] = 2.0f * (xy + wz);  R[4] = ww - xx + yy - zz;    R[5] = 2.0f * (yz - wx);
+    R[6] = 2.0f * (xz - wy);  R[7] = 2.0f * (yz + wx);     R[8] = ww - xx - yy + zz;
+}
+
+// R^T v (world -> local)
+__device__ inline void mat_tvec(const float *R, const float *v, float *out) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) out[j] = R[j] * v[0] + R[3 + j] * v[1] + R[6 + j] * v[2];
+}
+
+// R v (local -> world)
+__device__ inline void mat_vec(const float *R, const float *v, float *out) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) out[i] = R[3 * i] * v[0] + R[3 * i + 1] * v[1] + R[3 * i + 2] * v[2];
+}
+
+__device__ inline bool finite3(const float *p) { return p[0] == p[0] && p[1] == p[1] && p[2] == p[2]; }
+
+// Record layout (kRenderRecWords floats): c[0:3] world centre, R[3:12] world rotation (row-major), size[12:15],
+// bounding radius [15], type [16], flags [17] (as floats: small integers are exact).
+__device__ void build_prim(const RenderScene &S, const RenderCall &C, int f, int i, float *r) {
+    int type = T_NONE, flags = 0;
+    float c[3] = {0.0f, 0.0f, 0.0f};
+    float R[9] = {1.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 1.0f};
+    float sz[3] = {0.0f, 0.0f, 0.0f};
+    const int P = S.P, K = S.K;
+    if (i < P) {
+        type = S.prim_type[i];
+        flags = S.prim_flags[i];
+        const int b = S.prim_body[i];
+        const float *xp = C.xpos + ((size_t)f * S.nbody + b) * 3;
+        float Rb[9], Rl[9];
+        quat_mat(C.xquat + ((size_t)f * S.nbody + b) * 4, Rb);
+        quat_mat(S.prim_quat + 4 * i, Rl);
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+#pragma unroll
+            for (int q = 0; q < 3; ++q) R[3 * a + q] = Rb[3 * a] * Rl[q] + Rb[3 * a + 1] * Rl[3 + q] + Rb[3 * a + 2] * Rl[6 + q];
+        float lp[3];
+        mat_vec(Rb, S.prim_pos + 3 * i, lp);
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            c[a] = xp[a] + lp[a];
+            sz[a] = S.prim_size[3 * i + a];
+        }
+    } else if (i < P + K) {
+        const int k = i - P;
+        if (C.kp) {
+            const float *p = C.kp + ((size_t)f * K + k) * 3;
+            if (finite3(p)) {
+                type = T_SPHERE;
+                c[0] = p[0]; c[1] = p[1]; c[2] = p[2];
+                sz[0] = S.marker_r;
+            }
+        }
+    } else if (i < P + 2 * K) {
+        const int k = i - P - K;
+        if (C.markers) {
+            const float *p = C.markers + ((size_t)f * K + k) * 3;
+            if (finite3(p)) {
+                type = T_SPHERE;
+                c[0] = p[0]; c[1] = p[1]; c[2] = p[2];
+                sz[0] = S.marker_r;
+            }
+        }
+    } else {
+        const int k = i - P - 2 * K;
+        if (C.show_error && C.kp && C.markers) {
+            const float *a = C.kp + ((size_t)f * K + k) * 3;
+            const float *m = C.markers + ((size_t)f * K + k) * 3;
+            if (finite3(a) && finite3(m)) {
+                float d[3] = {m[0] - a[0], m[1] - a[1], m[2] - a[2]};
+                const float len = sqrtf(dot3(d, d));
+                float w[3] = {0.0f, 0.0f, 1.0f};
+                if (len > 0.0f) { w[0] = d[0] / len; w[1] = d[1] / len; w[2] = d[2] / len; }
+                type = T_CAPSULE;
+#pragma unroll
+                for (int q = 0; q < 3; ++q) c[q] = a[q] + d[q] * 0.5f;
+                R[2] = w[0]; R[5] = w[1]; R[8] = w[2];  // a capsule uses only its axis (column 2)
+                sz[0] = S.seg_r;
+                sz[1] = 0.5f * len;
+            }
+        }
+    }
+    float brad = 0.0f;
+    if (type == T_SPHERE) brad = sz[0];
+    else if (type == T_ELLIPSOID) brad = fmaxf(sz[0], fmaxf(sz[1], sz[2]));
+    else if (type == T_CAPSULE) brad = sz[1] + sz[0];
+    else if (type == T_CYLINDER || type == T_PLANE) brad = sqrtf(sz[0] * sz[0] + sz[1] * sz[1]);
+    else if (type == T_BOX) brad = sqrtf(dot3(sz, sz));
+#pragma unroll
+    for (int q = 0; q < 3; ++q) { r[q] = c[q]; r[12 + q] = sz[q]; }
+#pragma unroll
+    for (int q = 0; q < 9; ++q) r[3 + q] = R[q];
+    r[15] = brad;
+    r[16] = (float)type;
+    r[17] = (float)flags;
+}
+
+// Closest-approach sphere test: ray o + t d against |x - ctr| = rad.  Returns the entry t > 0 or -1.
+__device__ inline float hit_sphere(const float *ctr, float rad, const float *o, const float *d, float dd) {
+    const float oc[3] = {o[0] - ctr[0], o[1] - ctr[1], o[2] - ctr[2]};
+    const float tca = -dot3(oc, d) / dd;
+    const float p[3] = {oc[0] + d[0] * tca, oc[1] + d[1] * tca, oc[2] + d[2] * tca};
+    const float h2 = rad * rad - dot3(p, p);
+    if (!(h2 >= 0.0f)) return -1.0f;
+    const float t = tca - sqrtf(h2 / dd);
+    return t > 0.0f ? t : -1.0f;
+}
+
+// Entry t > 0 of the ray against record r (or -1), and the face that was hit (box axis; cylinder / capsule: 0 side,
+// 1 top, 2 bottom).  o / d are the world ray, dd = |d|^2.
+__device__ float intersect(const float *r, const float *o, const float *d, float dd, int *face) {
+    const int type = (int)r[16];
+    const float *c = r, *R = r + 3, *sz = r + 12;
+    *face = 0;
+    if (type == T_SPHERE) return hit_sphere(c, sz[0], o, d, dd);
+    const float oc[3] = {o[0] - c[0], o[1] - c[1], o[2] - c[2]};
+    if (type == T_CAPSULE) {
+        const float w[3] = {R[2], R[5], R[8]};
+        const float hl = sz[1], rad = sz[0];
+        const float oz = dot3(oc, w), dz = dot3(d, w);
+        const float op[3] = {oc[0] - w[0] * oz, oc[1] - w[1] * oz, oc[2] - w[2] * oz};
+        const float dp[3] = {d[0] - w[0] * dz, d[1] - w[1] * dz, d[2] - w[2] * dz};
+        const float a = dot3(dp, dp);
+        float best = INFINITY;
+        if (a > 0.0f) {
+            const float tca = -dot3(op, dp) / a;
+            const float p[3] = {op[0] + dp[0] * tca, op[1] + dp[1] * tca, op[2] + dp[2] * tca};
+            const float h2 = rad * rad - dot3(p, p);
+            if (h2 >= 0.0f) {
+                const float t = tca - sqrtf(h2 / a);
+                const float z = oz + dz * t;
+                if (t > 0.0f && fabsf(z) <= hl) best = t;
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const float e = s == 0 ? hl : -hl;
+            const float ctr[3] = {c[0] + w[0] * e, c[1] + w[1] * e, c[2] + w[2] * e};
+            const float t = hit_sphere(ctr, rad, o, d, dd);
+            if (t > 0.0f && t < best) { best = t; *face = 1 + s; }
+        }
+        return best < INFINITY ? best : -1.0f;
+    }
+    float ol[3], dl[3];
+    mat_tvec(R, oc, ol);
+    mat_tvec(R, d, dl);
+    if (type == T_ELLIPSOID) {
+        const float os[3] = {ol[0] / sz[0], ol[1] / sz[1], ol[2] / sz[2]};
+        const float ds[3] = {dl[0] / sz[0], dl[1] / sz[1], dl[2] / sz[2]};
+        const float a = dot3(ds, ds);
+        const float tca = -dot3(os, ds) / a;
+        const float p[3] = {os[0] + ds[0] * tca, os[1] + ds[1] * tca, os[2] + ds[2] * tca};
+        const float h2 = 1.0f - dot3(p, p);
+        if (!(h2 >= 0.0f)) return -1.0f;
+        const float t = tca - sqrtf(h2 / a);
+        return t > 0.0f ? t : -1.0f;
+    }
+    if (type == T_PLANE) {
+        if (!(ol[2] > 0.0f && dl[2] < 0.0f)) return -1.0f;
+        const float t = -ol[2] / dl[2];
+        const float x = ol[0] + dl[0] * t, y = ol[1] + dl[1] * t;
+        return (t > 0.0f && fabsf(x) <= sz[0] && fabsf(y) <= sz[1]) ? t : -1.0f;
+    }
+    if (type == T_BOX) {
+        float tn = -INFINITY, tf = INFINITY;
+        int ax = -1;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            if (dl[k] == 0.0f) {
+                if (fabsf(ol[k]) > sz[k]) return -1.0f;
+            } else {
+                const float t1 = (-sz[k] - ol[k]) / dl[k], t2 = (sz[k] - ol[k]) / dl[k];
+                const float lo = t1 < t2 ? t1 : t2, hi = t1 < t2 ? t2 : t1;
+                if (lo > tn) { tn = lo; ax = k; }
+                if (hi < tf) tf = hi;
+            }
+        }
+        *face = ax;
+        return (ax >= 0 && tn <= tf && tn > 0.0f) ? tn : -1.0f;
+    }
+    if (type == T_CYLINDER) {
+        const float rad = sz[0], hl = sz[1];
+        float best = INFINITY;
+        const float a = dl[0] * dl[0] + dl[1] * dl[1];
+        if (a > 0.0f) {
+            const float tca = -(ol[0] * dl[0] + ol[1] * dl[1]) / a;
+            const float px = ol[0] + dl[0] * tca, py = ol[1] + dl[1] * tca;
+            const float h2 = rad * rad - (px * px + py * py);
+            if (h2 >= 0.0f) {
+                const float t = tca - sqrtf(h2 / a);
+                const float z = ol[2] + dl[2] * t;
+                if (t > 0.0f && fabsf(z) <= hl) best = t;
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const float e = s == 0 ? hl : -hl;
+            const bool facing = s == 0 ? (ol[2] > hl && dl[2] < 0.0f) : (ol[2] < -hl && dl[2] > 0.0f);
+            if (facing) {
+                const float t = (e - ol[2]) / dl[2];
+                const float x = ol[0] + dl[0] * t, y = ol[1] + dl[1] * t;
+                if (t > 0.0f && x * x + y * y <= rad * rad && t < best) { best = t; *face = 1 + s; }
+            }
+        }
+        return best < INFINITY ? best : -1.0f;
+    }
+    return -1.0f;
+}
+
+// Unit world normal of record r at the hit (t, face) of the ray o + t d.
+__device__ void normal_at(const float *r, const float *o, const float *d, float t, int face, float *n) {
+    const int type = (int)r[16];
+    const float *c = r, *R = r + 3, *sz = r + 12;
+    const float q[3] = {o[0] + d[0] * t - c[0], o[1] + d[1] * t - c[1], o[2] + d[2] * t - c[2]};
+    float v[3];
+    if (type == T_SPHERE) {
+        v[0] = q[0]; v[1] = q[1]; v[2] = q[2];
+    } else if (type == T_CAPSULE) {
+        const float w[3] = {R[2], R[5], R[8]};
+        const float z = face == 0 ? dot3(q, w) : (face == 1 ? sz[1] : -sz[1]);
+        v[0] = q[0] - w[0] * z; v[1] = q[1] - w[1] * z; v[2] = q[2] - w[2] * z;
+    } else if (type == T_PLANE) {
+        v[0] = R[2]; v[1] = R[5]; v[2] = R[8];
+    } else {
+        float ql[3], nl[3];
+        mat_tvec(R, q, ql);
+        if (type == T_ELLIPSOID) {
+            nl[0] = ql[0] / (sz[0] * sz[0]); nl[1] = ql[1] / (sz[1] * sz[1]); nl[2] = ql[2] / (sz[2] * sz[2]);
+        } else if (type == T_BOX) {
+            float dl[3];
+            mat_tvec(R, d, dl);
+            nl[0] = 0.0f; nl[1] = 0.0f; nl[2] = 0.0f;
+            const float sgn = (face == 0 ? dl[0] : (face == 1 ? dl[1] : dl[2])) < 0.0f ? 1.0f : -1.0f;
+            if (face == 0) nl[0] = sgn; else if (face == 1) nl[1] = sgn; else nl[2] = sgn;
+        } else {  // cylinder
+            nl[0] = face == 0 ? ql[0] : 0.0f;
+            nl[1] = face == 0 ? ql[1] : 0.0f;
+            nl[2] = face == 0 ? 0.0f : (face == 1 ? 1.0f : -1.0f);
+        }
+        mat_vec(R, nl, v);
+    }
+    const float len = sqrtf(dot3(v, v));
+    n[0] = v[0] / len; n[1] = v[1] / len; n[2] = v[2] / len;
+}
+
+// Shaded colour of primitive `id` (record r) at the hit (t, face).  zc = the camera's z axis (towards the viewer).
+__device__ void shade(const RenderScene &S, const float *r, int id, const float *o, const float *d, float t, int face,
+                      const float *zc, float *col) {
+    float n[3];
+    normal_at(r, o, d, t, face, n);
+    const int P = S.P, K = S.K;
+    float rgb[3];
+    if (id < P) {
+        const float *c1 = S.prim_rgba + 4 * id;
+        rgb[0] = c1[0]; rgb[1] = c1[1]; rgb[2] = c1[2];
+        const int flags = (int)r[17];
+        if (flags & STAC_RENDER_CHECKER) {
+            const float *c = r, *R = r + 3, *sz = r + 12;
+            const float q[3] = {o[0] + d[0] * t - c[0], o[1] + d[1] * t - c[1], o[2] + d[2] * t - c[2]};
+            float ql[3];
+            mat_tvec(R, q, ql);
+            const float *rep = S.prim_tex + 2 * id;
+            const bool uni = (flags & STAC_RENDER_TEXUNIFORM) != 0;
+            const float u = ql[0] * rep[0] / (uni ? 1.0f : 2.0f * sz[0]);
+            const float v = ql[1] * rep[1] / (uni ? 1.0f : 2.0f * sz[1]);
+            const int cell = (int)floorf(2.0f * u) + (int)floorf(2.0f * v);
+            if (cell & 1) {
+                const float *c2 = S.prim_rgb2 + 3 * id;
+                rgb[0] = c2[0]; rgb[1] = c2[1]; rgb[2] = c2[2];
+            }
+        }
+    } else if (id < P + K) {
+        const float *c1 = S.kp_rgba + 4 * (id - P);
+        rgb[0] = c1[0]; rgb[1] = c1[1]; rgb[2] = c1[2];
+    } else if (id < P + 2 * K) {
+        rgb[0] = S.marker_rgba[0]; rgb[1] = S.marker_rgba[1]; rgb[2] = S.marker_rgba[2];
+    } else {
+        rgb[0] = S.seg_rgba[0]; rgb[1] = S.seg_rgba[1]; rgb[2] = S.seg_rgba[2];
+    }
+    const float ch = fmaxf(dot3(n, zc), 0.0f);
+    float L[3];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) L[q] = S.head_amb[q] + S.head_diff[q] * ch;
+    for (int l = 0; l < S.nlight; ++l) {
+        const float cl = fmaxf(-dot3(n, S.light_dir + 3 * l), 0.0f);
+#pragma unroll
+        for (int q = 0; q < 3; ++q) L[q] = L[q] + S.light_diff[3 * l + q] * cl;
+    }
+#pragma unroll
+    for (int q = 0; q < 3; ++q) col[q] = rgb[q] * fminf(L[q], 1.0f);
+}
+
+// u (x) and v (y) of the ray through the centre of pixel column x / row y (row 0 at the top).
+__device__ inline float pix_u(int x, int W, float tu) { return (((float)x + 0.5f) * 2.0f / (float)W - 1.0f) * tu; }
+__device__ inline float pix_v(int y, int H, float tv) { return (1.0f - ((float)y + 0.5f) * 2.0f / (float)H) * tv; }
+
+// true when the bounding sphere of record r lies entirely outside the frustum of the tile (half-spaces through the camera
+// centre with normals in camera coordinates) or behind the camera.  The margin keeps the test conservative against the
+// float rounding of the ray directions and of this test itself.
+__device__ inline bool culled(const float *r, const float *cam, float uL, float uR, float vT, float vB) {
+    if ((int)r[16] == T_NONE) return true;
+    const float w[3] = {r[0] - cam[0], r[1] - cam[1], r[2] - cam[2]};
+    float q[3];
+    mat_tvec(cam + 3, w, q);
+    const float m = r[15] * 1.001f + 1e-4f * sqrtf(dot3(q, q)) + 1e-6f;
+    if (q[2] > m) return true;
+    if ((q[0] + uL * q[2]) < -m * sqrtf(1.0f + uL * uL)) return true;
+    if ((-q[0] - uR * q[2]) < -m * sqrtf(1.0f + uR * uR)) return true;
+    if ((-q[1] - vT * q[2]) < -m * sqrtf(1.0f + vT * vT)) return true;
+    if ((q[1] + vB * q[2]) < -m * sqrtf(1.0f + vB * vB)) return true;
+    return false;
+}
+
+__device__ inline uint8_t quant(float c) {
+    const float x = c < 0.0f ? 0.0f : (c > 1.0f ? 1.0f : c);
+    return (uint8_t)(int)floorf(x * 255.0f + 0.5f);
+}
+
+__global__ __launch_bounds__(kRenderTile *kRenderTile) void render_kernel(const RenderScene *__restrict__ Sp, RenderCall C) {
+    const RenderScene &S = *Sp;
+    __shared__ float rec[kRenderMaxPrims * kRenderRecWords];
+    __shared__ int list[kRenderMaxPrims];
+    __shared__ int wcount[kRenderTile * kRenderTile / 64];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int Ptot = S.P + 3 * S.K;
+    const int x0 = blockIdx.x * kRenderTile, y0 = blockIdx.y * kRenderTile;
+    const int x = x0 + (tid % kRenderTile), y = y0 + (tid / kRenderTile);
+    const bool inside = x < C.W && y < C.H;
+    const float tv = C.tanh, tu = C.tanh * ((float)C.W / (float)C.H);
+    const float uL = pix_u(x0, C.W, tu), uR = pix_u(min(x0 + kRenderTile, C.W) - 1, C.W, tu);
+    const float vT = pix_v(y0, C.H, tv), vB = pix_v(min(y0 + kRenderTile, C.H) - 1, C.H, tv);
+    for (int f = blockIdx.z; f < C.N; f += gridDim.z) {
+        __syncthreads();  // the previous frame's readers are done with rec / list
+        for (int i = tid; i < Ptot; i += kRenderTile * kRenderTile) build_prim(S, C, f, i, rec + i * kRenderRecWords);
+        __syncthreads();
+        const float *cam = C.cam + (size_t)f * 12;
+        int count = 0;
+        for (int base = 0; base < Ptot; base += kRenderTile * kRenderTile) {
+            const int i = base + tid;
+            const bool vis = i < Ptot && !culled(rec + i * kRenderRecWords, cam, uL, uR, vT, vB);
+            const unsigned long long mask = __ballot(vis);
+            const int pre = __popcll(mask & ((1ull << lane) - 1ull));
+            if (lane == 0) wcount[wave] = __popcll(mask);
+            __syncthreads();
+            int off = count, total = 0;
+#pragma unroll
+            for (int w = 0; w < kRenderTile * kRenderTile / 64; ++w) {
+                if (w < wave) off += wcount[w];
+                total += wcount[w];
+            }
+            if (vis) list[off + pre] = i;
+            count += total;
+            __syncthreads();
+        }
+        if (!inside) continue;
+        const float o[3] = {cam[0], cam[1], cam[2]};
+        const float *Rc = cam + 3;
+        const float u = pix_u(x, C.W, tu), v = pix_v(y, C.H, tv);
+        float d[3];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) d[q] = Rc[3 * q] * u + Rc[3 * q + 1] * v - Rc[3 * q + 2];
+        {
+            const float len = sqrtf(dot3(d, d));
+            d[0] = d[0] / len; d[1] = d[1] / len; d[2] = d[2] / len;
+        }
+        const float dd = dot3(d, d);
+        float to = INFINITY;
+        int io = -1, fo = 0;
+        // the kRenderLayers nearest transparent hits, sorted by (t, id): key = bits(t) << 32 | id << 2 | face (t > 0, so the
+        // bits of t order like t); ~0 = empty.  One 64-bit key per slot keeps t, id and face together through the network.
+        unsigned long long L[kRenderLayers];
+#pragma unroll
+        for (int k = 0; k < kRenderLayers; ++k) L[k] = ~0ull;
+        for (int j = 0; j < count; ++j) {
+            const int id = list[j];
+            const float *r = rec + id * kRenderRecWords;
+            int face;
+            const float t = intersect(r, o, d, dd, &face);
+            if (!(t > 0.0f)) continue;
+            if (((int)r[17]) & STAC_RENDER_TRANSPARENT) {
+                unsigned long long key = ((unsigned long long)__float_as_uint(t) << 32) | ((unsigned)id << 2) | (unsigned)face;
+#pragma unroll
+                for (int k = 0; k < kRenderLayers; ++k) {  // insertion into the sorted list; the largest key drops out
+                    const unsigned long long cur = L[k];
+                    L[k] = key < cur ? key : cur;
+                    key = key < cur ? cur : key;
+                }
+            } else if (t < to || (t == to && id < io)) {
+                to = t; io = id; fo = face;
+            }
+        }
+        const float zc[3] = {Rc[2], Rc[5], Rc[8]};
+        float col[3] = {S.bg[0], S.bg[1], S.bg[2]};
+        if (io >= 0) shade(S, rec + io * kRenderRecWords, io, o, d, to, fo, zc, col);
+        const float a = S.alpha, na = 1.0f - S.alpha;
+#pragma unroll
+        for (int k = kRenderLayers - 1; k >= 0; --k) {  // back to front
+            const float tk = __uint_as_float((unsigned)(L[k] >> 32));
+            const int ik = (int)((L[k] >> 2) & 0x3fffffffu), fk = (int)(L[k] & 3u);
+            if (L[k] != ~0ull && tk < to) {
+                float s[3];
+                shade(S, rec + ik * kRenderRecWords, ik, o, d, tk, fk, zc, s);
+#pragma unroll
+                for (int q = 0; q < 3; ++q) col[q] = col[q] * na + s[q] * a;
+            }
+        }
+        const size_t px = ((size_t)f * C.H + y) * C.W + x;
+        if (C.rgb) {
+            C.rgb[3 * px] = quant(col[0]);
+            C.rgb[3 * px + 1] = quant(col[1]);
+            C.rgb[3 * px + 2] = quant(col[2]);
+        }
+        if (C.seg) C.seg[px] = io;
+        if (C.depth) C.depth[px] = to;
+    }
+}
+
+}  // namespace
+
+hipError_t launch_render(const RenderScene *S, const RenderCall &C, hipStream_t s) {
+    if (C.N <= 0) return hipSuccess;
+    const dim3 grid((C.W + kRenderTile - 1) / kRenderTile, (C.H + kRenderTile - 1) / kRenderTile, C.N < 65535 ? C.N : 65535);
+    hipLaunchKernelGGL(render_kernel, grid, dim3(kRenderTile * kRenderTile), 0, s, S, C);
+    return hipGetLastError();
+}
+
+}  // namespace stac

@@ -260,6 +260,7 @@ def compile_mjcf(
     scale: float = 1.0,
     legacy_joint_pos_scale: bool = False,
     from_string: bool = False,
+    _visit=None,
 ) -> ModelTables:
     """Compile an MJCF file (or string) to :class:`ModelTables`.
 
@@ -348,6 +349,8 @@ def compile_mjcf(
             elif child.tag == "site":
                 a, _ = resolved("site", child, cc)
                 native_sites.append((a.get("name", ""), bid, _floats(a.get("pos", "0 0 0"), 3)))
+            if _visit is not None and child.tag in ("geom", "site", "camera", "light", "inertial"):
+                _visit(child.tag, resolved(child.tag, child, cc)[0] if child.tag != "inertial" else dict(child.attrib), bid, scaled)
         for child in elem:
             if child.tag == "body":
                 # dm_scale_spec: scale_bodies(worldbody.first_body()) scales the pos of every body
@@ -362,6 +365,8 @@ def compile_mjcf(
         elif child.tag == "site":
             a, _ = resolved("site", child, world_cc)
             native_sites.append((a.get("name", ""), 0, _floats(a.get("pos", "0 0 0"), 3)))
+        if _visit is not None and child.tag in ("geom", "site", "camera", "light"):
+            _visit(child.tag, resolved(child.tag, child, world_cc)[0], 0, False)
 
     nbody = len(body_parent)
     # -- scaling (before qpos0 is derived, like spec.compile() after dm_scale_spec) ----------
@@ -481,3 +486,258 @@ def align_joint_dims(types, ranges, names):
         part_names += [name] * dims
     lb = np.minimum(np.asarray(lb, np.float32), np.float32(0.0))
     return lb, np.asarray(ub, np.float32), part_names
+
+
+# ----------------------------------------------------------------------------------
+# render scene (stac_mjx_amd/render.py; DESIGN.md "Rendering")
+# ----------------------------------------------------------------------------------
+GEOM_PLANE, GEOM_HFIELD, GEOM_SPHERE, GEOM_CAPSULE, GEOM_ELLIPSOID, GEOM_CYLINDER, GEOM_BOX, GEOM_MESH = range(8)  # mjtGeom
+_GEOM_TYPES = {"plane": GEOM_PLANE, "hfield": GEOM_HFIELD, "sphere": GEOM_SPHERE, "capsule": GEOM_CAPSULE,
+               "ellipsoid": GEOM_ELLIPSOID, "cylinder": GEOM_CYLINDER, "box": GEOM_BOX, "mesh": GEOM_MESH}
+CAMERA_MODES = ("fixed", "track", "trackcom")
+
+
+@dataclass
+class RenderScene:
+    """What the renderer draws of a model (float64, body frame).  Geoms and sites keep document order; ``geom_*`` holds the
+    supported primitive geoms of every group (mesh / height-field geoms are counted in ``n_skipped``)."""
+
+    nbody: int
+    body_names: list[str]
+    geom_names: list[str]
+    geom_type: np.ndarray  # [G] mjtGeom
+    geom_body: np.ndarray  # [G]
+    geom_group: np.ndarray  # [G]
+    geom_size: np.ndarray  # [G,3]
+    geom_pos: np.ndarray  # [G,3]
+    geom_quat: np.ndarray  # [G,4]
+    geom_rgba: np.ndarray  # [G,4] (rgb1 of a checker material)
+    geom_checker: np.ndarray  # [G] bool: plane with a builtin checker texture
+    geom_rgb2: np.ndarray  # [G,3]
+    geom_texrepeat: np.ndarray  # [G,2]
+    geom_texuniform: np.ndarray  # [G] bool
+    geom_mass: np.ndarray  # [G]
+    site_names: list[str]
+    site_type: np.ndarray
+    site_body: np.ndarray
+    site_group: np.ndarray
+    site_size: np.ndarray
+    site_pos: np.ndarray
+    site_quat: np.ndarray
+    site_rgba: np.ndarray
+    cam_names: list[str]
+    cam_body: np.ndarray
+    cam_mode: list[str]
+    cam_pos: np.ndarray  # [C,3]
+    cam_quat: np.ndarray  # [C,4]
+    cam_fovy: np.ndarray  # [C] degrees, vertical
+    light_dir: np.ndarray  # [L,3] unit
+    light_diffuse: np.ndarray  # [L,3]
+    light_directional: np.ndarray  # [L] bool (every light is drawn as a directional light)
+    head_ambient: np.ndarray  # [3]
+    head_diffuse: np.ndarray  # [3]
+    head_active: bool
+    azimuth: float  # degrees
+    elevation: float  # degrees
+    fovy: float  # free camera, degrees
+    alpha: float  # <visual><map alpha>
+    body_mass: np.ndarray  # [nbody]
+    body_ipos: np.ndarray  # [nbody,3] local centre of mass
+    n_skipped: int = 0
+
+
+def _geom_volume(t: int, size: np.ndarray) -> float:
+    """MuJoCo's primitive volumes (massless: plane, mesh, hfield)."""
+    if t == GEOM_SPHERE:
+        return 4.0 / 3.0 * math.pi * size[0] ** 3
+    if t == GEOM_ELLIPSOID:
+        return 4.0 / 3.0 * math.pi * size[0] * size[1] * size[2]
+    if t == GEOM_CAPSULE:
+        return math.pi * size[0] ** 2 * 2.0 * size[1] + 4.0 / 3.0 * math.pi * size[0] ** 3
+    if t == GEOM_CYLINDER:
+        return math.pi * size[0] ** 2 * 2.0 * size[1]
+    if t == GEOM_BOX:
+        return 8.0 * size[0] * size[1] * size[2]
+    return 0.0
+
+
+def _z_to_quat(v) -> np.ndarray:
+    """Quaternion of the shortest rotation taking +z to the direction v (the ``zaxis`` / ``fromto`` rule)."""
+    v = np.asarray(v, np.float64)
+    n = np.linalg.norm(v)
+    if n < 1e-14:
+        return np.array([1.0, 0.0, 0.0, 0.0])
+    v = v / n
+    z0 = np.array([0.0, 0.0, 1.0])
+    ax = np.cross(z0, v)
+    s = np.linalg.norm(ax)
+    ang = math.atan2(s, float(np.dot(z0, v)))
+    if s < 1e-10:
+        ax = np.array([1.0, 0.0, 0.0])
+    return _axis_angle_quat(ax, ang)
+
+
+def compile_render_scene(xml: str | Path, *, scale: float = 1.0, from_string: bool = False, log=print) -> RenderScene:
+    """Compile what :class:`stac_mjx_amd.render.Renderer` draws of an MJCF model.
+
+    The body walk is :func:`compile_mjcf`'s (same body ids and names, same default classes and ``childclass``); geom
+    ``size`` / ``pos`` / ``fromto`` of the bodies whose ``pos`` the ``dm_scale_spec`` rule scales are scaled by ``scale``.
+    ``mesh`` / ``hfield`` geoms are skipped (reported once through ``log``); other unknown types raise :class:`MjcfError`.
+    """
+    root = ET.fromstring(xml) if from_string else ET.parse(str(xml)).getroot()
+    comp = _Compiler(root)
+    # assets: checker textures and materials
+    textures, materials = {}, {}
+    for asset in root.findall("asset"):
+        for t in asset.findall("texture"):
+            textures[t.attrib.get("name", "")] = t.attrib
+        for m in asset.findall("material"):
+            materials[m.attrib.get("name", "")] = m.attrib
+    geoms, sites, cams, lights, inertials = [], [], [], [], {}
+
+    def visit(tag, a, bid, scaled):
+        {"geom": geoms, "site": sites, "camera": cams, "light": lights}.get(tag, []).append((a, bid, scaled))
+        if tag == "inertial":
+            inertials[bid] = a
+
+    tables = compile_mjcf(xml, scale=scale, from_string=from_string, _visit=visit)
+    nbody = tables.nbody
+
+    G = dict(names=[], type=[], body=[], group=[], size=[], pos=[], quat=[], rgba=[], checker=[], rgb2=[], rep=[], uni=[], mass=[])
+    n_skipped = 0
+    for a, bid, scaled in geoms:
+        tname = a.get("type", "sphere").strip().lower()
+        if tname not in _GEOM_TYPES:
+            raise MjcfError(f"unknown geom type {tname!r}")
+        t = _GEOM_TYPES[tname]
+        if t in (GEOM_MESH, GEOM_HFIELD):
+            n_skipped += 1
+            continue
+        size = np.zeros(3)
+        sv = _floats(a.get("size", "0"))
+        size[: min(3, sv.size)] = sv[:3]
+        if "fromto" in a and t in (GEOM_CAPSULE, GEOM_CYLINDER, GEOM_BOX, GEOM_ELLIPSOID):
+            ft = _floats(a["fromto"], 6)
+            if scaled:
+                ft = ft * scale
+            p0, p1 = ft[:3], ft[3:]
+            pos = 0.5 * (p0 + p1)
+            quat = _z_to_quat(p1 - p0)
+            half = 0.5 * float(np.linalg.norm(p1 - p0))
+            if scaled:
+                size = size * scale
+            if t in (GEOM_CAPSULE, GEOM_CYLINDER):
+                size[1] = half
+            else:
+                size[2] = half
+        else:
+            pos = _floats(a.get("pos", "0 0 0"), 3)
+            quat = comp.orientation(a)
+            if scaled:
+                pos, size = pos * scale, size * scale
+        rgba = np.array([0.5, 0.5, 0.5, 1.0])
+        checker, rgb2, rep, uni = False, np.zeros(3), np.ones(2), False
+        mat = materials.get(a.get("material", ""), None) if "material" in a else None
+        if mat is not None:
+            if "rgba" in mat:
+                rgba = _floats(mat["rgba"], 4)
+            tex = textures.get(mat.get("texture", ""), None)
+            if tex is not None and tex.get("builtin", "none") == "checker" and t == GEOM_PLANE:
+                checker = True
+                rgba = np.concatenate([_floats(tex.get("rgb1", "0.8 0.8 0.8"), 3), [rgba[3]]])
+                rgb2 = _floats(tex.get("rgb2", "0.5 0.5 0.5"), 3)
+                rep = _floats(mat.get("texrepeat", "1 1"), 2)
+                uni = mat.get("texuniform", "false").strip().lower() == "true"
+        if "rgba" in a and not checker:
+            rgba = _floats(a["rgba"], 4)
+        if "mass" in a:
+            mass = float(a["mass"])
+        else:
+            mass = float(a.get("density", 1000.0)) * _geom_volume(t, size)
+        G["names"].append(a.get("name", ""))
+        for k, v in (("type", t), ("body", bid), ("group", int(a.get("group", 0))), ("size", size), ("pos", pos), ("quat", quat),
+                     ("rgba", rgba), ("checker", checker), ("rgb2", rgb2), ("rep", rep), ("uni", uni), ("mass", mass)):
+            G[k].append(v)
+    if n_skipped:
+        log(f"compile_render_scene: {n_skipped} mesh / height-field geoms are not drawn")
+
+    S = dict(names=[], type=[], body=[], group=[], size=[], pos=[], quat=[], rgba=[])
+    for a, bid, _ in sites:
+        tname = a.get("type", "sphere").strip().lower()
+        if tname not in _GEOM_TYPES or _GEOM_TYPES[tname] in (GEOM_MESH, GEOM_HFIELD, GEOM_PLANE):
+            raise MjcfError(f"unsupported site type {tname!r}")
+        size = np.full(3, 0.005)
+        sv = _floats(a.get("size", "0.005"))
+        size[: min(3, sv.size)] = sv[:3]
+        S["names"].append(a.get("name", ""))
+        for k, v in (("type", _GEOM_TYPES[tname]), ("body", bid), ("group", int(a.get("group", 0))), ("size", size),
+                     ("pos", _floats(a.get("pos", "0 0 0"), 3)), ("quat", comp.orientation(a)),
+                     ("rgba", _floats(a.get("rgba", "0.5 0.5 0.5 1"), 4))):
+            S[k].append(v)
+
+    Cm = dict(names=[], body=[], mode=[], pos=[], quat=[], fovy=[])
+    for a, bid, _ in cams:
+        mode = a.get("mode", "fixed").strip().lower()
+        if mode not in CAMERA_MODES:
+            raise MjcfError(f"camera {a.get('name', '')!r}: mode {mode!r} is not supported (fixed, track, trackcom)")
+        Cm["names"].append(a.get("name", ""))
+        Cm["body"].append(bid)
+        Cm["mode"].append(mode)
+        Cm["pos"].append(_floats(a.get("pos", "0 0 0"), 3))
+        Cm["quat"].append(comp.orientation(a))
+        Cm["fovy"].append(float(a.get("fovy", 45.0)))
+
+    L = dict(dir=[], diffuse=[], directional=[])
+    for a, _, _ in lights:
+        d = _floats(a.get("dir", "0 0 -1"), 3)
+        L["dir"].append(d / max(np.linalg.norm(d), 1e-14))
+        L["diffuse"].append(_floats(a.get("diffuse", "0.7 0.7 0.7"), 3))
+        L["directional"].append(a.get("directional", "false").strip().lower() == "true")
+
+    head_amb, head_diff, active = np.full(3, 0.1), np.full(3, 0.4), True
+    az, el, fovy, alpha = 90.0, -45.0, 45.0, 0.3
+    for vis in root.findall("visual"):
+        for h in vis.findall("headlight"):
+            head_amb = _floats(h.attrib.get("ambient"), 3) if "ambient" in h.attrib else head_amb
+            head_diff = _floats(h.attrib.get("diffuse"), 3) if "diffuse" in h.attrib else head_diff
+            active = int(h.attrib.get("active", 1)) != 0 if "active" in h.attrib else active
+        for g in vis.findall("global"):
+            az = float(g.attrib.get("azimuth", az))
+            el = float(g.attrib.get("elevation", el))
+            fovy = float(g.attrib.get("fovy", fovy))
+        for m in vis.findall("map"):
+            alpha = float(m.attrib.get("alpha", alpha))
+
+    # body masses / local centres of mass: an explicit <inertial> wins, else the geoms' (density x volume, or mass)
+    body_mass = np.zeros(nbody)
+    body_ipos = np.zeros((nbody, 3))
+    gb, gm, gp = np.asarray(G["body"], np.int64), np.asarray(G["mass"], np.float64), np.asarray(G["pos"], np.float64).reshape(-1, 3)
+    for b in range(nbody):
+        if b in inertials:
+            body_mass[b] = float(inertials[b].get("mass", 0.0))
+            body_ipos[b] = _floats(inertials[b].get("pos", "0 0 0"), 3)
+            continue
+        sel = gb == b
+        m = float(gm[sel].sum()) if sel.any() else 0.0
+        body_mass[b] = m
+        if m > 0:
+            body_ipos[b] = (gm[sel, None] * gp[sel]).sum(0) / m
+
+    arr = lambda v, shape, dt=np.float64: np.asarray(v, dt).reshape(shape)
+    ng, ns, nc, nl = len(G["names"]), len(S["names"]), len(Cm["names"]), len(L["dir"])
+    return RenderScene(
+        nbody=nbody, body_names=list(tables.body_names),
+        geom_names=G["names"], geom_type=arr(G["type"], ng, np.int32), geom_body=arr(G["body"], ng, np.int32),
+        geom_group=arr(G["group"], ng, np.int32), geom_size=arr(G["size"], (ng, 3)), geom_pos=arr(G["pos"], (ng, 3)),
+        geom_quat=arr(G["quat"], (ng, 4)), geom_rgba=arr(G["rgba"], (ng, 4)), geom_checker=arr(G["checker"], ng, bool),
+        geom_rgb2=arr(G["rgb2"], (ng, 3)), geom_texrepeat=arr(G["rep"], (ng, 2)), geom_texuniform=arr(G["uni"], ng, bool),
+        geom_mass=arr(G["mass"], ng),
+        site_names=S["names"], site_type=arr(S["type"], ns, np.int32), site_body=arr(S["body"], ns, np.int32),
+        site_group=arr(S["group"], ns, np.int32), site_size=arr(S["size"], (ns, 3)), site_pos=arr(S["pos"], (ns, 3)),
+        site_quat=arr(S["quat"], (ns, 4)), site_rgba=arr(S["rgba"], (ns, 4)),
+        cam_names=Cm["names"], cam_body=arr(Cm["body"], nc, np.int32), cam_mode=Cm["mode"], cam_pos=arr(Cm["pos"], (nc, 3)),
+        cam_quat=arr(Cm["quat"], (nc, 4)), cam_fovy=arr(Cm["fovy"], nc),
+        light_dir=arr(L["dir"], (nl, 3)), light_diffuse=arr(L["diffuse"], (nl, 3)), light_directional=arr(L["directional"], nl, bool),
+        head_ambient=np.asarray(head_amb, np.float64), head_diffuse=np.asarray(head_diff, np.float64), head_active=bool(active),
+        azimuth=az, elevation=el, fovy=fovy, alpha=alpha, body_mass=body_mass, body_ipos=body_ipos, n_skipped=n_skipped,
+    )

@@ -1,6 +1,6 @@
 """``Stac``: model set-up, ``fit_offsets`` / ``ik_only`` and output packing on the HIP engine.
 
-Mirrors the hot-path part of ``stac_mjx/stac.py`` (:91-503; rendering is out of scope).  The
+Mirrors ``stac_mjx/stac.py`` (:91-658; ``render`` draws with the GPU ray caster of ``render.py``).  The
 per-frame Python loops of the reference (``compute_stac.pose_optimization``) run inside one
 ``stac_q_phase`` kernel launch per phase; sequencing, warm starts, sampling and packing follow the
 reference.
@@ -50,6 +50,7 @@ class Stac:
         self.timings = None  # bench.py --mode run: {} collects the phase times of ik_only (see _tick)
         self._t_last = 0.0
         self._timestep = s.tables.timestep
+        self._renderer = None
 
     # -- helpers ------------------------------------------------------------------------------------
     def _log(self, *a):
@@ -220,3 +221,46 @@ class Stac:
         return StacData(qpos=qpos, xpos=xpos, xquat=xquat, marker_sites=markers, offsets=offsets,
                         names_qpos=self._part_names, names_xpos=self._body_names, kp_data=kp_flat,
                         kp_names=self._kp_names)
+
+    # -- render (stac.py:505-658) -------------------------------------------------------------------------------
+    def _get_renderer(self):
+        if self._renderer is None:
+            if self._xml_path is None:
+                raise ValueError("Stac.render needs the model's MJCF file: this Stac was built from `setup=` without an xml_path")
+            from .mjcf import compile_render_scene
+            from .render import Renderer
+
+            cfgm = self.cfg.model
+            pairs = dict(cfgm.KEYPOINT_MODEL_PAIRS)
+            colours = dict(cfgm.KEYPOINT_COLOR_PAIRS)
+            rgba = [[float(c) for c in v.split()] if isinstance(v, str) else [float(c) for c in v] for v in (colours[k] for k in pairs)]
+            scene = compile_render_scene(self._xml_path, scale=float(cfgm.SCALE_FACTOR), log=self._log)
+            self._renderer = Renderer(self.engine, scene, list(pairs), list(pairs.values()), rgba,
+                                      marker_size=float(cfgm.get("MARKER_SIZE", 0.005) if hasattr(cfgm, "get") else cfgm.MARKER_SIZE))
+        return self._renderer
+
+    def render(self, qposes, kp_data, offsets, n_frames, save_path, start_frame=0, camera=0, height=1200, width=1920,
+               show_marker_error=False):
+        """Render fitted results as a video (the reference's signature and checks, ``stac.py:569-658``); returns the list of
+        H x W x 3 uint8 frames.  ``camera``: index, name, or -1 (free camera).  The engine's state is left as it was."""
+        qposes, kp_data = np.asarray(qposes), np.asarray(kp_data)
+        if qposes.shape[0] != kp_data.shape[0]:
+            raise ValueError(
+                f"Length of qposes ({qposes.shape[0]}) is not equal to the length of kp_data({kp_data.shape[0]})")
+        if start_frame < 0 or start_frame > kp_data.shape[0]:
+            raise ValueError(
+                f"start_frame ({start_frame}) must be non-negative and less than the length of kp_data ({kp_data.shape[0]})")
+        if start_frame + n_frames > kp_data.shape[0]:
+            raise ValueError(
+                f"start_frame + n_frames ({start_frame} + {n_frames}) must be less than the length of given qposes and kp_data ({kp_data.shape[0]})")
+        r = self._get_renderer()
+        r.camera_index(camera)
+        from .video import write_video
+
+        sl = slice(start_frame, start_frame + n_frames)
+        t = self.setup.tables
+        out = r.render(qposes[sl], kp_data[sl], offsets, qpos0=t.qpos0, parent=t.body_parentid, camera=camera, width=width,
+                       height=height, show_marker_error=show_marker_error)
+        frames = list(out["rgb"].numpy())
+        write_video(save_path, frames, fps=float(self.cfg.model.RENDER_FPS), log=self._log)
+        return frames

@@ -1,0 +1,21 @@
+"""``viz_stac``: render a result file (``stac_mjx/viz.py:10-61``) with the GPU renderer of ``Stac.render``."""
+
+from __future__ import annotations
+
+from pathlib import Path
+
+from . import io
+
+
+def viz_stac(data_path, n_frames: int, save_path, start_frame: int = 0, camera=0, height: int = 1200, width: int = 1920,
+             base_path: Path | None = None, show_marker_error: bool = False):
+    """Render forward kinematics from STAC output data; returns (config, list of rendered RGB frames)."""
+    from .stac import Stac
+
+    cfg, d = io.load_stac_data(data_path)
+    if base_path is None:
+        base_path = Path.cwd()
+    xml_path = Path(base_path) / cfg.model.MJCF_PATH
+    stac = Stac(xml_path, cfg, d.kp_names)
+    return cfg, stac.render(d.qpos, d.kp_data, d.offsets, n_frames, save_path, start_frame, camera, height, width,
+                            show_marker_error)

@@ -157,7 +157,7 @@ int32_t stac_m_phase_finish(const stac_model *m, const float *partial, const flo
                             const float *is_regularized, float reg_coef, float *offsets_out,
                             float *err_out, void *stream);
 
-/* ---- Rendering (DESIGN.md "Rendering"): a ray caster over primitive geoms, keypoints and markers. ------------------
+/* ---- Rendering (DESIGN.md "Rendering"): a ray caster over primitive and mesh geoms, keypoints and markers. --------
  * Static primitives (P: the visible model geoms, then the visible model sites) are posed by their body's xpos / xquat;
  * per frame there are also K keypoint spheres, K marker spheres and, with show_error, K keypoint-to-marker capsules.
  * Primitive ids: static 0..P-1, keypoint k -> P+k, marker k -> P+K+k, segment k -> P+2K+k.  P + 3K must not exceed
@@ -167,7 +167,8 @@ int32_t stac_m_phase_finish(const stac_model *m, const float *partial, const flo
 enum { STAC_RENDER_TRANSPARENT = 1, STAC_RENDER_CHECKER = 2, STAC_RENDER_TEXUNIFORM = 4 };
 
 /* HOST pointers, copied at stac_render_scene_create.  prim_type uses mjtGeom values: 0 plane, 2 sphere, 3 capsule,
- * 4 ellipsoid, 5 cylinder, 6 box. */
+ * 4 ellipsoid, 5 cylinder, 6 box, and 7 mesh (only through stac_render_scene_create_with_meshes; prim_size of a mesh
+ * primitive is ignored). */
 typedef struct stac_render_tables {
     int32_t nprim;               /* P */
     const int32_t *prim_type;    /* [P] */
@@ -196,6 +197,35 @@ typedef struct stac_render_scene stac_render_scene; /* opaque */
 /* Uploads the tables to the model's device.  Returns NULL on failure (see stac_last_error / stac_last_error_code). */
 stac_render_scene *stac_render_scene_create(const stac_model *m, const stac_render_tables *t);
 void stac_render_scene_destroy(stac_render_scene *s);
+
+/* Triangle meshes.  A mesh instance (a primitive of type 7) is ONE primitive against STAC_RENDER_MAX_PRIMS, whatever its
+ * triangle count; several primitives may share a mesh.  A mesh is two-sided and flat shaded: the hit of a ray is the
+ * triangle with the smallest t > 0, ties to the lower triangle index (its position in tri_vertex), whatever the
+ * hierarchy; zero-area triangles are never hit.  The triangle index travels in 20 bits of the pixel's 64-bit hit key,
+ * next to the 10 bits of the primitive id, hence the limit per mesh: */
+#define STAC_RENDER_MAX_MESH_TRIS 1048576
+/* HOST pointers, copied to device global memory at stac_render_scene_create_with_meshes.  Mesh k owns the nodes
+ * node_offset[k] .. node_offset[k+1]-1 and the triangles tri_offset[k] .. tri_offset[k+1]-1; node indices and triangle
+ * indices inside a mesh are relative to those.  Nodes are in depth-first order, node 0 is the root.  The walk starts
+ * at node 0; at node n: box missed -> n = skip; inner node (count 0) -> n = n + 1; leaf -> test the triangles
+ * first .. first+count-1, then n = skip; it stops when n reaches the mesh's node count.  So every skip must lie in
+ * n+1 .. node count (the walk only moves forward, it needs no stack), a leaf's skip is n + 1, and a leaf's range must
+ * lie inside the mesh's triangles; STAC_ERR_INVALID otherwise.  Boxes must contain the triangles below them; the kernel
+ * pads them per ray against float32 rounding.  Vertices are in the geom frame (prim_pos / prim_quat). */
+typedef struct stac_render_meshes {
+    int32_t nmesh;
+    const int32_t *node_offset; /* [nmesh+1], node_offset[0] = 0, every mesh has at least one node */
+    const int32_t *tri_offset;  /* [nmesh+1], tri_offset[0] = 0; at most STAC_RENDER_MAX_MESH_TRIS per mesh (STAC_ERR_CAPACITY) */
+    const float *node_box;      /* [NN,6] lo[3], hi[3] */
+    const int32_t *node_link;   /* [NN,3] skip, first, count */
+    const float *tri_vertex;    /* [NT,3,3] */
+    const int32_t *prim_mesh;   /* [P] mesh of a type-7 primitive (0 .. nmesh-1); ignored for the other types */
+} stac_render_meshes;
+
+/* stac_render_scene_create with meshes (meshes == NULL: exactly stac_render_scene_create, which refuses type 7).
+ * A scene without a type-7 primitive renders with the mesh-free kernel, bit for bit and at its speed. */
+stac_render_scene *stac_render_scene_create_with_meshes(const stac_model *m, const stac_render_tables *t,
+                                                        const stac_render_meshes *meshes);
 
 /* Renders N frames of width x height pixels, row 0 at the top.
  *   xpos[N,nbody,3], xquat[N,nbody,4]: body poses (stac_fk); kp[N,K,3] and markers[N,K,3] may be NULL (not drawn);

@@ -8,6 +8,17 @@
 * the split of a 1000-frame Stac.render-style job to .avi: FK + cameras + render, device-to-host copy, JPEG encode + write;
 * the f32 C restatement of the kernel (tests/tools/render_ref.c) on the CPU threads of the run: a CPU restatement figure,
   not a baseline of the reference (whose renderer is MuJoCo's OpenGL one).
+
+Mesh geoms (profiles/render/render_mesh_bench.json):
+
+  python profiles/tools/render_bench.py --sections kernel            # the mesh-free rodent lines only (parent comparison)
+  python profiles/tools/render_bench.py --sections mesh,hierarchy --out profiles/render/render_mesh_bench.json
+
+* ``mesh``: the rodent's stored fit with icospheres attached to its bodies (procedural, so the scene exists wherever the
+  script runs): 100 instances of 4 shared meshes, 214 400 triangles in all, about the reference's mouse; kernel frames/s at
+  1920 x 1200 from device events over at least 1 s, and the f32 restatement with meshes (tests/tools/render_mesh_ref.c);
+* ``hierarchy``: one 20 480-triangle icosphere filling the frame, with the hierarchy and with the developer switch
+  STAC_RENDER_MESH_SINGLE_LEAF=1 (read at scene creation): equal pictures, and the time of one launch each.
 """
 
 from __future__ import annotations
@@ -41,7 +52,10 @@ def main():
     ap.add_argument("--frames", type=int, default=2000)
     ap.add_argument("--viz-frames", type=int, default=1000)
     ap.add_argument("--quick", action="store_true", help="small sizes (a smoke run of this script)")
+    ap.add_argument("--sections", default="kernel,viz,cpu", help="comma list of kernel, viz, cpu, mesh, hierarchy")
+    ap.add_argument("--mesh-frames", type=int, default=200)
     args = ap.parse_args()
+    sections = set(args.sections.split(","))
     from render_cases import kp_rgba, rodent_scene
     from stac_mjx_amd.engine import Engine
     from stac_mjx_amd.fit_model import finish_fit_setup
@@ -70,7 +84,7 @@ def main():
     xpos, xquat, markers = r.poses(torch.as_tensor(qpos).cuda(), dv["offsets"])
     kpt = torch.as_tensor(kp, dtype=torch.float32).cuda().reshape(N, r.K, 3)
     rgb = torch.empty((N, H, W, 3), dtype=torch.uint8, device="cuda:0")
-    for camera in ("close_profile", -1):
+    for camera in ("close_profile", -1) if "kernel" in sections else ():
         cam, tanh = r.cameras(camera, xpos, xquat, t.qpos0, t.body_parentid)
         for show in (False, True):
             launch = lambda: r.handle.render(xpos, xquat, kpt, markers, show, cam, tanh, W, H, rgb)
@@ -94,6 +108,13 @@ def main():
             print(key, json.dumps(res["kernel"][key]), flush=True)
     del rgb
     torch.cuda.empty_cache()
+
+    if "mesh" in sections:
+        res["mesh"] = mesh_section(args, r, fs, scene, cfg, dv, W, H)
+    if "hierarchy" in sections:
+        res["hierarchy"] = hierarchy_section(args, eng, W, H)
+    if not {"viz", "cpu"} & sections:
+        return finish(args, res)
 
     # a viz job: FK + cameras + render, copy to the host, JPEG encode + AVI write
     V = 50 if args.quick else args.viz_frames
@@ -128,9 +149,140 @@ def main():
     dt = time.perf_counter() - t0
     res["cpu_restatement_f32"] = {"frames": nc, "frames_per_s": nc / dt, "threads": int(os.environ.get("OMP_NUM_THREADS", "0") or 0)}
     print("cpu_restatement_f32", json.dumps(res["cpu_restatement_f32"]), flush=True)
+    finish(args, res)
+
+
+def finish(args, res):
     if args.out:
         Path(args.out).parent.mkdir(parents=True, exist_ok=True)
         Path(args.out).write_text(json.dumps(res, indent=1) + "\n")
+
+
+def timed(launch, min_s=1.0):
+    """(launches, seconds) of ``launch`` repeated for at least ``min_s`` of device time, after one warm-up."""
+    launch()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    n, elapsed = 0, 0.0
+    e0.record()
+    while elapsed < min_s or n < 2:
+        launch()
+        n += 1
+        e1.record()
+        e1.synchronize()
+        elapsed = e0.elapsed_time(e1) / 1e3
+    return n, elapsed
+
+
+def mesh_bench_scene(scene, n_inst=100):
+    """The rodent's scene with ``n_inst`` icospheres on its bodies: 4 shared meshes (subdivisions 2 to 5, radius 6 to 12 mm;
+    30, 60, 5 and 5 instances of 100: 214 400 triangles, the reference's mouse has 207 k in 100 files), instance k on body
+    1 + k % (nbody - 1), offset by a few mm; see-through like every geom of a moving body.  Returns the scene, the triangle
+    count over the instances and the time to build the hierarchies."""
+    import copy
+
+    from render_mesh_cases import icosphere
+    from stac_mjx_amd.mesh import make_mesh
+    from stac_mjx_amd.mjcf import GEOM_MESH
+
+    t0 = time.perf_counter()
+    meshes = [make_mesh(f"ico{s}", icosphere(s, 0.006 + 0.002 * i)) for i, s in enumerate((2, 3, 4, 5))]
+    build_s = time.perf_counter() - t0
+    sc = copy.copy(scene)
+    rng = np.random.default_rng(0)
+    G = len(scene.geom_names)
+    body = 1 + np.arange(n_inst) % (scene.nbody - 1)
+    which = rng.permutation(np.repeat([0, 1, 2, 3], [30, 60, 5, 5]))[:n_inst]
+    add = lambda a, b: np.concatenate([a, b])
+    sc.geom_names = list(scene.geom_names) + [f"ico_{k}" for k in range(n_inst)]
+    sc.geom_type = add(scene.geom_type, np.full(n_inst, GEOM_MESH, np.int32))
+    sc.geom_body = add(scene.geom_body, body.astype(np.int32))
+    sc.geom_group = add(scene.geom_group, np.zeros(n_inst, np.int32))
+    sc.geom_size = add(scene.geom_size, np.zeros((n_inst, 3)))
+    sc.geom_pos = add(scene.geom_pos, rng.uniform(-0.004, 0.004, size=(n_inst, 3)))
+    sc.geom_quat = add(scene.geom_quat, np.tile([1.0, 0, 0, 0], (n_inst, 1)))
+    sc.geom_rgba = add(scene.geom_rgba, np.concatenate([rng.uniform(0.2, 1, size=(n_inst, 3)), np.ones((n_inst, 1))], 1))
+    sc.geom_checker = add(scene.geom_checker, np.zeros(n_inst, bool))
+    sc.geom_rgb2 = add(scene.geom_rgb2, np.zeros((n_inst, 3)))
+    sc.geom_texrepeat = add(scene.geom_texrepeat, np.ones((n_inst, 2)))
+    sc.geom_texuniform = add(scene.geom_texuniform, np.zeros(n_inst, bool))
+    sc.geom_mass = add(scene.geom_mass, np.zeros(n_inst))
+    sc.geom_mesh = add(scene.geom_mesh if scene.geom_mesh is not None else np.full(G, -1, np.int32), which.astype(np.int32))
+    sc.meshes = meshes
+    return sc, int(sum(meshes[m].n_tris for m in which)), build_s
+
+
+def mesh_section(args, r, fs, scene, cfg, dv, W, H):
+    from render_cases import kp_rgba
+    from stac_mjx_amd.render import Renderer
+
+    n_inst = 20 if args.quick else 100
+    sc, tris, build_s = mesh_bench_scene(scene, n_inst)
+    meshes = sc.meshes
+    pairs = cfg["KEYPOINT_MODEL_PAIRS"]
+    rm = Renderer(r.engine, sc, list(pairs), list(pairs.values()), kp_rgba(cfg), float(cfg["MARKER_SIZE"]), memory_budget=16 << 30)
+    N = 20 if args.quick else args.mesh_frames
+    reps = (N + 49) // 50
+    qpos, kp = np.tile(dv["qpos"], (reps, 1))[:N], np.tile(dv["kp_data"], (reps, 1))[:N]
+    xpos, xquat, markers = rm.poses(torch.as_tensor(qpos).cuda(), dv["offsets"])
+    kpt = torch.as_tensor(kp, dtype=torch.float32).cuda().reshape(N, rm.K, 3)
+    rgb = torch.empty((N, H, W, 3), dtype=torch.uint8, device="cuda:0")
+    t = fs.tables
+    out = {"instances": n_inst, "meshes": len(meshes), "triangles_over_instances": tris, "build_s": build_s, "frames": N,
+           "primitives": rm.P + 3 * rm.K, "kernel": {}}
+    for camera in ("close_profile", -1):
+        cam, tanh = rm.cameras(camera, xpos, xquat, t.qpos0, t.body_parentid)
+        n, elapsed = timed(lambda: rm.handle.render(xpos, xquat, kpt, markers, False, cam, tanh, W, H, rgb))
+        fps = n * N / elapsed
+        out["kernel"][f"{camera}_plain"] = {"frames_per_s": fps, "ms_per_frame": 1e3 / fps, "launches": n, "window_s": elapsed}
+        print("mesh", camera, json.dumps(out["kernel"][f"{camera}_plain"]), flush=True)
+    from build_render_mesh_ref import RenderRef as MeshRef
+
+    ref = MeshRef("float")
+    nc = 1 if args.quick else 2
+    t0 = time.perf_counter()
+    ref.render(rm.tables, t.nbody, xpos[:nc].cpu().numpy(), xquat[:nc].cpu().numpy(), kp[:nc], markers[:nc].cpu().numpy(), False,
+               cam[:nc].cpu().numpy(), tanh, W, H)
+    dt = time.perf_counter() - t0
+    out["cpu_restatement_f32"] = {"frames": nc, "frames_per_s": nc / dt, "threads": int(os.environ.get("OMP_NUM_THREADS", "0") or 0)}
+    print("mesh cpu_restatement_f32", json.dumps(out["cpu_restatement_f32"]), flush=True)
+    rm.close()
+    return out
+
+
+def hierarchy_section(args, eng, W, H):
+    """One icosphere of 20 480 triangles filling the frame: the hierarchy against the single-leaf upload."""
+    from render_cases import look_at
+    from render_mesh_cases import icosphere, static_scene
+    from stac_mjx_amd.mesh import make_mesh
+    from stac_mjx_amd.render import RenderSceneHandle
+
+    m = make_mesh("ico5", icosphere(5, 0.5))
+    sc = static_scene([m], [(0, [0, 0, 0.6], [1, 0, 0, 0], [0.7, 0.7, 0.9, 1], 0)], [look_at([1.3, 0.2, 0.9], [0, 0, 0.6])], K=eng.K)
+    t = dict(sc[0])
+    t["kp_rgba"] = np.ones((eng.K, 4), np.float32)
+    xpos = np.zeros((1, eng.nbody, 3), np.float32)
+    xquat = np.zeros((1, eng.nbody, 4), np.float32)
+    xquat[..., 0] = 1
+    d = lambda a: torch.as_tensor(np.ascontiguousarray(a)).cuda()
+    out = {"triangles": m.n_tris, "width": W, "height": H}
+    pics = {}
+    for name, val in (("hierarchy", "0"), ("single_leaf", "1")):
+        os.environ["STAC_RENDER_MESH_SINGLE_LEAF"] = val  # read by stac_render_scene_create_with_meshes
+        h = RenderSceneHandle(eng, t)
+        rgb = torch.empty((1, H, W, 3), dtype=torch.uint8, device="cuda:0")
+        seg = torch.empty((1, H, W), dtype=torch.int32, device="cuda:0")
+        depth = torch.empty((1, H, W), dtype=torch.float32, device="cuda:0")
+        a = (d(xpos), d(xquat), d(sc[3]), d(sc[4]), False, d(sc[5]), sc[6], W, H, rgb, seg, depth)
+        n, elapsed = timed(lambda: h.render(*a), min_s=0.2)
+        out[name + "_ms_per_launch"] = 1e3 * elapsed / n
+        pics[name] = (rgb.cpu().numpy(), seg.cpu().numpy(), depth.cpu().numpy().view(np.uint32))
+        h.close()
+    os.environ.pop("STAC_RENDER_MESH_SINGLE_LEAF", None)
+    out["pictures_equal"] = bool(all((x == y).all() for x, y in zip(pics["hierarchy"], pics["single_leaf"])))
+    out["mesh_share_of_pixels"] = float((pics["hierarchy"][1] >= 0).mean())
+    print("hierarchy", json.dumps(out), flush=True)
+    return out
 
 
 if __name__ == "__main__":

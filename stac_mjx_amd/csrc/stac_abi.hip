@@ -1939,7 +1939,7 @@ extern "C" int32_t stac_m_phase_finish(const stac_model *m, const float *partial
 }
 
 // ---- rendering (stac_render.hip) ------------------------------------------------------------------------------------
-namespace stac { hipError_t launch_render(const RenderScene *S, const RenderCall &C, hipStream_t s); }
+namespace stac { hipError_t launch_render(const RenderScene *S, const RenderCall &C, bool meshes, hipStream_t s); }
 
 struct stac_render_scene {
     int device = 0;
@@ -1947,9 +1947,68 @@ struct stac_render_scene {
     RenderScene *d_scene = nullptr;
     int32_t *d_int = nullptr;
     float *d_float = nullptr;
+    float *d_nodes = nullptr;      // meshes: kRenderNodeWords words per node (see stac_render.hpp)
+    float *d_tris = nullptr;       // [NT,3,3]
+    bool has_mesh = false;         // a type-7 primitive: render with the mesh kernel
 };
 
+// Checks stac_render_meshes against the tables (see include/stac_hip.h).  Returns false after fail().
+static bool check_render_meshes(const stac_render_tables *t, const stac_render_meshes *ms, bool *has_mesh) {
+    const std::string who = "stac_render_scene_create_with_meshes: ";
+    *has_mesh = false;
+    if (ms->nmesh < 0 || (ms->nmesh && (!ms->node_offset || !ms->tri_offset || !ms->node_box || !ms->node_link || !ms->tri_vertex))) {
+        fail(STAC_ERR_INVALID, who + "bad argument");
+        return false;
+    }
+    if (ms->nmesh && (ms->node_offset[0] != 0 || ms->tri_offset[0] != 0)) {
+        fail(STAC_ERR_INVALID, who + "node_offset[0] and tri_offset[0] must be 0");
+        return false;
+    }
+    for (int k = 0; k < ms->nmesh; ++k) {
+        const long nn = (long)ms->node_offset[k + 1] - ms->node_offset[k], nt = (long)ms->tri_offset[k + 1] - ms->tri_offset[k];
+        if (nn < 1 || nt < 0) {
+            fail(STAC_ERR_INVALID, who + "mesh " + std::to_string(k) + " has no node, or offsets that decrease");
+            return false;
+        }
+        if (nt > STAC_RENDER_MAX_MESH_TRIS) {
+            fail(STAC_ERR_CAPACITY, who + "mesh " + std::to_string(k) + " has " + std::to_string(nt) +
+                                        " triangles, more than STAC_RENDER_MAX_MESH_TRIS = " + std::to_string(STAC_RENDER_MAX_MESH_TRIS));
+            return false;
+        }
+        const int32_t *link = ms->node_link + 3 * (size_t)ms->node_offset[k];
+        for (long n = 0; n < nn; ++n) {
+            const long skip = link[3 * n], first = link[3 * n + 1], count = link[3 * n + 2];
+            if (skip <= n || skip > nn || (count > 0 && skip != n + 1)) {
+                fail(STAC_ERR_INVALID, who + "mesh " + std::to_string(k) + " node " + std::to_string(n) + ": skip link " +
+                                           std::to_string(skip) + " does not point forward inside the mesh's " + std::to_string(nn) +
+                                           " nodes (a leaf's is the next node)");
+                return false;
+            }
+            if (count < 0 || (count > 0 && (first < 0 || first + count > nt))) {
+                fail(STAC_ERR_INVALID, who + "mesh " + std::to_string(k) + " node " + std::to_string(n) + ": leaf range " +
+                                           std::to_string(first) + " + " + std::to_string(count) + " outside the mesh's " +
+                                           std::to_string(nt) + " triangles");
+                return false;
+            }
+        }
+    }
+    for (int i = 0; i < t->nprim; ++i) {
+        if (t->prim_type[i] != 7) continue;
+        *has_mesh = true;
+        if (!ms->prim_mesh || ms->prim_mesh[i] < 0 || ms->prim_mesh[i] >= ms->nmesh) {
+            fail(STAC_ERR_INVALID, who + "primitive " + std::to_string(i) + " is a mesh (type 7) without a mesh, or with a mesh index out of range");
+            return false;
+        }
+    }
+    return true;
+}
+
 extern "C" stac_render_scene *stac_render_scene_create(const stac_model *m, const stac_render_tables *t) {
+    return stac_render_scene_create_with_meshes(m, t, nullptr);
+}
+
+extern "C" stac_render_scene *stac_render_scene_create_with_meshes(const stac_model *m, const stac_render_tables *t,
+                                                                   const stac_render_meshes *ms) {
     if (!m || !t || t->nprim < 0 || t->nkp < 0 || t->nlight < 0 || (t->nprim && (!t->prim_type || !t->prim_body || !t->prim_flags
         || !t->prim_size || !t->prim_pos || !t->prim_quat || !t->prim_rgba || !t->prim_rgb2 || !t->prim_texrepeat))
         || (t->nkp && !t->kp_rgba) || (t->nlight && (!t->light_dir || !t->light_diffuse))) {
@@ -1965,10 +2024,42 @@ extern "C" stac_render_scene *stac_render_scene_create(const stac_model *m, cons
     const int P = t->nprim, K = t->nkp, NL = t->nlight;
     for (int i = 0; i < P; ++i) {
         const int ty = t->prim_type[i];
-        if (t->prim_body[i] < 0 || t->prim_body[i] >= m->h.nbody || !(ty == 0 || (ty >= 2 && ty <= 6))) {
+        if (t->prim_body[i] < 0 || t->prim_body[i] >= m->h.nbody || !(ty == 0 || (ty >= 2 && ty <= 6) || (ty == 7 && ms))) {
             fail(STAC_ERR_INVALID, "stac_render_scene_create: primitive " + std::to_string(i) + " has a bad type or body");
             return nullptr;
         }
+    }
+    bool has_mesh = false;
+    if (ms && !check_render_meshes(t, ms, &has_mesh)) return nullptr;
+    // with meshes the int block grows by mesh[P] node_offset[M+1] tri_offset[M+1]; nodes and triangles get blocks of their own
+    const int M = has_mesh ? ms->nmesh : 0;
+    std::vector<float> hnodes;
+    std::vector<int32_t> hnoff, htoff;
+    if (has_mesh) {
+        // developer switch: every mesh as one leaf over all its triangles, to show what the hierarchy saves
+        const char *env = getenv("STAC_RENDER_MESH_SINGLE_LEAF");
+        const bool single = env && env[0] && env[0] != '0';
+        hnoff.push_back(0);
+        for (int k = 0; k < M; ++k) {
+            const size_t n0 = (size_t)ms->node_offset[k], nn = single ? 1 : (size_t)(ms->node_offset[k + 1] - ms->node_offset[k]);
+            for (size_t n = 0; n < nn; ++n) {
+                const float *b = ms->node_box + 6 * (n0 + n);
+                const int32_t *l = ms->node_link + 3 * (n0 + n);
+                const bool leaf = single || l[2] > 0;
+                // device node: lo[3], hi[3], then (first, count) of a leaf or (skip, 0) of an inner node, as bit patterns
+                const int32_t nt = ms->tri_offset[k + 1] - ms->tri_offset[k];
+                const int32_t w6 = single ? (nt > 0 ? 0 : 1) : (leaf ? l[1] : l[0]);  // (an empty mesh: an inner node that ends the walk)
+                const int32_t w7 = single ? nt : (leaf ? l[2] : 0);
+                float f6, f7;
+                memcpy(&f6, &w6, 4);
+                memcpy(&f7, &w7, 4);
+                hnodes.insert(hnodes.end(), b, b + 6);
+                hnodes.push_back(f6);
+                hnodes.push_back(f7);
+            }
+            hnoff.push_back((int32_t)(hnodes.size() / stac::kRenderNodeWords));
+        }
+        htoff.assign(ms->tri_offset, ms->tri_offset + M + 1);
     }
     // int block: type[P] body[P] flags[P]; float block: size[3P] pos[3P] quat[4P] rgba[4P] rgb2[3P] tex[2P] kp_rgba[4K]
     // light_dir[3NL] light_diff[3NL]
@@ -1976,6 +2067,11 @@ extern "C" stac_render_scene *stac_render_scene_create(const stac_model *m, cons
     hi.insert(hi.end(), t->prim_type, t->prim_type + P);
     hi.insert(hi.end(), t->prim_body, t->prim_body + P);
     hi.insert(hi.end(), t->prim_flags, t->prim_flags + P);
+    if (has_mesh) {
+        for (int i = 0; i < P; ++i) hi.push_back(t->prim_type[i] == 7 ? ms->prim_mesh[i] : -1);
+        hi.insert(hi.end(), hnoff.begin(), hnoff.end());
+        hi.insert(hi.end(), htoff.begin(), htoff.end());
+    }
     std::vector<float> hf;
     size_t off[8];
     auto put = [&](int k, const float *p, size_t n) { off[k] = hf.size(); if (n) hf.insert(hf.end(), p, p + n); };
@@ -1994,6 +2090,8 @@ extern "C" stac_render_scene *stac_render_scene_create(const stac_model *m, cons
         if (sc->d_int) (void)hipFree(sc->d_int);
         if (sc->d_float) (void)hipFree(sc->d_float);
         if (sc->d_scene) (void)hipFree(sc->d_scene);
+        if (sc->d_nodes) (void)hipFree(sc->d_nodes);
+        if (sc->d_tris) (void)hipFree(sc->d_tris);
         delete sc;
         return nullptr;
     };
@@ -2002,6 +2100,18 @@ extern "C" stac_render_scene *stac_render_scene_create(const stac_model *m, cons
     e = upload(&sc->d_float, hf.data(), hf.size());
     if (e != hipSuccess) return bail(e);
     RenderScene &S = sc->S;
+    sc->has_mesh = has_mesh;
+    if (has_mesh) {
+        e = upload(&sc->d_nodes, hnodes.data(), hnodes.size());
+        if (e != hipSuccess) return bail(e);
+        const size_t nt = 9 * (size_t)ms->tri_offset[M];
+        const float none[9] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+        e = upload(&sc->d_tris, nt ? ms->tri_vertex : none, nt ? nt : 9);
+        if (e != hipSuccess) return bail(e);
+        S.nmesh = M;
+        S.prim_mesh = sc->d_int + 3 * P; S.mesh_node_off = sc->d_int + 4 * P; S.mesh_tri_off = sc->d_int + 4 * P + M + 1;
+        S.mesh_nodes = sc->d_nodes; S.mesh_tris = sc->d_tris;
+    }
     S.P = P; S.K = K; S.nbody = m->h.nbody; S.nlight = NL;
     S.prim_type = sc->d_int; S.prim_body = sc->d_int + P; S.prim_flags = sc->d_int + 2 * P;
     S.prim_size = sc->d_float + off[0]; S.prim_pos = sc->d_float + off[1]; S.prim_quat = sc->d_float + off[2];
@@ -2025,6 +2135,8 @@ extern "C" void stac_render_scene_destroy(stac_render_scene *sc) {
     (void)hipFree(sc->d_int);
     (void)hipFree(sc->d_float);
     (void)hipFree(sc->d_scene);
+    if (sc->d_nodes) (void)hipFree(sc->d_nodes);
+    if (sc->d_tris) (void)hipFree(sc->d_tris);
     if (sw) (void)hipSetDevice(prev);
     delete sc;
 }
@@ -2041,7 +2153,7 @@ extern "C" int32_t stac_render(const stac_render_scene *sc, int32_t N, const flo
     C.N = N; C.W = width; C.H = height; C.show_error = show_error ? 1 : 0;
     C.xpos = xpos; C.xquat = xquat; C.kp = kp; C.markers = markers; C.cam = cam; C.tanh = tan_half_fovy;
     C.rgb = rgb_out; C.seg = seg_out; C.depth = depth_out;
-    const hipError_t e = launch_render(sc->d_scene, C, (hipStream_t)stream);
+    const hipError_t e = launch_render(sc->d_scene, C, sc->has_mesh, (hipStream_t)stream);
     if (sw) (void)hipSetDevice(prev);
     if (e != hipSuccess) return fail(STAC_ERR_HIP, std::string("stac_render: ") + hipGetErrorString(e));
     return STAC_OK;

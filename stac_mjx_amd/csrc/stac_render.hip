@@ -1,4 +1,4 @@
-// Ray caster of primitive-geom scenes: the hot path of Renderer / Stac.render (DESIGN.md "Rendering").
+// Ray caster of primitive- and mesh-geom scenes: the hot path of Renderer / Stac.render (DESIGN.md "Rendering").
 //
 // One workgroup = one 16 x 16 tile of one frame (grid z strides over the frames).  Per frame the workgroup
 //   1. builds the frame's primitive records in LDS (the primitive pass: world pose and bounding sphere of every
@@ -6,6 +6,10 @@
 //   2. culls them against the tile's frustum into a compact list (wave ballot + prefix count);
 //   3. casts one ray per pixel centre against the list, keeps the nearest opaque hit and the kRenderLayers nearest
 //      transparent hits in registers, shades and composites them, and writes rgb / seg / depth.
+// A mesh instance is one more primitive: its record holds the pose of the geom frame and the bounding sphere of the mesh's
+// root box; its triangles and their hierarchy stay in global memory (hit_mesh).  The kernel is built twice: render_kernel<false>
+// is the kernel of mesh-free scenes, render_kernel<true> adds the mesh records, the culled list of mesh instances and the
+// loop over it, after the loop over the quadrics and boxes so that the lanes of a wavefront walk the same tree together.
 // The arithmetic is written operation by operation (no FMA: -ffp-contract=off) so that tests/tools/render_ref.c,
 // built with float, reproduces every output bit for bit.
 #include <hip/hip_runtime.h>
@@ -18,7 +22,9 @@
 namespace stac {
 namespace {
 
-enum { T_NONE = -1, T_PLANE = 0, T_SPHERE = 2, T_CAPSULE = 3, T_ELLIPSOID = 4, T_CYLINDER = 5, T_BOX = 6 };
+enum { T_NONE = -1, T_PLANE = 0, T_SPHERE = 2, T_CAPSULE = 3, T_ELLIPSOID = 4, T_CYLINDER = 5, T_BOX = 6, T_MESH = 7 };
+
+constexpr float kMeshPad = 1.0f / 65536.0f;  // hit_mesh: box padding per unit of coordinate magnitude (float32 eps = 2^-24)
 
 __device__ inline float dot3(const float *a, const float *b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
 
@@ -47,12 +53,16 @@ __device__ inline void mat_vec(const float *R, const float *v, float *out) {
 __device__ inline bool finite3(const float *p) { return p[0] == p[0] && p[1] == p[1] && p[2] == p[2]; }
 
 // Record layout (kRenderRecWords floats): c[0:3] world centre, R[3:12] world rotation (row-major), size[12:15],
-// bounding radius [15], type [16], flags [17] (as floats: small integers are exact).
+// bounding radius [15], type [16], flags [17] (as floats: small integers are exact).  A mesh: c = world centre of the mesh's
+// root box (what the cull needs), [12:15] = world position of the geom frame's origin, [18] = mesh index, [19] = sum over the
+// axes of the root box's largest |coordinate| (the scale of hit_mesh's padding).
+template <bool MESH>
 __device__ void build_prim(const RenderScene &S, const RenderCall &C, int f, int i, float *r) {
     int type = T_NONE, flags = 0;
     float c[3] = {0.0f, 0.0f, 0.0f};
     float R[9] = {1.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 1.0f};
     float sz[3] = {0.0f, 0.0f, 0.0f};
+    [[maybe_unused]] float mesh_brad = 0.0f, mesh_idx = 0.0f, mesh_mag = 0.0f;
     const int P = S.P, K = S.K;
     if (i < P) {
         type = S.prim_type[i];
@@ -72,6 +82,26 @@ __device__ void build_prim(const RenderScene &S, const RenderCall &C, int f, int
         for (int a = 0; a < 3; ++a) {
             c[a] = xp[a] + lp[a];
             sz[a] = S.prim_size[3 * i + a];
+        }
+        if constexpr (MESH) {
+            if (type == T_MESH) {
+                const int mi = S.prim_mesh[i];
+                const float *nd = S.mesh_nodes + (size_t)S.mesh_node_off[mi] * kRenderNodeWords;
+                float bc[3], he[3], wc[3];
+                float mag = 0.0f;
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    bc[a] = (nd[a] + nd[3 + a]) * 0.5f;
+                    he[a] = (nd[3 + a] - nd[a]) * 0.5f;
+                    mag = mag + fmaxf(fabsf(nd[a]), fabsf(nd[3 + a]));
+                }
+                mat_vec(R, bc, wc);
+#pragma unroll
+                for (int a = 0; a < 3; ++a) { sz[a] = c[a]; c[a] = c[a] + wc[a]; }
+                mesh_brad = sqrtf(dot3(he, he));
+                mesh_idx = (float)mi;
+                mesh_mag = mag;
+            }
         }
     } else if (i < P + K) {
         const int k = i - P;
@@ -118,6 +148,11 @@ __device__ void build_prim(const RenderScene &S, const RenderCall &C, int f, int
     else if (type == T_CAPSULE) brad = sz[1] + sz[0];
     else if (type == T_CYLINDER || type == T_PLANE) brad = sqrtf(sz[0] * sz[0] + sz[1] * sz[1]);
     else if (type == T_BOX) brad = sqrtf(dot3(sz, sz));
+    if constexpr (MESH) {
+        if (type == T_MESH) brad = mesh_brad;
+        r[18] = mesh_idx;
+        r[19] = mesh_mag;
+    }
 #pragma unroll
     for (int q = 0; q < 3; ++q) { r[q] = c[q]; r[12 + q] = sz[q]; }
 #pragma unroll
@@ -239,8 +274,72 @@ __device__ float intersect(const float *r, const float *o, const float *d, float
     return -1.0f;
 }
 
-// Unit world normal of record r at the hit (t, face) of the ray o + t d.
-__device__ void normal_at(const float *r, const float *o, const float *d, float t, int face, float *n) {
+// Nearest hit of the ray against the mesh instance of record r: t > 0 of the triangle with the smallest t, ties to the lower
+// triangle index (*tri), or -1.  The ray goes to the geom frame; the nodes are walked in their depth-first order by skip
+// links (no stack): a node whose padded box the ray misses, or enters beyond the best hit so far, hands over to its skip link.
+// The padding (kMeshPad per unit of coordinate magnitude, far above the rounding of the slab test and of the triangle test)
+// makes sure that no box is rejected whose triangle the ray hits, so the result is that of testing every triangle.
+// Two-sided Moeller-Trumbore test on the face normal N = e1 x e2; N = 0 (a zero-area triangle) gives det = 0: never hit.
+__device__ float hit_mesh(const RenderScene &S, const float *r, const float *o, const float *d, int *tri) {
+    const float *R = r + 3, *org = r + 12;
+    const int mi = (int)r[18];
+    const float oc[3] = {o[0] - org[0], o[1] - org[1], o[2] - org[2]};
+    float ol[3], dl[3];
+    mat_tvec(R, oc, ol);
+    mat_tvec(R, d, dl);
+    const float pad = (fabsf(ol[0]) + fabsf(ol[1]) + fabsf(ol[2]) + r[19]) * kMeshPad;
+    const float idl[3] = {1.0f / dl[0], 1.0f / dl[1], 1.0f / dl[2]};
+    const int n0 = S.mesh_node_off[mi];
+    const int nn = S.mesh_node_off[mi + 1] - n0;
+    const float4 *nodes = reinterpret_cast<const float4 *>(S.mesh_nodes + (size_t)n0 * kRenderNodeWords);
+    const float *tris = S.mesh_tris + (size_t)S.mesh_tri_off[mi] * 9;
+    float best = INFINITY;
+    int btri = -1;
+    int n = 0;
+    while (n < nn) {
+        const float4 a = nodes[2 * n], b = nodes[2 * n + 1];
+        const float lo[3] = {a.x, a.y, a.z}, hi[3] = {a.w, b.x, b.y};
+        const int w6 = __float_as_int(b.z), w7 = __float_as_int(b.w);  // leaf: first, count; inner node: skip, 0
+        float tn = -INFINITY, tf = INFINITY;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float t1 = ((lo[k] - pad) - ol[k]) * idl[k], t2 = ((hi[k] + pad) - ol[k]) * idl[k];
+            const float lo_t = t1 < t2 ? t1 : t2, hi_t = t1 < t2 ? t2 : t1;
+            if (lo_t > tn) tn = lo_t;
+            if (hi_t < tf) tf = hi_t;
+        }
+        if (!(tn <= tf && tf > 0.0f && tn <= best)) {
+            n = w7 > 0 ? n + 1 : w6;
+            continue;
+        }
+        for (int k = 0; k < w7; ++k) {
+            const int ti = w6 + k;
+            const float *v = tris + (size_t)ti * 9;
+            const float e1[3] = {v[3] - v[0], v[4] - v[1], v[5] - v[2]};
+            const float e2[3] = {v[6] - v[0], v[7] - v[1], v[8] - v[2]};
+            const float N[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
+            const float det = -dot3(dl, N);
+            if (det == 0.0f) continue;
+            const float inv = 1.0f / det;
+            const float ao[3] = {ol[0] - v[0], ol[1] - v[1], ol[2] - v[2]};
+            const float dao[3] = {ao[1] * dl[2] - ao[2] * dl[1], ao[2] * dl[0] - ao[0] * dl[2], ao[0] * dl[1] - ao[1] * dl[0]};
+            const float bu = dot3(e2, dao) * inv;
+            const float bv = -dot3(e1, dao) * inv;
+            const float t = dot3(ao, N) * inv;
+            if (bu >= 0.0f && bv >= 0.0f && bu + bv <= 1.0f && t > 0.0f && (t < best || (t == best && ti < btri))) {
+                best = t;
+                btri = ti;
+            }
+        }
+        n = n + 1;
+    }
+    *tri = btri;
+    return btri >= 0 ? best : -1.0f;
+}
+
+// Unit world normal of record r at the hit (t, face) of the ray o + t d (a mesh: of its triangle tri, towards the ray's origin).
+template <bool MESH>
+__device__ void normal_at(const RenderScene &S, const float *r, const float *o, const float *d, float t, int face, int tri, float *n) {
     const int type = (int)r[16];
     const float *c = r, *R = r + 3, *sz = r + 12;
     const float q[3] = {o[0] + d[0] * t - c[0], o[1] + d[1] * t - c[1], o[2] + d[2] * t - c[2]};
@@ -253,6 +352,17 @@ __device__ void normal_at(const float *r, const float *o, const float *d, float 
         v[0] = q[0] - w[0] * z; v[1] = q[1] - w[1] * z; v[2] = q[2] - w[2] * z;
     } else if (type == T_PLANE) {
         v[0] = R[2]; v[1] = R[5]; v[2] = R[8];
+    } else if (MESH && type == T_MESH) {
+        if constexpr (MESH) {
+            const float *p = S.mesh_tris + ((size_t)S.mesh_tri_off[(int)r[18]] + (size_t)tri) * 9;
+            const float e1[3] = {p[3] - p[0], p[4] - p[1], p[5] - p[2]};
+            const float e2[3] = {p[6] - p[0], p[7] - p[1], p[8] - p[2]};
+            float N[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
+            float dl[3];
+            mat_tvec(R, d, dl);
+            if (dot3(dl, N) > 0.0f) { N[0] = -N[0]; N[1] = -N[1]; N[2] = -N[2]; }
+            mat_vec(R, N, v);
+        }
     } else {
         float ql[3], nl[3];
         mat_tvec(R, q, ql);
@@ -276,10 +386,11 @@ __device__ void normal_at(const float *r, const float *o, const float *d, float 
 }
 
 // Shaded colour of primitive `id` (record r) at the hit (t, face).  zc = the camera's z axis (towards the viewer).
-__device__ void shade(const RenderScene &S, const float *r, int id, const float *o, const float *d, float t, int face,
+template <bool MESH>
+__device__ void shade(const RenderScene &S, const float *r, int id, const float *o, const float *d, float t, int face, int tri,
                       const float *zc, float *col) {
     float n[3];
-    normal_at(r, o, d, t, face, n);
+    normal_at<MESH>(S, r, o, d, t, face, tri, n);
     const int P = S.P, K = S.K;
     float rgb[3];
     if (id < P) {
@@ -348,11 +459,33 @@ __device__ inline uint8_t quant(float c) {
     return (uint8_t)(int)floorf(x * 255.0f + 0.5f);
 }
 
+// One hit of the pixel's ray: a transparent one goes into the sorted layers, an opaque one competes for the nearest.
+// key = bits(t) << 32 | id << 22 | tri << 2 | face (t > 0, so the bits of t order like t; id < 2^10, tri < 2^20, 0 for a
+// primitive that is no mesh): the layers are ordered by (t, id); ~0 = empty.
+__device__ __forceinline__ void take_hit(const float *r, int id, float t, int face, int tri, unsigned long long (&L)[kRenderLayers],
+                                         float &to, int &io, int &fo, int &tro) {
+    if (((int)r[17]) & STAC_RENDER_TRANSPARENT) {
+        unsigned long long key = ((unsigned long long)__float_as_uint(t) << 32) | ((unsigned)id << (kRenderTriBits + 2)) |
+                                 ((unsigned)tri << 2) | (unsigned)face;
+#pragma unroll
+        for (int k = 0; k < kRenderLayers; ++k) {  // insertion into the sorted list; the largest key drops out
+            const unsigned long long cur = L[k];
+            L[k] = key < cur ? key : cur;
+            key = key < cur ? cur : key;
+        }
+    } else if (t < to || (t == to && id < io)) {
+        to = t; io = id; fo = face; tro = tri;
+    }
+}
+
+template <bool MESH>
 __global__ __launch_bounds__(kRenderTile *kRenderTile) void render_kernel(const RenderScene *__restrict__ Sp, RenderCall C) {
     const RenderScene &S = *Sp;
     __shared__ float rec[kRenderMaxPrims * kRenderRecWords];
     __shared__ int list[kRenderMaxPrims];
     __shared__ int wcount[kRenderTile * kRenderTile / 64];
+    __shared__ int mlist[MESH ? kRenderMaxPrims : 1];  // the tile's mesh instances
+    __shared__ int wmcount[kRenderTile * kRenderTile / 64];
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
     const int Ptot = S.P + 3 * S.K;
@@ -364,13 +497,30 @@ __global__ __launch_bounds__(kRenderTile *kRenderTile) void render_kernel(const 
     const float vT = pix_v(y0, C.H, tv), vB = pix_v(min(y0 + kRenderTile, C.H) - 1, C.H, tv);
     for (int f = blockIdx.z; f < C.N; f += gridDim.z) {
         __syncthreads();  // the previous frame's readers are done with rec / list
-        for (int i = tid; i < Ptot; i += kRenderTile * kRenderTile) build_prim(S, C, f, i, rec + i * kRenderRecWords);
+        for (int i = tid; i < Ptot; i += kRenderTile * kRenderTile) build_prim<MESH>(S, C, f, i, rec + i * kRenderRecWords);
         __syncthreads();
         const float *cam = C.cam + (size_t)f * 12;
         int count = 0;
+        [[maybe_unused]] int mcount = 0;
         for (int base = 0; base < Ptot; base += kRenderTile * kRenderTile) {
             const int i = base + tid;
-            const bool vis = i < Ptot && !culled(rec + i * kRenderRecWords, cam, uL, uR, vT, vB);
+            bool vis = i < Ptot && !culled(rec + i * kRenderRecWords, cam, uL, uR, vT, vB);
+            bool mvis = false;
+            if constexpr (MESH) {
+                mvis = vis && (int)rec[i * kRenderRecWords + 16] == T_MESH;
+                vis = vis && !mvis;
+                const unsigned long long mm = __ballot(mvis);
+                if (lane == 0) wmcount[wave] = __popcll(mm);
+                __syncthreads();
+                int moff = mcount, mtotal = 0;
+#pragma unroll
+                for (int w = 0; w < kRenderTile * kRenderTile / 64; ++w) {
+                    if (w < wave) moff += wmcount[w];
+                    mtotal += wmcount[w];
+                }
+                if (mvis) mlist[moff + __popcll(mm & ((1ull << lane) - 1ull))] = i;
+                mcount += mtotal;
+            }
             const unsigned long long mask = __ballot(vis);
             const int pre = __popcll(mask & ((1ull << lane) - 1ull));
             if (lane == 0) wcount[wave] = __popcll(mask);
@@ -398,9 +548,9 @@ __global__ __launch_bounds__(kRenderTile *kRenderTile) void render_kernel(const 
         }
         const float dd = dot3(d, d);
         float to = INFINITY;
-        int io = -1, fo = 0;
-        // the kRenderLayers nearest transparent hits, sorted by (t, id): key = bits(t) << 32 | id << 2 | face (t > 0, so the
-        // bits of t order like t); ~0 = empty.  One 64-bit key per slot keeps t, id and face together through the network.
+        int io = -1, fo = 0, tro = 0;
+        // the kRenderLayers nearest transparent hits, sorted by (t, id): see take_hit.  One 64-bit key per slot keeps t, id,
+        // triangle and face together through the network.
         unsigned long long L[kRenderLayers];
 #pragma unroll
         for (int k = 0; k < kRenderLayers; ++k) L[k] = ~0ull;
@@ -410,29 +560,30 @@ __global__ __launch_bounds__(kRenderTile *kRenderTile) void render_kernel(const 
             int face;
             const float t = intersect(r, o, d, dd, &face);
             if (!(t > 0.0f)) continue;
-            if (((int)r[17]) & STAC_RENDER_TRANSPARENT) {
-                unsigned long long key = ((unsigned long long)__float_as_uint(t) << 32) | ((unsigned)id << 2) | (unsigned)face;
-#pragma unroll
-                for (int k = 0; k < kRenderLayers; ++k) {  // insertion into the sorted list; the largest key drops out
-                    const unsigned long long cur = L[k];
-                    L[k] = key < cur ? key : cur;
-                    key = key < cur ? cur : key;
-                }
-            } else if (t < to || (t == to && id < io)) {
-                to = t; io = id; fo = face;
+            take_hit(r, id, t, face, 0, L, to, io, fo, tro);
+        }
+        if constexpr (MESH) {
+            for (int j = 0; j < mcount; ++j) {
+                const int id = mlist[j];
+                const float *r = rec + id * kRenderRecWords;
+                int tri;
+                const float t = hit_mesh(S, r, o, d, &tri);
+                if (!(t > 0.0f)) continue;
+                take_hit(r, id, t, 0, tri, L, to, io, fo, tro);
             }
         }
         const float zc[3] = {Rc[2], Rc[5], Rc[8]};
         float col[3] = {S.bg[0], S.bg[1], S.bg[2]};
-        if (io >= 0) shade(S, rec + io * kRenderRecWords, io, o, d, to, fo, zc, col);
+        if (io >= 0) shade<MESH>(S, rec + io * kRenderRecWords, io, o, d, to, fo, tro, zc, col);
         const float a = S.alpha, na = 1.0f - S.alpha;
 #pragma unroll
         for (int k = kRenderLayers - 1; k >= 0; --k) {  // back to front
             const float tk = __uint_as_float((unsigned)(L[k] >> 32));
-            const int ik = (int)((L[k] >> 2) & 0x3fffffffu), fk = (int)(L[k] & 3u);
+            const int ik = (int)((L[k] >> (kRenderTriBits + 2)) & 0x3ffu), fk = (int)(L[k] & 3u);
+            const int trk = (int)((L[k] >> 2) & ((1u << kRenderTriBits) - 1u));
             if (L[k] != ~0ull && tk < to) {
                 float s[3];
-                shade(S, rec + ik * kRenderRecWords, ik, o, d, tk, fk, zc, s);
+                shade<MESH>(S, rec + ik * kRenderRecWords, ik, o, d, tk, fk, trk, zc, s);
 #pragma unroll
                 for (int q = 0; q < 3; ++q) col[q] = col[q] * na + s[q] * a;
             }
@@ -450,10 +601,11 @@ __global__ __launch_bounds__(kRenderTile *kRenderTile) void render_kernel(const 
 
 }  // namespace
 
-hipError_t launch_render(const RenderScene *S, const RenderCall &C, hipStream_t s) {
+hipError_t launch_render(const RenderScene *S, const RenderCall &C, bool meshes, hipStream_t s) {
     if (C.N <= 0) return hipSuccess;
     const dim3 grid((C.W + kRenderTile - 1) / kRenderTile, (C.H + kRenderTile - 1) / kRenderTile, C.N < 65535 ? C.N : 65535);
-    hipLaunchKernelGGL(render_kernel, grid, dim3(kRenderTile * kRenderTile), 0, s, S, C);
+    if (meshes) hipLaunchKernelGGL(render_kernel<true>, grid, dim3(kRenderTile * kRenderTile), 0, s, S, C);
+    else hipLaunchKernelGGL(render_kernel<false>, grid, dim3(kRenderTile * kRenderTile), 0, s, S, C);
     return hipGetLastError();
 }
 

@@ -53,7 +53,7 @@ ABI_SYMBOLS = (
     "stac_last_error", "stac_last_error_code", "stac_abi_version", "stac_device_count", "stac_model_create", "stac_model_destroy",
     "stac_model_info", "stac_set_site_pos", "stac_get_site_pos", "stac_fk", "stac_q_solve", "stac_q_phase",
     "stac_m_phase_workspace_floats", "stac_m_phase_partial", "stac_m_phase_finish",
-    "stac_render_scene_create", "stac_render_scene_destroy", "stac_render",
+    "stac_render_scene_create", "stac_render_scene_create_with_meshes", "stac_render_scene_destroy", "stac_render",
 )  # fmt: skip
 
 

@@ -500,7 +500,8 @@ CAMERA_MODES = ("fixed", "track", "trackcom")
 @dataclass
 class RenderScene:
     """What the renderer draws of a model (float64, body frame).  Geoms and sites keep document order; ``geom_*`` holds the
-    supported primitive geoms of every group (mesh / height-field geoms are counted in ``n_skipped``)."""
+    primitive and mesh geoms of every group (height-field geoms and meshes that cannot be read are counted in
+    ``n_skipped``).  A mesh geom has ``geom_type`` GEOM_MESH and ``geom_mesh`` = its index into ``meshes``."""
 
     nbody: int
     body_names: list[str]
@@ -544,6 +545,8 @@ class RenderScene:
     body_mass: np.ndarray  # [nbody]
     body_ipos: np.ndarray  # [nbody,3] local centre of mass
     n_skipped: int = 0
+    geom_mesh: np.ndarray | None = None  # [G] index into meshes, -1 for a primitive
+    meshes: list = field(default_factory=list)  # stac_mjx_amd.mesh.Mesh: triangles in the geom frame and their hierarchy
 
 
 def _geom_volume(t: int, size: np.ndarray) -> float:
@@ -577,15 +580,61 @@ def _z_to_quat(v) -> np.ndarray:
     return _axis_angle_quat(ax, ang)
 
 
-def compile_render_scene(xml: str | Path, *, scale: float = 1.0, from_string: bool = False, log=print) -> RenderScene:
+def compile_render_scene(xml: str | Path, *, scale: float = 1.0, from_string: bool = False, log=print,
+                         asset_dir: str | Path | None = None) -> RenderScene:
     """Compile what :class:`stac_mjx_amd.render.Renderer` draws of an MJCF model.
 
     The body walk is :func:`compile_mjcf`'s (same body ids and names, same default classes and ``childclass``); geom
     ``size`` / ``pos`` / ``fromto`` of the bodies whose ``pos`` the ``dm_scale_spec`` rule scales are scaled by ``scale``.
-    ``mesh`` / ``hfield`` geoms are skipped (reported once through ``log``); other unknown types raise :class:`MjcfError`.
+    ``mesh`` geoms are drawn from their ``.stl`` / ``.obj`` file: ``<asset><mesh name file scale refpos refquat>`` (class
+    defaults included), looked up under ``<compiler meshdir>`` relative to the XML file (``asset_dir`` for a
+    ``from_string`` scene).  Vertex in the geom frame = ``scale * rotate(conj(refquat), v - refpos)``; the geom frame is the
+    geom's own ``pos`` / ``quat``; every mesh ``scale`` is multiplied by ``scale`` (``dm_scale_spec`` scales all meshes).
+    ``hfield`` geoms, and mesh geoms whose asset is undeclared, of another file type, missing or unreadable, are skipped
+    (reported once through ``log``); other unknown types raise :class:`MjcfError`.
     """
+    from . import mesh as _mesh
+
     root = ET.fromstring(xml) if from_string else ET.parse(str(xml)).getroot()
     comp = _Compiler(root)
+    # mesh assets: declared now, loaded when a drawn geom first names them
+    base = Path(asset_dir) if asset_dir is not None else (None if from_string else Path(xml).resolve().parent)
+    meshdir = ""
+    for c in root.findall("compiler"):
+        meshdir = c.attrib.get("meshdir", c.attrib.get("assetdir", meshdir))
+    mesh_defaults = _collect_defaults(root)
+    mesh_decl: dict[str, dict] = {}
+    for asset in root.findall("asset"):
+        for m in asset.findall("mesh"):
+            attrs = dict(mesh_defaults.get(m.attrib.get("class", "main"), {}).get("mesh", {}))
+            attrs.update(m.attrib)
+            name = attrs.get("name") or (Path(attrs["file"]).stem if "file" in attrs else "")
+            mesh_decl[name] = attrs
+    meshes: list = []
+    mesh_index: dict[str, int | str] = {}  # name -> index into meshes, or the reason it cannot be drawn
+
+    def load_mesh_asset(name: str):
+        if name in mesh_index:
+            return mesh_index[name]
+        attrs = mesh_decl.get(name)
+        if attrs is None:
+            res = f"mesh {name!r} is not declared"
+        elif "file" not in attrs:
+            res = f"mesh {name!r} has no file"
+        elif base is None:
+            res = f"mesh {name!r}: no asset_dir to look up {attrs['file']!r}"
+        else:
+            try:
+                tri = _mesh.load_mesh(base / meshdir / attrs["file"])
+                sc = _floats(attrs.get("scale", "1 1 1"), 3) * scale
+                tri = _mesh.place(tri, sc, _floats(attrs.get("refpos", "0 0 0"), 3), _floats(attrs.get("refquat", "1 0 0 0"), 4))
+                meshes.append(_mesh.make_mesh(name, tri))
+                res = len(meshes) - 1
+            except (_mesh.MeshError, MjcfError) as exc:
+                res = f"mesh {name!r}: {exc}"
+        mesh_index[name] = res
+        return res
+
     # assets: checker textures and materials
     textures, materials = {}, {}
     for asset in root.findall("asset"):
@@ -603,15 +652,23 @@ def compile_render_scene(xml: str | Path, *, scale: float = 1.0, from_string: bo
     tables = compile_mjcf(xml, scale=scale, from_string=from_string, _visit=visit)
     nbody = tables.nbody
 
-    G = dict(names=[], type=[], body=[], group=[], size=[], pos=[], quat=[], rgba=[], checker=[], rgb2=[], rep=[], uni=[], mass=[])
+    G = dict(names=[], type=[], body=[], group=[], size=[], pos=[], quat=[], rgba=[], checker=[], rgb2=[], rep=[], uni=[], mass=[],
+             mesh=[], cpos=[])
     n_skipped = 0
+    why_skipped: list[str] = []
     for a, bid, scaled in geoms:
-        tname = a.get("type", "sphere").strip().lower()
+        # MuJoCo's rule: a geom with a mesh and no type (its own or its class's) is a mesh geom
+        tname = a.get("type", "mesh" if "mesh" in a else "sphere").strip().lower()
         if tname not in _GEOM_TYPES:
             raise MjcfError(f"unknown geom type {tname!r}")
         t = _GEOM_TYPES[tname]
-        if t in (GEOM_MESH, GEOM_HFIELD):
+        mi = -1
+        if t == GEOM_MESH:
+            mi = load_mesh_asset(a.get("mesh", ""))
+        if t == GEOM_HFIELD or isinstance(mi, str):
             n_skipped += 1
+            if isinstance(mi, str) and mi not in why_skipped:
+                why_skipped.append(mi)
             continue
         size = np.zeros(3)
         sv = _floats(a.get("size", "0"))
@@ -635,6 +692,8 @@ def compile_render_scene(xml: str | Path, *, scale: float = 1.0, from_string: bo
             quat = comp.orientation(a)
             if scaled:
                 pos, size = pos * scale, size * scale
+        if t == GEOM_MESH:
+            size = np.zeros(3)  # a mesh geom's size is ignored
         rgba = np.array([0.5, 0.5, 0.5, 1.0])
         checker, rgb2, rep, uni = False, np.zeros(3), np.ones(2), False
         mat = materials.get(a.get("material", ""), None) if "material" in a else None
@@ -650,16 +709,24 @@ def compile_render_scene(xml: str | Path, *, scale: float = 1.0, from_string: bo
                 uni = mat.get("texuniform", "false").strip().lower() == "true"
         if "rgba" in a and not checker:
             rgba = _floats(a["rgba"], 4)
+        cpos = pos  # where the geom's mass sits, in the body frame
+        if t == GEOM_MESH:  # density x volume at the volume centroid
+            vol = meshes[mi].volume
+            cpos = pos + _mesh._quat_mat(quat) @ meshes[mi].centroid
+        else:
+            vol = _geom_volume(t, size)
         if "mass" in a:
             mass = float(a["mass"])
         else:
-            mass = float(a.get("density", 1000.0)) * _geom_volume(t, size)
+            mass = float(a.get("density", 1000.0)) * vol
         G["names"].append(a.get("name", ""))
         for k, v in (("type", t), ("body", bid), ("group", int(a.get("group", 0))), ("size", size), ("pos", pos), ("quat", quat),
-                     ("rgba", rgba), ("checker", checker), ("rgb2", rgb2), ("rep", rep), ("uni", uni), ("mass", mass)):
+                     ("rgba", rgba), ("checker", checker), ("rgb2", rgb2), ("rep", rep), ("uni", uni), ("mass", mass),
+                     ("mesh", mi), ("cpos", cpos)):
             G[k].append(v)
     if n_skipped:
-        log(f"compile_render_scene: {n_skipped} mesh / height-field geoms are not drawn")
+        log(f"compile_render_scene: {n_skipped} mesh / height-field geoms are not drawn"
+            + (f" ({'; '.join(why_skipped[:3])}{' ...' if len(why_skipped) > 3 else ''})" if why_skipped else ""))
 
     S = dict(names=[], type=[], body=[], group=[], size=[], pos=[], quat=[], rgba=[])
     for a, bid, _ in sites:
@@ -711,7 +778,7 @@ def compile_render_scene(xml: str | Path, *, scale: float = 1.0, from_string: bo
     # body masses / local centres of mass: an explicit <inertial> wins, else the geoms' (density x volume, or mass)
     body_mass = np.zeros(nbody)
     body_ipos = np.zeros((nbody, 3))
-    gb, gm, gp = np.asarray(G["body"], np.int64), np.asarray(G["mass"], np.float64), np.asarray(G["pos"], np.float64).reshape(-1, 3)
+    gb, gm, gp = np.asarray(G["body"], np.int64), np.asarray(G["mass"], np.float64), np.asarray(G["cpos"], np.float64).reshape(-1, 3)
     for b in range(nbody):
         if b in inertials:
             body_mass[b] = float(inertials[b].get("mass", 0.0))
@@ -740,4 +807,5 @@ def compile_render_scene(xml: str | Path, *, scale: float = 1.0, from_string: bo
         light_dir=arr(L["dir"], (nl, 3)), light_diffuse=arr(L["diffuse"], (nl, 3)), light_directional=arr(L["directional"], nl, bool),
         head_ambient=np.asarray(head_amb, np.float64), head_diffuse=np.asarray(head_diff, np.float64), head_active=bool(active),
         azimuth=az, elevation=el, fovy=fovy, alpha=alpha, body_mass=body_mass, body_ipos=body_ipos, n_skipped=n_skipped,
+        geom_mesh=arr(G["mesh"], ng, np.int32), meshes=meshes,
     )

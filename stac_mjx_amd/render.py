@@ -1,7 +1,7 @@
 """GPU renderer of fitted poses: ``Renderer`` (FK + cameras + the ``stac_render`` kernel) behind ``Stac.render``.
 
 What a frame shows is the rule of DESIGN.md "Rendering" (modelled on ``stac_mjx/stac.py:505-658``): model geoms of groups 0
-and 2, model sites of groups 0-2, one sphere per keypoint and per fitted marker, and optionally a red segment from each
+and 2 (primitives and triangle meshes), model sites of groups 0-2, one sphere per keypoint and per fitted marker, and optionally a red segment from each
 keypoint to its marker; Lambert shading from the headlight and the model's lights; model geoms of moving bodies drawn
 see-through with opacity ``<visual><map alpha>``.  The pixels come from ``stac_render`` (csrc/stac_render.hip); this module
 only prepares its inputs on the device.
@@ -41,20 +41,30 @@ class StacRenderTables(C.Structure):
     ]  # fmt: skip
 
 
+class StacRenderMeshes(C.Structure):
+    _fields_ = [
+        ("nmesh", C.c_int32), ("node_offset", _i32p), ("tri_offset", _i32p), ("node_box", _f32p), ("node_link", _i32p),
+        ("tri_vertex", _f32p), ("prim_mesh", _i32p),
+    ]  # fmt: skip
+
+
 def bind(lib):
     """Argument types of the render entry points (idempotent)."""
     vp = C.c_void_p
     lib.stac_render_scene_create.restype = vp
     lib.stac_render_scene_create.argtypes = [vp, C.POINTER(StacRenderTables)]
+    lib.stac_render_scene_create_with_meshes.restype = vp
+    lib.stac_render_scene_create_with_meshes.argtypes = [vp, C.POINTER(StacRenderTables), C.POINTER(StacRenderMeshes)]
     lib.stac_render_scene_destroy.argtypes = [vp]
     lib.stac_render.argtypes = [vp, C.c_int32, vp, vp, vp, vp, C.c_int32, vp, C.c_float, C.c_int32, C.c_int32, vp, vp, vp, vp]
     lib.stac_render.restype = C.c_int32
 
 
-def render_tables(scene: RenderScene, kp_rgba, marker_size: float) -> dict:
-    """Host arrays of ``stac_render_tables`` (float32 / int32) and the static primitives' names: the geoms of GEOM_GROUPS,
-    then the sites of SITE_GROUPS, in document order."""
-    g = np.flatnonzero(np.isin(scene.geom_group, GEOM_GROUPS))
+def render_tables(scene: RenderScene, kp_rgba, marker_size: float, geom_groups=None) -> dict:
+    """Host arrays of ``stac_render_tables`` (float32 / int32) and the static primitives' names: the geoms of ``geom_groups``
+    (None: GEOM_GROUPS), mesh geoms among them, then the sites of SITE_GROUPS, in document order.  With mesh geoms the dict
+    has a ``meshes`` entry: the arrays of ``stac_render_meshes`` (only the meshes that a drawn geom uses)."""
+    g = np.flatnonzero(np.isin(scene.geom_group, GEOM_GROUPS if geom_groups is None else tuple(int(v) for v in geom_groups)))
     s = np.flatnonzero(np.isin(scene.site_group, SITE_GROUPS))
     f32 = lambda a, shape: np.ascontiguousarray(np.asarray(a, np.float64).reshape(shape), dtype=np.float32)
     P = len(g) + len(s)
@@ -65,7 +75,16 @@ def render_tables(scene: RenderScene, kp_rgba, marker_size: float) -> dict:
     flags[: len(g)] |= np.where(scene.geom_texuniform[g] & scene.geom_checker[g], FLAG_TEXUNIFORM, 0).astype(np.int32)
     kp_rgba = f32(kp_rgba, (-1, 4))
     head_on = 1.0 if scene.head_active else 0.0
-    return dict(
+    meshes = None
+    gm = scene.geom_mesh[g] if scene.geom_mesh is not None else np.full(len(g), -1, np.int32)
+    if (gm >= 0).any():
+        from .mesh import pack_meshes
+
+        used = sorted(set(int(m) for m in gm if m >= 0))
+        remap = {m: k for k, m in enumerate(used)}
+        meshes = pack_meshes([scene.meshes[m] for m in used])
+        meshes["prim_mesh"] = np.asarray([remap.get(int(m), -1) for m in gm] + [-1] * len(s), np.int32)
+    out = dict(
         prim_type=np.ascontiguousarray(np.concatenate([scene.geom_type[g], scene.site_type[s]]), dtype=np.int32),
         prim_body=np.ascontiguousarray(np.concatenate([scene.geom_body[g], scene.site_body[s]]), dtype=np.int32),
         prim_flags=flags,
@@ -83,6 +102,9 @@ def render_tables(scene: RenderScene, kp_rgba, marker_size: float) -> dict:
         alpha=np.float32(scene.alpha), background=f32(BACKGROUND, 3),
         names=[scene.geom_names[i] for i in g] + [scene.site_names[i] for i in s],
     )
+    if meshes is not None:
+        out["meshes"] = meshes
+    return out
 
 
 def _ctables(t: dict):
@@ -100,6 +122,18 @@ def _ctables(t: dict):
     return ct
 
 
+def _cmeshes(m: dict):
+    cm = StacRenderMeshes()
+    cm.nmesh = len(m["node_offset"]) - 1
+    for k in ("node_offset", "tri_offset", "node_link", "prim_mesh"):
+        m[k] = np.ascontiguousarray(m[k], dtype=np.int32)
+        setattr(cm, k, m[k].ctypes.data_as(_i32p))
+    for k in ("node_box", "tri_vertex"):
+        m[k] = np.ascontiguousarray(m[k], dtype=np.float32)
+        setattr(cm, k, m[k].ctypes.data_as(_f32p))
+    return cm
+
+
 class RenderSceneHandle:
     """A ``stac_render_scene`` on the engine's device (uploaded once; no host upload per call)."""
 
@@ -108,7 +142,11 @@ class RenderSceneHandle:
         bind(self.lib)
         self.tables = tables
         self.P, self.K = len(tables["prim_type"]), len(tables["kp_rgba"])
-        self._h = self.lib.stac_render_scene_create(C.c_void_p(engine._h), C.byref(_ctables(tables)))
+        if tables.get("meshes") is not None:  # triangles and hierarchies go to device memory once, here
+            self._h = self.lib.stac_render_scene_create_with_meshes(C.c_void_p(engine._h), C.byref(_ctables(tables)),
+                                                                    C.byref(_cmeshes(tables["meshes"])))
+        else:
+            self._h = self.lib.stac_render_scene_create(C.c_void_p(engine._h), C.byref(_ctables(tables)))
         if not self._h:
             self.code = int(self.lib.stac_last_error_code())
             raise StacHipError(f"stac_render_scene_create failed: libstac_hip error {self.code}: {engine._err()}")
@@ -216,14 +254,16 @@ class Renderer:
     """Renders poses of the engine's model with the scene's primitives (see the module docstring).
 
     ``kp_names`` / ``kp_body`` name the keypoints and the bodies their markers sit on (``KEYPOINT_MODEL_PAIRS``);
-    ``kp_rgba`` [K, 4] colours the keypoints (``KEYPOINT_COLOR_PAIRS``); ``marker_size`` is ``MARKER_SIZE``."""
+    ``kp_rgba`` [K, 4] colours the keypoints (``KEYPOINT_COLOR_PAIRS``); ``marker_size`` is ``MARKER_SIZE``;
+    ``geom_groups``: the geom groups to draw (None = GEOM_GROUPS, the reference's rule; ``(0, 1, 2)`` shows the fruit fly's
+    body meshes, which sit in group 1)."""
 
     def __init__(self, engine: Engine, scene: RenderScene, kp_names, kp_body, kp_rgba, marker_size=0.005,
-                 memory_budget=1 << 30):
+                 memory_budget=1 << 30, *, geom_groups=None):
         if scene.nbody != engine.nbody:
             raise ValueError(f"scene has {scene.nbody} bodies, the engine's model {engine.nbody}")
         self.engine, self.scene = engine, scene
-        self.tables = render_tables(scene, kp_rgba, marker_size)
+        self.tables = render_tables(scene, kp_rgba, marker_size, geom_groups)
         self.K = len(self.tables["kp_rgba"])
         if self.K != engine.K:
             raise ValueError(f"{self.K} keypoint colours for a model with {engine.K} markers")

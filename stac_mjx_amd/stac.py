@@ -223,7 +223,11 @@ class Stac:
                         kp_names=self._kp_names)
 
     # -- render (stac.py:505-658) -------------------------------------------------------------------------------
-    def _get_renderer(self):
+    def _get_renderer(self, geom_groups=None):
+        key = None if geom_groups is None else tuple(int(g) for g in geom_groups)
+        if self._renderer is not None and getattr(self, "_renderer_groups", None) != key:
+            self._renderer.close()
+            self._renderer = None
         if self._renderer is None:
             if self._xml_path is None:
                 raise ValueError("Stac.render needs the model's MJCF file: this Stac was built from `setup=` without an xml_path")
@@ -236,13 +240,16 @@ class Stac:
             rgba = [[float(c) for c in v.split()] if isinstance(v, str) else [float(c) for c in v] for v in (colours[k] for k in pairs)]
             scene = compile_render_scene(self._xml_path, scale=float(cfgm.SCALE_FACTOR), log=self._log)
             self._renderer = Renderer(self.engine, scene, list(pairs), list(pairs.values()), rgba,
-                                      marker_size=float(cfgm.get("MARKER_SIZE", 0.005) if hasattr(cfgm, "get") else cfgm.MARKER_SIZE))
+                                      marker_size=float(cfgm.get("MARKER_SIZE", 0.005) if hasattr(cfgm, "get") else cfgm.MARKER_SIZE),
+                                      geom_groups=key)
+            self._renderer_groups = key
         return self._renderer
 
     def render(self, qposes, kp_data, offsets, n_frames, save_path, start_frame=0, camera=0, height=1200, width=1920,
-               show_marker_error=False):
+               show_marker_error=False, *, geom_groups=None):
         """Render fitted results as a video (the reference's signature and checks, ``stac.py:569-658``); returns the list of
-        H x W x 3 uint8 frames.  ``camera``: index, name, or -1 (free camera).  The engine's state is left as it was."""
+        H x W x 3 uint8 frames.  ``camera``: index, name, or -1 (free camera).  ``geom_groups``: the geom groups to draw
+        (None = the reference's rule, groups 0 and 2).  The engine's state is left as it was."""
         qposes, kp_data = np.asarray(qposes), np.asarray(kp_data)
         if qposes.shape[0] != kp_data.shape[0]:
             raise ValueError(
@@ -253,7 +260,7 @@ class Stac:
         if start_frame + n_frames > kp_data.shape[0]:
             raise ValueError(
                 f"start_frame + n_frames ({start_frame} + {n_frames}) must be less than the length of given qposes and kp_data ({kp_data.shape[0]})")
-        r = self._get_renderer()
+        r = self._get_renderer(geom_groups)
         r.camera_index(camera)
         from .video import write_video
 

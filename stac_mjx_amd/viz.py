@@ -8,8 +8,9 @@ from . import io
 
 
 def viz_stac(data_path, n_frames: int, save_path, start_frame: int = 0, camera=0, height: int = 1200, width: int = 1920,
-             base_path: Path | None = None, show_marker_error: bool = False):
-    """Render forward kinematics from STAC output data; returns (config, list of rendered RGB frames)."""
+             base_path: Path | None = None, show_marker_error: bool = False, *, geom_groups=None):
+    """Render forward kinematics from STAC output data; returns (config, list of rendered RGB frames).  ``geom_groups``: the
+    geom groups to draw (None = the reference's rule, groups 0 and 2)."""
     from .stac import Stac
 
     cfg, d = io.load_stac_data(data_path)
@@ -17,5 +18,6 @@ def viz_stac(data_path, n_frames: int, save_path, start_frame: int = 0, camera=0
         base_path = Path.cwd()
     xml_path = Path(base_path) / cfg.model.MJCF_PATH
     stac = Stac(xml_path, cfg, d.kp_names)
+    kw = {} if geom_groups is None else {"geom_groups": geom_groups}
     return cfg, stac.render(d.qpos, d.kp_data, d.offsets, n_frames, save_path, start_frame, camera, height, width,
-                            show_marker_error)
+                            show_marker_error, **kw)

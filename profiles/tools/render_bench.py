@@ -16,7 +16,7 @@ Mesh geoms (profiles/render/render_mesh_bench.json):
 
 * ``mesh``: the rodent's stored fit with icospheres attached to its bodies (procedural, so the scene exists wherever the
   script runs): 100 instances of 4 shared meshes, 214 400 triangles in all, about the reference's mouse; kernel frames/s at
-  1920 x 1200 from device events over at least 1 s, and the f32 restatement with meshes (tests/tools/render_mesh_ref.c);
+  1920 x 1200 from device events over at least 1 s, and the f32 restatement (the same file) on the mesh scene;
 * ``hierarchy``: one 20 480-triangle icosphere filling the frame, with the hierarchy and with the developer switch
   STAC_RENDER_MESH_SINGLE_LEAF=1 (read at scene creation): equal pictures, and the time of one launch each.
 """
@@ -236,9 +236,9 @@ def mesh_section(args, r, fs, scene, cfg, dv, W, H):
         fps = n * N / elapsed
         out["kernel"][f"{camera}_plain"] = {"frames_per_s": fps, "ms_per_frame": 1e3 / fps, "launches": n, "window_s": elapsed}
         print("mesh", camera, json.dumps(out["kernel"][f"{camera}_plain"]), flush=True)
-    from build_render_mesh_ref import RenderRef as MeshRef
+    from build_render_ref import RenderRef
 
-    ref = MeshRef("float")
+    ref = RenderRef("float")
     nc = 1 if args.quick else 2
     t0 = time.perf_counter()
     ref.render(rm.tables, t.nbody, xpos[:nc].cpu().numpy(), xquat[:nc].cpu().numpy(), kp[:nc], markers[:nc].cpu().numpy(), False,

@@ -11,7 +11,7 @@
 // is the kernel of mesh-free scenes, render_kernel<true> adds the mesh records, the culled list of mesh instances and the
 // loop over it, after the loop over the quadrics and boxes so that the lanes of a wavefront walk the same tree together.
 // The arithmetic is written operation by operation (no FMA: -ffp-contract=off) so that tests/tools/render_ref.c,
-// built with float, reproduces every output bit for bit.
+// the one CPU restatement of both kernels, built with float, reproduces every output bit for bit.
 #include <hip/hip_runtime.h>
 
 #include <math.h>

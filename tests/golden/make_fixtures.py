@@ -34,6 +34,12 @@ Fixtures are DATA only (inputs / expected outputs / compiled model tables), no r
                             frame of tests/data/test_synth_1_frames.nwb through load_data semantics, float32 [1, 3] (read
                             under /opt/conda/bin/python3.9 like the mouse mocap).  Written deterministically (fixed zip
                             timestamps), so that `--only synth` reproduces them byte for byte.
+  render_ref_digests.json   SHA-256 of rgb, seg, depth and amb of the mesh-free render scenes of
+                            tests/render_cases.py::pinned_scenes, float and double build of the CPU restatement of the render
+                            kernel (`--only render_digests`; needs no reference checkout).  The committed file was made at
+                            commit 045d64a from the mesh-free tests/tools/render_ref.c of that commit, before it and its
+                            mesh-aware copy became one file (the copy gave the same bytes on every scene).  It is
+                            regenerated only when the frame rule is changed on purpose.
 """
 
 from __future__ import annotations
@@ -109,12 +115,38 @@ def synth_fixtures(ref: Path):
     subprocess.run(["/opt/conda/bin/python3.9", "-c", code, str(ROOT), str(ref), str(HERE / "synth_kp_1.npy")], check=True)
 
 
+RENDER_DIGESTS_MADE_BY = ("tests/golden/make_fixtures.py --only render_digests at commit 045d64a, from that commit's mesh-free "
+                          "tests/tools/render_ref.c; regenerated only when the frame rule is changed on purpose")
+
+
+def render_digests():
+    """The pictures of the mesh-free render scenes, by digest (tests/test_render_host.py compares them)."""
+    import tarfile
+    import tempfile
+
+    sys.path.insert(0, str(ROOT / "tests"))
+    import render_cases
+
+    cfg = json.load(open(HERE / "rodent_model_cfg.json"))
+    with tempfile.TemporaryDirectory() as tmp, tarfile.open(HERE / "reference_fixtures.tar.xz") as tf:
+        tf.extractall(tmp, filter="data")
+        digests = render_cases.picture_digests(render_cases.rodent_scene(Path(tmp), cfg), cfg)
+    with open(HERE / "render_ref_digests.json", "w") as fh:
+        json.dump({"_made_by": RENDER_DIGESTS_MADE_BY, **digests}, fh, indent=0, sort_keys=True)
+        fh.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reference", default="/root/reference")
-    ap.add_argument("--only", choices=("all", "synth"), default="all",
-                    help="synth: write only the three synth fixtures (the others carry zip timestamps)")
+    ap.add_argument("--only", choices=("all", "synth", "render_digests"), default="all",
+                    help="synth: write only the three synth fixtures (the others carry zip timestamps); "
+                         "render_digests: write only render_ref_digests.json (not part of `all`)")
     args = ap.parse_args()
+    if args.only == "render_digests":
+        render_digests()
+        print("render digests written to", HERE)
+        return
     ref = Path(args.reference)
     if args.only == "synth":
         synth_fixtures(ref)

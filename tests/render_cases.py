@@ -1,15 +1,25 @@
-"""Scenes of the render tests (tests/test_render_host.py, tests/test_gpu_render.py): the rodent of the reference's fixtures
-with the stored demo_viz fit, the synth model, and seeded random scenes of every primitive type."""
+"""Scenes and shared helpers of the render tests (tests/test_render_host.py, tests/test_gpu_render.py and their mesh
+siblings): the rodent of the reference's fixtures with the stored demo_viz fit, the synth model, seeded random scenes of
+every primitive type, the scenes whose pictures are pinned, the checker (tests/tools/build_render_ref.py) and the
+comparisons against it."""
 
 from __future__ import annotations
 
+import hashlib
 import math
+import sys
 
 import numpy as np
+import torch
 
-from conftest import GOLDEN
+from conftest import GOLDEN, ROOT
+
+sys.path.insert(0, str(ROOT / "tests" / "tools"))
+from build_render_ref import RenderRef  # noqa: E402,F401
 
 GEOM_TYPES = (0, 2, 3, 4, 5, 6)  # plane, sphere, capsule, ellipsoid, cylinder, box
+AMB_CAP = 0.01  # at most 1 % of an image's pixels may be flagged ambiguous by the double build (a condition, not a tolerance)
+SENTINEL = 0xAB
 
 
 def kp_rgba(cfg) -> list:
@@ -130,3 +140,100 @@ def random_scene(seed, nbody, K, n_static=60, n_frames=2, layered=True, near=Tru
 def load_demo_viz():
     with np.load(GOLDEN / "demo_viz_golden.npz") as d:
         return {k: d[k] for k in d.files}
+
+
+def rodent_render_args(scene, cfg, camera, idx=(0, 25, 49), W=480, H=300):
+    """The argument list of ``RenderRef.render`` for the stored fit's frames ``idx`` of the rodent through ``camera``,
+    error segments on."""
+    from stac_mjx_amd.mjcf import ModelTables
+    from stac_mjx_amd.render import camera_frames, render_tables
+
+    tables = ModelTables.load(GOLDEN / "rodent_tables_legacy.npz")
+    xpos, xquat, mk, kp = rodent_frames(tables, load_demo_viz(), list(idx))
+    x0, q0 = qpos0_pose(tables)
+    cam, tanh = camera_frames(scene, tables.body_parentid, camera, torch.tensor(xpos), torch.tensor(xquat), x0, q0)
+    t = render_tables(scene, kp_rgba(cfg), float(cfg["MARKER_SIZE"]))
+    return t, tables.nbody, xpos, xquat, kp, mk, True, cam.float().numpy(), tanh, W, H
+
+
+def pinned_scenes(rodent, cfg):
+    """(name, RenderRef.render arguments) of the mesh-free scenes whose pictures tests/golden/render_ref_digests.json pins."""
+    for seed in (0, 1, 2, 3):
+        t, xpos, xquat, kp, markers, cams, tanh = random_scene(seed, 67, 23, n_frames=2)
+        for W, H in ((160, 120), (97, 61)):
+            for show in (False, True):
+                yield f"random{seed}/{W}x{H}/show_error={int(show)}", (t, 67, xpos, xquat, kp, markers, show, cams, tanh, W, H)
+    for camera in (0, 2, 4, 5, -1):
+        yield f"rodent_camera{camera}/480x300/show_error=1", rodent_render_args(rodent, cfg, camera)
+
+
+def picture_digests(rodent, cfg) -> dict:
+    """SHA-256 of the raw bytes of rgb, seg, depth and amb of every pinned scene, float and double build."""
+    out = {}
+    for real in ("float", "double"):
+        ref = RenderRef(real)
+        for name, args in pinned_scenes(rodent, cfg):
+            for what, a in zip(("rgb", "seg", "depth", "amb"), ref.render(*args)):
+                out[f"{name}/{real}/{what}"] = hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+    return out
+
+
+def compare_builds(refs, args):
+    """The f32 build against the f64 build on every pixel the f64 build does not flag as ambiguous.
+
+    Ambiguous pixels.  Each decision of a pixel is a sign test of a computed quantity whose float32 evaluation carries a
+    relative error of a few units of 2^-24 of the inputs it is formed from.  For a quadric (sphere, ellipsoid after its
+    map to the unit sphere, the side of a capsule or cylinder), the test is h2 = r^2 - |p|^2 >= 0 with p the closest point
+    of the ray to the axis or centre: p is formed from o - c, so its error is about eps |o - c|, and that of h2 about
+    2 r eps |o - c|.  The margin |h2| / r^2 is therefore compared with 64 x 2^-24 times the condition number |o - c| / r.
+    The linear tests (slab overlap and face choice of a box, |z| <= half length, a plane's extent, the checker edges) use
+    the same factor on their absolute margin against |o - c|.  Depth ties (the two nearest opaque hits, the order of
+    transparent hits and their order against the opaque one) use the relative gap.  64 leaves room for the dozen
+    roundings on the path of each quantity.
+
+    Bounds on the other pixels.  seg is exact.  RGB may differ by one quantisation step, where a colour lies within float32
+    noise of a rounding boundary.  Depth: the entry distance t = tca - sqrt(h2 / a) of the closest-approach form has an
+    absolute error of a few ulp of |o - c|; relative to t this stays near 1e-7 where t is comparable to |o - c| and grows
+    only for primitives that reach close to the camera, so 1e-5 is the bound (measured: at most 5e-6 on the random scenes
+    with primitives crossing the camera's near side, below 1.2e-6 on the rodent)."""
+    r32, r64 = refs
+    a = r32.render(*args)
+    b = r64.render(*args)
+    amb = b[3].astype(bool)
+    frac = amb.mean(axis=(1, 2))
+    print("ambiguous fraction per image:", frac)
+    assert (frac <= AMB_CAP).all(), frac
+    ok = ~amb
+    np.testing.assert_array_equal(a[1][ok], b[1][ok])
+    assert np.abs(a[0].astype(int) - b[0].astype(int))[ok].max() <= 1
+    fin = ok & np.isfinite(b[2])
+    assert (np.isinf(a[2]) == np.isinf(b[2]))[ok].all()
+    rel = np.abs(a[2][fin].astype(np.float64) - b[2][fin]) / np.abs(b[2][fin])
+    print("max relative depth difference:", rel.max() if rel.size else 0.0)
+    assert rel.size == 0 or rel.max() <= 1e-5
+    return a, b
+
+
+def _dev(a, dtype=torch.float32):
+    return torch.as_tensor(np.ascontiguousarray(a)).to(device="cuda:0", dtype=dtype) if a is not None else None
+
+
+def gpu_render(handle, xpos, xquat, kp, markers, show_error, cam, tanh, W, H, want_seg=True, want_depth=True):
+    """stac_render on outputs prefilled with a sentinel byte; returns numpy rgb, seg, depth."""
+    N = cam.shape[0]
+    rgb = torch.full((N, H, W, 3), SENTINEL, dtype=torch.uint8, device="cuda:0")
+    seg = torch.full((N * H * W * 4,), SENTINEL, dtype=torch.uint8, device="cuda:0").view(torch.int32).view(N, H, W) if want_seg else None
+    depth = torch.full((N * H * W * 4,), SENTINEL, dtype=torch.uint8, device="cuda:0").view(torch.float32).view(N, H, W) if want_depth else None
+    handle.render(_dev(xpos), _dev(xquat), _dev(kp), _dev(markers), show_error, _dev(cam), tanh, W, H, rgb, seg, depth)
+    torch.cuda.synchronize()
+    return rgb.cpu().numpy(), seg.cpu().numpy() if want_seg else None, depth.cpu().numpy() if want_depth else None
+
+
+def assert_same(got, want, what=""):
+    for name, g, w in zip(("rgb", "seg", "depth"), got, want):
+        if g is None:
+            continue
+        if name == "depth":
+            g, w = g.view(np.uint32), w.view(np.uint32)  # bit for bit, +inf included
+        bad = np.argwhere(g != w)
+        assert bad.size == 0, f"{what} {name}: {len(bad)} values differ, first at {bad[:3].tolist()}: {g[tuple(bad[0])]} vs {w[tuple(bad[0])]}"

@@ -211,6 +211,28 @@ def static_scene(meshes, inst, cams, nbody=1, K=1, extra=None):
     return t, xpos, xquat, kp, kp.copy(), np.stack(cams).astype(np.float32), math.tan(math.radians(45) / 2)
 
 
+def pad_bodies(scene, nbody):
+    """A scene made for one body, for an engine with ``nbody`` bodies (the others at the origin, unused)."""
+    t, xpos, xquat, kp, markers, cams, tanh = scene
+    N = xpos.shape[0]
+    xp = np.zeros((N, nbody, 3), np.float32)
+    xq = np.zeros((N, nbody, 4), np.float32)
+    xq[..., 0] = 1
+    xp[:, : xpos.shape[1]], xq[:, : xquat.shape[1]] = xpos, xquat
+    return t, xp, xq, kp, markers, cams, tanh
+
+
+def big_sphere_scene(eng, subdiv):
+    from stac_mjx_amd.mesh import make_mesh
+
+    m = make_mesh("big", icosphere(subdiv, 0.5))
+    cams = [look_at([1.3, 0.2, 0.9], [0, 0, 0.6]), look_at([0.0, 0.0, 0.6], [1.0, 0.2, 0.7])]  # outside, filling the frame; inside
+    sc = static_scene([m], [(0, [0, 0, 0.6], [1, 0, 0, 0], [0.7, 0.7, 0.9, 1], 0)], cams, K=eng.K)
+    t = dict(sc[0])
+    t["kp_rgba"] = np.ones((eng.K, 4), np.float32)
+    return pad_bodies((t,) + sc[1:], eng.nbody)
+
+
 def awkward_scene(subdiv=3):
     """Grazing rays, a camera inside a mesh, an open sheet seen from both sides, coincident faces of two instances (opaque
     and see-through: ties by id) and zero-area triangles."""

@@ -4,20 +4,15 @@ of every primitive type, NaN keypoints, the primitive cap, chunked and very long
 FK consistency of the pictures, Stac.render leaving the fit state alone, and viz_stac end to end."""
 
 import math
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import GOLDEN, ROOT
-from render_cases import kp_rgba, random_scene, rodent_scene
-
-sys.path.insert(0, str(ROOT / "tests" / "tools"))
-from build_render_ref import RenderRef  # noqa: E402
+from conftest import GOLDEN
+from render_cases import RenderRef, assert_same, gpu_render, kp_rgba, random_scene, rodent_scene
 
 pytestmark = pytest.mark.gpu
-SENTINEL = 0xAB
 
 
 @pytest.fixture(scope="module")
@@ -36,31 +31,6 @@ def rodent(reference_dir, rodent_cfg, rodent_setup_legacy):
     pairs = rodent_cfg["KEYPOINT_MODEL_PAIRS"]
     r = Renderer(eng, scene, list(pairs), list(pairs.values()), kp_rgba(rodent_cfg), float(rodent_cfg["MARKER_SIZE"]))
     return eng, scene, r, fs.tables
-
-
-def _dev(a, dtype=torch.float32):
-    return torch.as_tensor(np.ascontiguousarray(a)).to(device="cuda:0", dtype=dtype) if a is not None else None
-
-
-def gpu_render(handle, xpos, xquat, kp, markers, show_error, cam, tanh, W, H, want_seg=True, want_depth=True):
-    """stac_render on outputs prefilled with a sentinel byte; returns numpy rgb, seg, depth."""
-    N = cam.shape[0]
-    rgb = torch.full((N, H, W, 3), SENTINEL, dtype=torch.uint8, device="cuda:0")
-    seg = torch.full((N * H * W * 4,), SENTINEL, dtype=torch.uint8, device="cuda:0").view(torch.int32).view(N, H, W) if want_seg else None
-    depth = torch.full((N * H * W * 4,), SENTINEL, dtype=torch.uint8, device="cuda:0").view(torch.float32).view(N, H, W) if want_depth else None
-    handle.render(_dev(xpos), _dev(xquat), _dev(kp), _dev(markers), show_error, _dev(cam), tanh, W, H, rgb, seg, depth)
-    torch.cuda.synchronize()
-    return rgb.cpu().numpy(), seg.cpu().numpy() if want_seg else None, depth.cpu().numpy() if want_depth else None
-
-
-def assert_same(got, want, what=""):
-    for name, g, w in zip(("rgb", "seg", "depth"), got, want):
-        if g is None:
-            continue
-        if name == "depth":
-            g, w = g.view(np.uint32), w.view(np.uint32)  # bit for bit, +inf included
-        bad = np.argwhere(g != w)
-        assert bad.size == 0, f"{what} {name}: {len(bad)} values differ, first at {bad[:3].tolist()}: {g[tuple(bad[0])]} vs {w[tuple(bad[0])]}"
 
 
 def check_renderer(ref32, r, tables, qpos, kp, offsets, camera, W, H, show):

@@ -1,5 +1,5 @@
 """Mesh geoms in the render kernel (csrc/stac_render.hip, render_kernel<true>) against the float build of
-tests/tools/render_mesh_ref.c: rgb, seg and depth equal bit for bit, on random scenes that mix every primitive type with
+tests/tools/render_ref.c: rgb, seg and depth equal bit for bit, on random scenes that mix every primitive type with
 mesh instances, the awkward cases, C. elegans with a few of its own mesh files, the primitive cap, every refusal of
 stac_render_scene_create_with_meshes, one mesh of 327 680 triangles in full HD, the single-leaf developer switch, and
 Stac.render / viz_stac end to end on a model with mesh geoms."""
@@ -15,20 +15,16 @@ import pytest
 import torch
 
 from conftest import GOLDEN, ROOT
-from render_cases import kp_rgba, look_at, random_scene
-from render_mesh_cases import (awkward_scene, icosphere, library, random_mesh_scene, add_meshes, static_scene, torus,
-                               write_obj, write_stl_binary)
-
-sys.path.insert(0, str(ROOT / "tests" / "tools"))
-from build_render_mesh_ref import RenderRef as MeshRef  # noqa: E402
-from test_gpu_render import assert_same, gpu_render  # noqa: E402
+from render_cases import RenderRef, assert_same, gpu_render, random_scene
+from render_mesh_cases import (add_meshes, awkward_scene, icosphere, library, pad_bodies, random_mesh_scene, torus, write_obj,
+                               write_stl_binary)
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def ref32():
-    return MeshRef("float")
+    return RenderRef("float")
 
 
 @pytest.fixture(scope="module")
@@ -55,17 +51,6 @@ def check_tables(ref32, eng, scene, sizes, shows=(False, True), what=""):
     return out
 
 
-def _pad_bodies(scene, nbody):
-    """A scene made for one body, for an engine with ``nbody`` bodies (the others at the origin, unused)."""
-    t, xpos, xquat, kp, markers, cams, tanh = scene
-    N = xpos.shape[0]
-    xp = np.zeros((N, nbody, 3), np.float32)
-    xq = np.zeros((N, nbody, 4), np.float32)
-    xq[..., 0] = 1
-    xp[:, : xpos.shape[1]], xq[:, : xquat.shape[1]] = xpos, xquat
-    return t, xp, xq, kp, markers, cams, tanh
-
-
 @pytest.mark.parametrize("seed,n_mesh,subdivs", [(0, 1, (0,)), (1, 12, (0, 1, 2, 3)), (2, 40, (0, 2, 4, 5)), (3, 25, (1, 3, 5))])
 def test_random_scenes_with_meshes(ref32, eng, seed, n_mesh, subdivs):
     sc = random_mesh_scene(seed, eng.nbody, eng.K, n_mesh=n_mesh, subdivs=subdivs, n_frames=3)
@@ -79,7 +64,7 @@ def test_awkward_cases(ref32, eng):
     t["kp_rgba"] = np.ones((eng.K, 4), np.float32)
     N = sc[1].shape[0]
     kp = np.full((N, eng.K, 3), np.nan, np.float32)
-    sc = _pad_bodies((t, sc[1], sc[2], kp, kp.copy(), sc[5], sc[6]), eng.nbody)
+    sc = pad_bodies((t, sc[1], sc[2], kp, kp.copy(), sc[5], sc[6]), eng.nbody)
     got = check_tables(ref32, eng, sc, ((160, 120), (33, 47)), shows=(False,), what="awkward")
     assert (got[1][0] >= 0).all()  # the camera inside the shell sees its inside everywhere
 
@@ -204,17 +189,6 @@ def test_refusals(eng):
     assert "error -3" in str(ei.value)
 
 
-def _big_sphere_scene(eng, subdiv):
-    from stac_mjx_amd.mesh import make_mesh
-
-    m = make_mesh("big", icosphere(subdiv, 0.5))
-    cams = [look_at([1.3, 0.2, 0.9], [0, 0, 0.6]), look_at([0.0, 0.0, 0.6], [1.0, 0.2, 0.7])]  # outside, filling the frame; inside
-    sc = static_scene([m], [(0, [0, 0, 0.6], [1, 0, 0, 0], [0.7, 0.7, 0.9, 1], 0)], cams, K=eng.K)
-    t = dict(sc[0])
-    t["kp_rgba"] = np.ones((eng.K, 4), np.float32)
-    return _pad_bodies((t,) + sc[1:], eng.nbody)
-
-
 def test_one_large_mesh_in_full_hd_through_the_renderer(ref32, rodent_setup_legacy, rodent_cfg, tmp_path):
     """Icosphere at subdivision 7 (327 680 triangles) on the rodent's torso, 1920 x 1200, through Renderer.render."""
     from stac_mjx_amd.engine import Engine
@@ -258,12 +232,12 @@ from stac_mjx_amd.engine import Engine
 from stac_mjx_amd.fit_model import finish_fit_setup
 from stac_mjx_amd.mjcf import ModelTables
 from stac_mjx_amd.render import RenderSceneHandle
-import test_gpu_render_mesh as T
-from test_gpu_render import gpu_render
+from render_cases import gpu_render
+from render_mesh_cases import big_sphere_scene
 cfg = json.load(open({golden!r} + "/rodent_model_cfg.json"))
 fs = finish_fit_setup(ModelTables.load({golden!r} + "/rodent_tables_legacy.npz"), cfg, list(cfg["KEYPOINT_MODEL_PAIRS"]))
 eng = Engine(fs.tables, fs.lb, fs.ub, device="cuda:0")
-t, xpos, xquat, kp, markers, cams, tanh = T._big_sphere_scene(eng, 5)
+t, xpos, xquat, kp, markers, cams, tanh = big_sphere_scene(eng, 5)
 h = RenderSceneHandle(eng, t)
 W, H = 640, 400
 got = gpu_render(h, xpos, xquat, kp, markers, False, cams, tanh, W, H)

@@ -10,13 +10,9 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import GOLDEN, ROOT
-from render_cases import kp_rgba, load_demo_viz, qpos0_pose, random_scene, rodent_frames, rodent_scene
-
-sys.path.insert(0, str(ROOT / "tests" / "tools"))
-from build_render_ref import RenderRef  # noqa: E402
-
-AMB_CAP = 0.01  # at most 1 % of an image's pixels may be flagged ambiguous by the double build (a condition, not a tolerance)
+from conftest import GOLDEN
+from render_cases import (AMB_CAP, RenderRef, compare_builds, load_demo_viz, picture_digests, qpos0_pose, random_scene,
+                          rodent_frames, rodent_render_args, rodent_scene)
 
 
 @pytest.fixture(scope="module")
@@ -172,42 +168,6 @@ def test_free_camera_rule(rodent):
 
 
 # ---- the checker: float build vs double build -------------------------------------------------------------------------------
-def compare_builds(refs, args):
-    """The f32 build against the f64 build on every pixel the f64 build does not flag as ambiguous.
-
-    Ambiguous pixels.  Each decision of a pixel is a sign test of a computed quantity whose float32 evaluation carries a
-    relative error of a few units of 2^-24 of the inputs it is formed from.  For a quadric (sphere, ellipsoid after its
-    map to the unit sphere, the side of a capsule or cylinder), the test is h2 = r^2 - |p|^2 >= 0 with p the closest point
-    of the ray to the axis or centre: p is formed from o - c, so its error is about eps |o - c|, and that of h2 about
-    2 r eps |o - c|.  The margin |h2| / r^2 is therefore compared with 64 x 2^-24 times the condition number |o - c| / r.
-    The linear tests (slab overlap and face choice of a box, |z| <= half length, a plane's extent, the checker edges) use
-    the same factor on their absolute margin against |o - c|.  Depth ties (the two nearest opaque hits, the order of
-    transparent hits and their order against the opaque one) use the relative gap.  64 leaves room for the dozen
-    roundings on the path of each quantity.
-
-    Bounds on the other pixels.  seg is exact.  RGB may differ by one quantisation step, where a colour lies within float32
-    noise of a rounding boundary.  Depth: the entry distance t = tca - sqrt(h2 / a) of the closest-approach form has an
-    absolute error of a few ulp of |o - c|; relative to t this stays near 1e-7 where t is comparable to |o - c| and grows
-    only for primitives that reach close to the camera, so 1e-5 is the bound (measured: at most 5e-6 on the random scenes
-    with primitives crossing the camera's near side, below 1.2e-6 on the rodent)."""
-    r32, r64 = refs
-    a = r32.render(*args)
-    b = r64.render(*args)
-    amb = b[3].astype(bool)
-    frac = amb.mean(axis=(1, 2))
-    print("ambiguous fraction per image:", frac)
-    assert (frac <= AMB_CAP).all(), frac
-    ok = ~amb
-    np.testing.assert_array_equal(a[1][ok], b[1][ok])
-    assert np.abs(a[0].astype(int) - b[0].astype(int))[ok].max() <= 1
-    fin = ok & np.isfinite(b[2])
-    assert (np.isinf(a[2]) == np.isinf(b[2]))[ok].all()
-    rel = np.abs(a[2][fin].astype(np.float64) - b[2][fin]) / np.abs(b[2][fin])
-    print("max relative depth difference:", rel.max() if rel.size else 0.0)
-    assert rel.size == 0 or rel.max() <= 1e-5
-    return a, b
-
-
 @pytest.mark.parametrize("seed", [0, 1, 2, 3])
 def test_f32_checker_matches_f64_on_random_scenes(refs, seed):
     t, xpos, xquat, kp, markers, cams, tanh = random_scene(seed, 67, 23, n_frames=3)
@@ -217,17 +177,26 @@ def test_f32_checker_matches_f64_on_random_scenes(refs, seed):
 
 @pytest.mark.parametrize("camera", [0, 2, 4, 5, -1])
 def test_f32_checker_matches_f64_on_rodent_frames(refs, rodent, rodent_cfg, camera):
-    from stac_mjx_amd.mjcf import ModelTables
-    from stac_mjx_amd.render import camera_frames, render_tables
-
-    tables = ModelTables.load(GOLDEN / "rodent_tables_legacy.npz")
-    dv = load_demo_viz()
-    xpos, xquat, mk, kp = rodent_frames(tables, dv, [0, 25, 49])
-    x0, q0 = qpos0_pose(tables)
-    cam, tanh = camera_frames(rodent, tables.body_parentid, camera, torch.tensor(xpos), torch.tensor(xquat), x0, q0)
-    t = render_tables(rodent, kp_rgba(rodent_cfg), float(rodent_cfg["MARKER_SIZE"]))
-    a, _ = compare_builds(refs, (t, tables.nbody, xpos, xquat, kp, mk, True, cam.float().numpy(), tanh, 480, 300))
+    a, _ = compare_builds(refs, rodent_render_args(rodent, rodent_cfg, camera))
     assert (a[1] >= 0).mean() > 0.05
+
+
+def test_pictures_of_the_mesh_free_scenes_are_pinned(rodent, rodent_cfg):
+    """rgb, seg, depth and amb of ``render_cases.pinned_scenes``, float and double build, against the SHA-256 digests of
+    tests/golden/render_ref_digests.json: the pictures of the mesh-free restatement that the mesh-free kernel was validated
+    against, before it and the mesh-aware one became one file.  The restatement uses only IEEE + - * /, sqrt, floor, fmax
+    and fmin with contraction off and nothing is reduced across threads, so the bytes do not depend on the machine.  The
+    random scenes pin the checker alone; the rodent frames also pin ``compile_render_scene`` and ``render_tables`` on the
+    rodent, on purpose: a change there is a change of the pictures.  The file is regenerated
+    (tests/golden/make_fixtures.py --only render_digests) only when the frame rule is changed on purpose."""
+    import json
+
+    want = json.load(open(GOLDEN / "render_ref_digests.json"))
+    want.pop("_made_by")
+    got = picture_digests(rodent, rodent_cfg)
+    assert sorted(got) == sorted(want)
+    bad = [k for k in want if got[k] != want[k]]
+    assert not bad, f"{len(bad)} of {len(want)} digests differ: {bad[:8]}"
 
 
 # ---- closed forms --------------------------------------------------------------------------------------------------------------

@@ -1,32 +1,24 @@
 """Mesh geoms of the renderer, everything that needs no GPU: the loaders, the scene compile (placement, scale, mass), the
-hierarchy's invariants, the CPU restatement tests/tools/render_mesh_ref.c with the hierarchy against the same with every
+hierarchy's invariants, the CPU restatement tests/tools/render_ref.c with the hierarchy against the same with every
 triangle tested (zero differing pixels), its float build against its double build (the rule of
-tests/test_render_host.py::compare_builds, same cap), closed forms, and equality with render_ref.c on mesh-free scenes."""
+render_cases.compare_builds, same cap), closed forms, and a mesh library that no primitive uses changing nothing."""
 
-import math
 import os
-import sys
 from pathlib import Path
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
-from render_cases import look_at, random_scene
-from render_mesh_cases import (awkward_scene, cube_soup, icosphere, random_mesh_scene, sheet, static_scene, torus,
-                               with_degenerates, write_obj, write_stl_ascii, write_stl_binary, _empty_tables)
-
-sys.path.insert(0, str(ROOT / "tests" / "tools"))
-from build_render_mesh_ref import RenderRef as MeshRef  # noqa: E402
-from build_render_ref import RenderRef  # noqa: E402
-from test_render_host import compare_builds  # noqa: E402
+from render_cases import RenderRef, assert_same, compare_builds, look_at, random_scene
+from render_mesh_cases import (add_meshes, awkward_scene, cube_soup, icosphere, library, random_mesh_scene, sheet, static_scene,
+                               torus, with_degenerates, write_obj, write_stl_ascii, write_stl_binary, _empty_tables)
 
 REFERENCE_MODELS = Path(os.environ.get("STAC_REFERENCE_MODELS", "/root/reference/models"))  # the reference checkout, where there is one
 
 
 @pytest.fixture(scope="module")
 def mrefs():
-    return MeshRef("float"), MeshRef("double")
+    return RenderRef("float"), RenderRef("double")
 
 
 # ---- loaders ----------------------------------------------------------------------------------------------------------------
@@ -228,19 +220,12 @@ def test_hierarchy_invariants(tri):
 
 
 # ---- the reference: hierarchy against brute force --------------------------------------------------------------------------------
-def _same_pictures(a, b, what):
-    for name, x, y in zip(("rgb", "seg", "depth"), a, b):
-        if name == "depth":
-            x, y = x.view(np.uint32), y.view(np.uint32)
-        assert (x != y).sum() == 0, f"{what}: {name} differs in {(x != y).sum()} values"
-
-
 def test_hierarchy_equals_brute_force_on_awkward_scene(mrefs):
     args = awkward_scene(3) + (160, 120)
     args = args[:5] + (False,) + args[5:]
     a = mrefs[0].render(*_args(args))
     b = mrefs[0].render(*_args(args), brute=True)
-    _same_pictures(a, b, "awkward scene")
+    assert_same(a[:3], b[:3], "awkward scene")
     seg = a[1]
     assert (seg[0] >= 0).all()  # inside the shell every ray hits something: the inside of a mesh is drawn
     assert (seg[0] == 1).any() and (seg[1] == 2).any() and (seg[2] == 2).any()  # the sheet from above and from below
@@ -260,7 +245,7 @@ def test_hierarchy_equals_brute_force_on_random_scenes(mrefs, seed):
     for W, H, show in ((160, 120, True), (97, 61, False)):
         a = mrefs[0].render(t, 20, xpos, xquat, kp, markers, show, cams, tanh, W, H)
         b = mrefs[0].render(t, 20, xpos, xquat, kp, markers, show, cams, tanh, W, H, brute=True)
-        _same_pictures(a, b, f"seed {seed} {W}x{H}")
+        assert_same(a[:3], b[:3], f"seed {seed} {W}x{H}")
         assert np.isin(a[1], np.flatnonzero(t["prim_type"] == 7)).any()  # meshes are in the picture
 
 
@@ -349,10 +334,15 @@ def test_icosphere_silhouette_lies_between_inscribed_and_circumscribed_spheres(m
 # ---- mesh-free scenes -----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("seed", [0, 1])
 @pytest.mark.parametrize("real", ["float", "double"])
-def test_mesh_free_scenes_equal_render_ref(seed, real):
+def test_an_unused_mesh_library_changes_nothing(mrefs, seed, real):
+    """Mesh-free tables as they are (``nmesh = 0``, null mesh pointers) and with a ``meshes`` entry that no primitive uses
+    (``nmesh > 0``, ``prim_mesh`` all -1): the same bytes in every output."""
+    ref = mrefs[0] if real == "float" else mrefs[1]
     t, xpos, xquat, kp, markers, cams, tanh = random_scene(seed, 67, 23, n_frames=2)
+    tm = add_meshes(t, library((0, 2)), [], [], np.zeros((0, 3)), np.zeros((0, 4)), np.zeros((0, 4)), [])
+    assert "meshes" not in t and len(tm["meshes"]["node_offset"]) > 1 and (tm["meshes"]["prim_mesh"] == -1).all()
     for show in (False, True):
-        a = MeshRef(real).render(t, 67, xpos, xquat, kp, markers, show, cams, tanh, 160, 120)
-        b = RenderRef(real).render(t, 67, xpos, xquat, kp, markers, show, cams, tanh, 160, 120)
-        _same_pictures(a[:3], b[:3], f"seed {seed} {real}")
+        a = ref.render(t, 67, xpos, xquat, kp, markers, show, cams, tanh, 160, 120)
+        b = ref.render(tm, 67, xpos, xquat, kp, markers, show, cams, tanh, 160, 120)
+        assert_same(a[:3], b[:3], f"seed {seed} {real} show_error={show}")
         np.testing.assert_array_equal(a[3], b[3])

@@ -1,4 +1,5 @@
-"""Builds and binds tests/tools/render_ref.c, the CPU restatement of the render kernel (test infrastructure only).
+"""Builds and binds tests/tools/render_ref.c, the CPU restatement of the render kernel, mesh geoms included (test
+infrastructure only).
 
 Two builds, with the oracle's flags (oracle/Makefile): ``RR_REAL=float`` (the kernel's operation order: the tolerance-0
 checker) and ``RR_REAL=double`` (independent evaluation; flags the pixels that float32 rounding can flip)."""
@@ -39,27 +40,34 @@ class RrScene(C.Structure):
         ("prim_tex", _f32p), ("kp_rgba", _f32p), ("light_dir", _f32p), ("light_diff", _f32p),
         ("marker_rgba", C.c_float * 4), ("seg_rgba", C.c_float * 4), ("marker_r", C.c_float), ("seg_r", C.c_float),
         ("head_amb", C.c_float * 3), ("head_diff", C.c_float * 3), ("alpha", C.c_float), ("bg", C.c_float * 3),
+        ("nmesh", C.c_int), ("node_offset", _i32p), ("tri_offset", _i32p), ("node_box", _f32p), ("node_link", _i32p),
+        ("tri_vertex", _f32p), ("prim_mesh", _i32p),
     ]  # fmt: skip
 
 
 class RenderRef:
     """``render(tables, nbody, xpos, xquat, kp, markers, show_error, cam, tan_half_fovy, W, H)`` -> rgb, seg, depth, amb
-    (numpy).  ``tables``: the dict of ``stac_mjx_amd.render.render_tables``."""
+    (numpy).  ``tables``: the dict of ``stac_mjx_amd.render.render_tables``; its optional ``meshes`` entry is the dict of
+    ``stac_mjx_amd.mesh.pack_meshes`` plus ``prim_mesh``.  ``brute=True`` ignores the hierarchy."""
 
     def __init__(self, real: str = "float"):
         self.lib = C.CDLL(str(build(real)))
         vp = C.c_void_p
-        self.lib.rr_render.argtypes = [C.POINTER(RrScene), C.c_int, vp, vp, vp, vp, C.c_int, vp, C.c_float, C.c_int, C.c_int,
-                                       vp, vp, vp, vp]
-        self.lib.rr_render.restype = C.c_int
+        for fn in (self.lib.rr_render, self.lib.rr_render_brute):
+            fn.argtypes = [C.POINTER(RrScene), C.c_int, vp, vp, vp, vp, C.c_int, vp, C.c_float, C.c_int, C.c_int, vp, vp, vp, vp]
+            fn.restype = C.c_int
 
-    def render(self, t, nbody, xpos, xquat, kp, markers, show_error, cam, tan_half_fovy, W, H):
+    def render(self, t, nbody, xpos, xquat, kp, markers, show_error, cam, tan_half_fovy, W, H, brute=False):
         keep = []
 
         def arr(a, dt):
             a = np.ascontiguousarray(np.asarray(a), dtype=dt)
             keep.append(a)
             return a
+
+        def flat(a, dt, ptr):  # an empty table is passed as one zero, never read
+            a = np.asarray(a)
+            return arr(a.reshape(-1) if a.size else np.zeros(1), dt).ctypes.data_as(ptr)
 
         s = RrScene()
         s.nprim, s.nbody, s.nkp, s.nlight = len(t["prim_type"]), int(nbody), len(t["kp_rgba"]), len(t["light_dir"])
@@ -68,13 +76,21 @@ class RenderRef:
         for k, src in (("prim_size", "prim_size"), ("prim_pos", "prim_pos"), ("prim_quat", "prim_quat"), ("prim_rgba", "prim_rgba"),
                        ("prim_rgb2", "prim_rgb2"), ("prim_tex", "prim_texrepeat"), ("kp_rgba", "kp_rgba"),
                        ("light_dir", "light_dir"), ("light_diff", "light_diffuse")):
-            setattr(s, k, arr(np.asarray(t[src]).reshape(-1) if np.asarray(t[src]).size else np.zeros(1), np.float32).ctypes.data_as(_f32p))
+            setattr(s, k, flat(t[src], np.float32, _f32p))
         s.marker_rgba[:] = [float(v) for v in t["marker_rgba"]]
         s.seg_rgba[:] = [float(v) for v in t["segment_rgba"]]
         s.head_amb[:] = [float(v) for v in t["head_ambient"]]
         s.head_diff[:] = [float(v) for v in t["head_diffuse"]]
         s.bg[:] = [float(v) for v in t["background"]]
         s.marker_r, s.seg_r, s.alpha = float(t["marker_radius"]), float(t["segment_radius"]), float(t["alpha"])
+        m = t.get("meshes")
+        s.nmesh = 0
+        if m is not None:
+            s.nmesh = len(m["node_offset"]) - 1
+            for k in ("node_offset", "tri_offset", "node_link", "prim_mesh"):
+                setattr(s, k, flat(m[k], np.int32, _i32p))
+            for k in ("node_box", "tri_vertex"):
+                setattr(s, k, flat(m[k], np.float32, _f32p))
         cam = arr(cam, np.float32).reshape(-1, 12)
         N = cam.shape[0]
         xpos, xquat = arr(xpos, np.float32), arr(xquat, np.float32)
@@ -85,8 +101,9 @@ class RenderRef:
         depth = np.zeros((N, H, W), np.float32)
         amb = np.zeros((N, H, W), np.uint8)
         p = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None
-        rc = self.lib.rr_render(C.byref(s), N, p(xpos), p(xquat), p(kp), p(markers), 1 if show_error else 0, p(cam),
-                                C.c_float(float(tan_half_fovy)), int(W), int(H), p(rgb), p(seg), p(depth), p(amb))
+        fn = self.lib.rr_render_brute if brute else self.lib.rr_render
+        rc = fn(C.byref(s), N, p(xpos), p(xquat), p(kp), p(markers), 1 if show_error else 0, p(cam), C.c_float(float(tan_half_fovy)),
+                int(W), int(H), p(rgb), p(seg), p(depth), p(amb))
         if rc != 0:
             raise RuntimeError(f"rr_render returned {rc}")
         return rgb, seg, depth, amb

@@ -1,12 +1,17 @@
 /*
- * render_ref.c -- CPU restatement of the frame rule of DESIGN.md "Rendering" and of the arithmetic of
- * stac_mjx_amd/csrc/stac_render.hip (TEST INFRASTRUCTURE ONLY).
+ * render_ref.c -- CPU restatement of the frame rule of DESIGN.md "Rendering", mesh geoms included, and of the arithmetic of
+ * stac_mjx_amd/csrc/stac_render.hip (TEST INFRASTRUCTURE ONLY): the one checker of the render kernel, render_kernel<false>
+ * and render_kernel<true> alike.
+ *
+ * A mesh instance (type 7) is walked through the hierarchy arrays of stac_render_meshes exactly as the kernel walks them
+ * (rr_render), or tested triangle by triangle with the hierarchy ignored (rr_render_brute).  A scene without meshes has
+ * nmesh = 0 and null mesh pointers.
  *
  * Built twice by tests/tools/build_render_ref.py:
  *   -DRR_REAL=float : the kernel's operation order, operation by operation (no FMA, -ffp-contract=off): the
  *                     tolerance-0 checker of the GPU tests;
  *   -DRR_REAL=double: the same rule evaluated in double, the independent evaluation.  It also flags the pixels
- *                     whose outcome float32 rounding can flip (rr_render's `amb`, see tests/test_render_host.py).
+ *                     whose outcome float32 rounding can flip (rr_render's `amb`, see compare_builds in tests/render_cases.py).
  * It does not cull: it only skips a primitive whose bounding sphere misses the ray by a generous margin, tested
  * in double.  Rows run in parallel with OpenMP.
  */
@@ -31,7 +36,8 @@ static real rmin(real a, real b) { return IS_F32 ? (real)fminf((float)a, (float)
 /* margin of a hit test against float32 rounding: 64 x 2^-24 */
 #define AMB_TOL (64.0 / 16777216.0)
 
-enum { T_NONE = -1, T_PLANE = 0, T_SPHERE = 2, T_CAPSULE = 3, T_ELLIPSOID = 4, T_CYLINDER = 5, T_BOX = 6 };
+enum { T_NONE = -1, T_PLANE = 0, T_SPHERE = 2, T_CAPSULE = 3, T_ELLIPSOID = 4, T_CYLINDER = 5, T_BOX = 6, T_MESH = 7 };
+#define MESH_PAD R_(1.0 / 65536.0)
 enum { F_TRANSPARENT = 1, F_CHECKER = 2, F_TEXUNIFORM = 4 };
 #define LAYERS 8
 #define MAXP 512
@@ -46,11 +52,20 @@ typedef struct {
     float head_amb[3], head_diff[3];
     float alpha;
     float bg[3];
+    /* stac_render_meshes */
+    int nmesh;
+    const int32_t *node_offset, *tri_offset;
+    const float *node_box;
+    const int32_t *node_link;
+    const float *tri_vertex;
+    const int32_t *prim_mesh;
 } rr_scene;
 
 typedef struct {
     real c[3], R[9], sz[3], brad;
     int type, flags;
+    int mesh;  /* a mesh: sz = world position of the geom frame's origin, c = world centre of the root box */
+    real mag;
 } rec_t;
 
 static real dot3(const real *a, const real *b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
@@ -75,7 +90,8 @@ static int finite3(const float *p) { return p[0] == p[0] && p[1] == p[1] && p[2]
 static void build_prim(const rr_scene *S, int f, int i, const float *xpos, const float *xquat, const float *kp,
                        const float *markers, int show_error, rec_t *r) {
     int type = T_NONE, flags = 0;
-    real c[3] = {0, 0, 0}, R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, sz[3] = {0, 0, 0};
+    real c[3] = {0, 0, 0}, R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, sz[3] = {0, 0, 0}, brad = 0;
+    r->mesh = -1; r->mag = 0;
     const int P = S->nprim, K = S->nkp;
     if (i < P) {
         type = S->prim_type[i];
@@ -90,6 +106,21 @@ static void build_prim(const rr_scene *S, int f, int i, const float *xpos, const
         for (int a = 0; a < 3; ++a) pp[a] = R_(S->prim_pos[3 * i + a]);
         mat_vec(Rb, pp, lp);
         for (int a = 0; a < 3; ++a) { c[a] = R_(xp[a]) + lp[a]; sz[a] = R_(S->prim_size[3 * i + a]); }
+        if (type == T_MESH) {
+            const int mi = S->prim_mesh[i];
+            const float *nd = S->node_box + 6 * (size_t)S->node_offset[mi];
+            real bc[3], he[3], wc[3], mag = 0;
+            for (int a = 0; a < 3; ++a) {
+                bc[a] = (R_(nd[a]) + R_(nd[3 + a])) * R_(0.5);
+                he[a] = (R_(nd[3 + a]) - R_(nd[a])) * R_(0.5);
+                mag = mag + rmax(FABS(R_(nd[a])), FABS(R_(nd[3 + a])));
+            }
+            mat_vec(R, bc, wc);
+            for (int a = 0; a < 3; ++a) { sz[a] = c[a]; c[a] = c[a] + wc[a]; }
+            brad = SQRT(dot3(he, he));
+            r->mesh = mi;
+            r->mag = mag;
+        }
     } else if (i < P + K) {
         if (kp) {
             const float *p = kp + ((size_t)f * K + (i - P)) * 3;
@@ -117,7 +148,6 @@ static void build_prim(const rr_scene *S, int f, int i, const float *xpos, const
             }
         }
     }
-    real brad = 0;
     if (type == T_SPHERE) brad = sz[0];
     else if (type == T_ELLIPSOID) brad = rmax(sz[0], rmax(sz[1], sz[2]));
     else if (type == T_CAPSULE) brad = sz[1] + sz[0];
@@ -257,7 +287,95 @@ static real intersect(const rec_t *r, const real *o, const real *d, real dd, int
     return -1;
 }
 
-static void normal_at(const rec_t *r, const real *o, const real *d, real t, int face, real *n) {
+/* One triangle of the mesh against the geom-frame ray ol + t dl; updates (best, btri).  amb: the barycentric sign tests,
+ * t > 0 and the tie with the best hit so far, each against 64 x 2^-24 times its condition number: the numerators are
+ * formed from ao = ol - v0 (error about eps (|ol| + |v0|)) times an edge, divided by det. */
+static void hit_tri(const float *v, int ti, const real *ol, const real *dl, real *best, int *btri, int *bill, int *amb) {
+    int ill = 0;
+    const real v0[3] = {R_(v[0]), R_(v[1]), R_(v[2])};
+    const real e1[3] = {R_(v[3]) - v0[0], R_(v[4]) - v0[1], R_(v[5]) - v0[2]};
+    const real e2[3] = {R_(v[6]) - v0[0], R_(v[7]) - v0[1], R_(v[8]) - v0[2]};
+    const real N[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
+    const real det = -dot3(dl, N);
+    if (det == 0) return;
+    const real inv = R_(1) / det;
+    const real ao[3] = {ol[0] - v0[0], ol[1] - v0[1], ol[2] - v0[2]};
+    const real dao[3] = {ao[1] * dl[2] - ao[2] * dl[1], ao[2] * dl[0] - ao[0] * dl[2], ao[0] * dl[1] - ao[1] * dl[0]};
+    const real bu = dot3(e2, dao) * inv;
+    const real bv = -dot3(e1, dao) * inv;
+    const real t = dot3(ao, N) * inv;
+    {
+        const double A = sqrt((double)dot3(ol, ol)) + sqrt((double)dot3(v0, v0)) + sqrt((double)dot3(ao, ao));
+        const double l1 = sqrt((double)dot3(e1, e1)), l2 = sqrt((double)dot3(e2, e2)), ln = sqrt((double)dot3(N, N));
+        const double ad = fabs((double)det);
+        const int near_in = (double)bu >= -0.5 && (double)bv >= -0.5 && (double)(bu + bv) <= 1.5;  /* far misses cannot flip */
+        if (near_in) {
+            const int in_u = bu >= 0, in_v = bv >= 0, in_w = bu + bv <= 1;
+            /* a sign test matters when the other two hold (or are themselves close: they get flagged on their own) */
+            if (in_v && in_w) flag(amb, (double)bu, A * l2 / ad + fabs((double)bu));
+            if (in_u && in_w) flag(amb, (double)bv, A * l1 / ad + fabs((double)bv));
+            if (in_u && in_v) flag(amb, 1.0 - (double)(bu + bv), A * (l1 + l2) / ad + 1.0);
+            if (in_u && in_v && in_w) {
+                flag(amb, (double)t, A * ln / ad);
+                if (*btri >= 0 && t > 0) flag(amb, (double)(t - *best), A * ln / ad + fabs((double)t));
+                /* depth of a grazing hit.  t = (ao . N) / det cancels in both dot products when the ray runs nearly in
+                 * the triangle's plane: ao carries an absolute error of about 4 eps A, the numerator 3 more roundings,
+                 * det about 8 eps |N|, so the relative error of t is bounded by 8 eps (A / t + 1) |N| / |det|.  Where
+                 * that bound exceeds the 1e-5 that compare_builds allows a depth, float32 cannot give the depth: the pixel
+                 * is flagged if this hit becomes its depth (*bill, see render). */
+                if (t > 0 && 8.0 / 16777216.0 * (A / (double)t + 1.0) * ln / ad > 1e-5) ill = 1;
+            }
+        }
+    }
+    if (bu >= 0 && bv >= 0 && bu + bv <= 1 && t > 0 && (t < *best || (t == *best && ti < *btri))) {
+        *best = t;
+        *btri = ti;
+        *bill = ill;
+    }
+}
+
+/* The kernel's hit_mesh; brute != 0 ignores the hierarchy and tests every triangle of the mesh in index order. */
+static real hit_mesh(const rr_scene *S, const rec_t *r, const real *o, const real *d, int brute, int *tri, int *ill, int *amb) {
+    const real *R = r->R, *org = r->sz;
+    const int mi = r->mesh;
+    const real oc[3] = {o[0] - org[0], o[1] - org[1], o[2] - org[2]};
+    real ol[3], dl[3];
+    mat_tvec(R, oc, ol);
+    mat_tvec(R, d, dl);
+    const real pad = (FABS(ol[0]) + FABS(ol[1]) + FABS(ol[2]) + r->mag) * MESH_PAD;
+    const real idl[3] = {R_(1) / dl[0], R_(1) / dl[1], R_(1) / dl[2]};
+    const int n0 = S->node_offset[mi], nn = S->node_offset[mi + 1] - n0;
+    const float *box = S->node_box + 6 * (size_t)n0;
+    const int32_t *link = S->node_link + 3 * (size_t)n0;
+    const float *tris = S->tri_vertex + 9 * (size_t)S->tri_offset[mi];
+    const int nt = S->tri_offset[mi + 1] - S->tri_offset[mi];
+    real best = (real)INFINITY;
+    int btri = -1;
+    if (brute) {
+        for (int ti = 0; ti < nt; ++ti) hit_tri(tris + 9 * (size_t)ti, ti, ol, dl, &best, &btri, ill, amb);
+    } else {
+        int n = 0;
+        while (n < nn) {
+            const float *b = box + 6 * (size_t)n;
+            real tn = -(real)INFINITY, tf = (real)INFINITY;
+            for (int k = 0; k < 3; ++k) {
+                const real t1 = ((R_(b[k]) - pad) - ol[k]) * idl[k], t2 = ((R_(b[3 + k]) + pad) - ol[k]) * idl[k];
+                const real lo_t = t1 < t2 ? t1 : t2, hi_t = t1 < t2 ? t2 : t1;
+                if (lo_t > tn) tn = lo_t;
+                if (hi_t < tf) tf = hi_t;
+            }
+            if (!(tn <= tf && tf > 0 && tn <= best)) { n = link[3 * n]; continue; }
+            const int first = link[3 * n + 1], count = link[3 * n + 2];
+            if (count == 0) { n = n + 1; continue; }
+            for (int k = 0; k < count; ++k) hit_tri(tris + 9 * (size_t)(first + k), first + k, ol, dl, &best, &btri, ill, amb);
+            n = link[3 * n];
+        }
+    }
+    *tri = btri;
+    return btri >= 0 ? best : -1;
+}
+
+static void normal_at(const rr_scene *S, const rec_t *r, const real *o, const real *d, real t, int face, int tri, real *n) {
     const int type = r->type;
     const real *c = r->c, *R = r->R, *sz = r->sz;
     const real q[3] = {o[0] + d[0] * t - c[0], o[1] + d[1] * t - c[1], o[2] + d[2] * t - c[2]};
@@ -270,6 +388,15 @@ static void normal_at(const rec_t *r, const real *o, const real *d, real t, int 
         v[0] = q[0] - w[0] * z; v[1] = q[1] - w[1] * z; v[2] = q[2] - w[2] * z;
     } else if (type == T_PLANE) {
         v[0] = R[2]; v[1] = R[5]; v[2] = R[8];
+    } else if (type == T_MESH) {
+        const float *p = S->tri_vertex + 9 * ((size_t)S->tri_offset[r->mesh] + (size_t)tri);
+        const real e1[3] = {R_(p[3]) - R_(p[0]), R_(p[4]) - R_(p[1]), R_(p[5]) - R_(p[2])};
+        const real e2[3] = {R_(p[6]) - R_(p[0]), R_(p[7]) - R_(p[1]), R_(p[8]) - R_(p[2])};
+        real N[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
+        real dl[3];
+        mat_tvec(R, d, dl);
+        if (dot3(dl, N) > 0) { N[0] = -N[0]; N[1] = -N[1]; N[2] = -N[2]; }
+        mat_vec(R, N, v);
     } else {
         real ql[3], nl[3];
         mat_tvec(R, q, ql);
@@ -292,10 +419,10 @@ static void normal_at(const rec_t *r, const real *o, const real *d, real t, int 
     n[0] = v[0] / len; n[1] = v[1] / len; n[2] = v[2] / len;
 }
 
-static void shade(const rr_scene *S, const rec_t *r, int id, const real *o, const real *d, real t, int face, const real *zc,
-                  real *col, int *amb) {
+static void shade(const rr_scene *S, const rec_t *r, int id, const real *o, const real *d, real t, int face, int tri,
+                  const real *zc, real *col, int *amb) {
     real n[3], rgb[3];
-    normal_at(r, o, d, t, face, n);
+    normal_at(S, r, o, d, t, face, tri, n);
     const int P = S->nprim, K = S->nkp;
     if (id < P) {
         const float *c1 = S->prim_rgba + 4 * id;
@@ -343,14 +470,14 @@ static uint8_t quant(real c) {
     return (uint8_t)(int)FLOOR(x * R_(255) + R_(0.5));
 }
 
-typedef struct { real t; int id, face; } hit_t;
+typedef struct { real t; int id, face, tri; } hit_t;
 
 static int hit_less(const hit_t *a, const hit_t *b) { return a->t < b->t || (a->t == b->t && a->id < b->id); }
 
 /* Renders N frames; rgb [N,H,W,3], seg [N,H,W], depth [N,H,W], amb [N,H,W] (each may be NULL).  Returns 0. */
-int rr_render(const rr_scene *S, int N, const float *xpos, const float *xquat, const float *kp, const float *markers,
-              int show_error, const float *cam, float tanhf_, int W, int H, uint8_t *rgb, int32_t *seg, float *depth,
-              uint8_t *ambout) {
+static int render(const rr_scene *S, int N, const float *xpos, const float *xquat, const float *kp, const float *markers,
+                  int show_error, const float *cam, float tanhf_, int W, int H, uint8_t *rgb, int32_t *seg, float *depth,
+                  uint8_t *ambout, int brute) {
     const int Ptot = S->nprim + 3 * S->nkp;
     if (Ptot > MAXP) return -3;
     rec_t *recs = (rec_t *)malloc(sizeof(rec_t) * (Ptot > 0 ? Ptot : 1));
@@ -376,7 +503,7 @@ int rr_render(const rr_scene *S, int N, const float *xpos, const float *xquat, c
                 }
                 const real dd = dot3(d, d);
                 real to = (real)INFINITY, to2 = (real)INFINITY;
-                int io = -1, fo = 0, nt = 0;
+                int io = -1, fo = 0, tro = 0, nt = 0, to_ill = 0;
                 for (int i = 0; i < Ptot; ++i) {
                     const rec_t *r = &recs[i];
                     if (r->type == T_NONE) continue;
@@ -387,18 +514,20 @@ int rr_render(const rr_scene *S, int N, const float *xpos, const float *xquat, c
                     const double br = (double)r->brad * 1.01 + 1e-6 + 1e-6 * sqrt(ww);
                     if (wd < -br) continue;
                     if (ww - wd * wd > br * br) continue;
-                    int face;
-                    const real t = intersect(r, o, d, dd, &face, &amb);
+                    int face, tri = 0, ill = 0;
+                    const real t = r->type == T_MESH ? (face = 0, hit_mesh(S, r, o, d, brute, &tri, &ill, &amb))
+                                                     : intersect(r, o, d, dd, &face, &amb);
                     if (!(t > 0)) continue;
                     if (r->flags & F_TRANSPARENT) {
-                        tr[nt].t = t; tr[nt].id = i; tr[nt].face = face; ++nt;
+                        tr[nt].t = t; tr[nt].id = i; tr[nt].face = face; tr[nt].tri = tri; ++nt;
                     } else if (t < to || (t == to && i < io)) {
                         to2 = to;
-                        to = t; io = i; fo = face;
+                        to = t; io = i; fo = face; tro = tri; to_ill = ill;
                     } else if (t < to2) {
                         to2 = t;
                     }
                 }
+                if (io >= 0 && to_ill) amb = 1;  /* the depth is a grazing mesh hit's: see hit_tri */
                 /* depth ties between the two nearest opaque hits: relative gap */
                 if (io >= 0 && to2 < (real)INFINITY) flag(&amb, (double)(to2 - to), (double)to);
                 /* the LAYERS nearest transparent hits by (t, id) */
@@ -414,12 +543,12 @@ int rr_render(const rr_scene *S, int N, const float *xpos, const float *xquat, c
                 }
                 const real zc[3] = {Rc[2], Rc[5], Rc[8]};
                 real col[3] = {R_(S->bg[0]), R_(S->bg[1]), R_(S->bg[2])};
-                if (io >= 0) shade(S, &recs[io], io, o, d, to, fo, zc, col, &amb);
+                if (io >= 0) shade(S, &recs[io], io, o, d, to, fo, tro, zc, col, &amb);
                 const real a = R_(S->alpha), na = R_(1) - R_(S->alpha);
                 for (int k = (nt < LAYERS ? nt : LAYERS) - 1; k >= 0; --k) {
                     if (tr[k].t < to) {
                         real s[3];
-                        shade(S, &recs[tr[k].id], tr[k].id, o, d, tr[k].t, tr[k].face, zc, s, &amb);
+                        shade(S, &recs[tr[k].id], tr[k].id, o, d, tr[k].t, tr[k].face, tr[k].tri, zc, s, &amb);
                         for (int q = 0; q < 3; ++q) col[q] = col[q] * na + s[q] * a;
                     }
                 }
@@ -433,4 +562,17 @@ int rr_render(const rr_scene *S, int N, const float *xpos, const float *xquat, c
     }
     free(recs);
     return 0;
+}
+
+int rr_render(const rr_scene *S, int N, const float *xpos, const float *xquat, const float *kp, const float *markers,
+              int show_error, const float *cam, float tanhf_, int W, int H, uint8_t *rgb, int32_t *seg, float *depth,
+              uint8_t *ambout) {
+    return render(S, N, xpos, xquat, kp, markers, show_error, cam, tanhf_, W, H, rgb, seg, depth, ambout, 0);
+}
+
+/* The same picture with the hierarchy ignored: every triangle of every mesh instance is tested. */
+int rr_render_brute(const rr_scene *S, int N, const float *xpos, const float *xquat, const float *kp, const float *markers,
+                    int show_error, const float *cam, float tanhf_, int W, int H, uint8_t *rgb, int32_t *seg, float *depth,
+                    uint8_t *ambout) {
+    return render(S, N, xpos, xquat, kp, markers, show_error, cam, tanhf_, W, H, rgb, seg, depth, ambout, 1);
 }

@@ -237,6 +237,29 @@ int32_t stac_render(const stac_render_scene *s, int32_t N, const float *xpos, co
                     const float *markers, int32_t show_error, const float *cam, float tan_half_fovy, int32_t width,
                     int32_t height, uint8_t *rgb_out, int32_t *seg_out, float *depth_out, void *stream);
 
+/* ---- JPEG encoding of frames on the device (no stac_model needed; the current device is used) ----------------------
+ * Baseline sequential JPEG exactly as libjpeg writes it with its default tables: 8 bit, YCbCr 4:2:0, one interleaved
+ * scan, Annex K Huffman tables, IJG quality scaling, integer colour conversion and "slow integer" DCT, a restart marker
+ * every restart_mcus MCUs (16 x 16 pixels).  The bytes equal what libjpeg produces for the same pixels, quality and
+ * restart interval.  width, height: 1 .. 65535; quality: 1 .. 100. */
+
+/* HOST.  Writes SOI .. SOS (everything in front of the entropy-coded data) to buf and returns its length (at most 640);
+ * restart_mcus 0 .. 65535, 0 = no DRI segment.  buf == NULL: only the length.  Negative on error. */
+int64_t stac_jpeg_header(int32_t width, int32_t height, int32_t quality, int32_t restart_mcus, uint8_t *buf, int64_t capacity);
+
+/* Bytes of device workspace that stac_jpeg_encode needs for N frames (restart_mcus 1 .. 65535).  Negative on error. */
+int64_t stac_jpeg_workspace_bytes(int64_t N, int32_t width, int32_t height, int32_t restart_mcus);
+
+/* Encodes rgb[N,H,W,3] (device, uint8, any byte alignment) into N complete files (SOI .. EOI) written back to back into
+ * out (device); frame f occupies out[frame_offset[f] .. frame_offset[f+1]).  frame_offset (device, [N+1]) always holds
+ * the true sizes.  Nothing is written at or beyond out + out_capacity: when frame_offset[N] > out_capacity the output
+ * is truncated there and the call is to be repeated with a larger buffer.  workspace: device, 8-byte aligned, at least
+ * stac_jpeg_workspace_bytes(...) bytes, its contents do not matter; it may be reused once the call has finished on
+ * `stream`.  restart_mcus: 1 .. 65535.  N == 0: nothing is done. */
+int32_t stac_jpeg_encode(int64_t N, int32_t width, int32_t height, int32_t quality, int32_t restart_mcus, const uint8_t *rgb,
+                         uint8_t *out, int64_t out_capacity, int64_t *frame_offset, void *workspace, int64_t workspace_bytes,
+                         void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,18 @@ Mesh geoms (profiles/render/render_mesh_bench.json):
   1920 x 1200 from device events over at least 1 s, and the f32 restatement (the same file) on the mesh scene;
 * ``hierarchy``: one 20 480-triangle icosphere filling the frame, with the hierarchy and with the developer switch
   STAC_RENDER_MESH_SINGLE_LEAF=1 (read at scene creation): equal pictures, and the time of one launch each.
+
+The JPEG encoder (profiles/render/render_jpeg_bench.json):
+
+  python profiles/tools/render_bench.py --sections encoder --encoders pil,gpu,gpu_noframes --out <file>
+  python profiles/tools/render_bench.py --sections encoder --encoders pil --tree <checkout of the parent commit>
+
+* ``encoder``: the 1000-frame rodent job at 1920 x 1200 to ``.avi`` as ``Stac.render`` runs it (a Renderer with the default
+  memory budget, so chunks of frames), ``--runs`` times per encoder, the encoders alternating: wall time end to end and its
+  parts (FK + cameras + render + copies to the host as far as the encoder needs them; PIL encode; file write).  The GPU
+  encoders get one more, instrumented pass with a device synchronisation between the steps of every chunk: render, the
+  encode kernels, the copy of the compressed bytes (and of the raw frames) to the host; and the ``.avi`` size against
+  Pillow's files without restart markers.  ``--tree``: import the package from another checkout (only ``pil`` there).
 """
 
 from __future__ import annotations
@@ -36,6 +48,8 @@ import numpy as np
 import torch
 
 ROOT = Path(__file__).resolve().parents[2]
+if "--tree" in sys.argv:  # before the package is imported
+    ROOT = Path(sys.argv[sys.argv.index("--tree") + 1]).resolve()
 sys.path[:0] = [str(ROOT), str(ROOT / "tests"), str(ROOT / "tests" / "tools")]
 HBM_PEAK_BPS = 8.0e12  # MI355X HBM3E peak
 
@@ -54,6 +68,9 @@ def main():
     ap.add_argument("--quick", action="store_true", help="small sizes (a smoke run of this script)")
     ap.add_argument("--sections", default="kernel,viz,cpu", help="comma list of kernel, viz, cpu, mesh, hierarchy")
     ap.add_argument("--mesh-frames", type=int, default=200)
+    ap.add_argument("--encoders", default="pil,gpu,gpu_noframes", help="encoder section: comma list of pil, gpu, gpu_noframes")
+    ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--tree", default=None, help="import the package from this checkout instead of the script's own")
     args = ap.parse_args()
     sections = set(args.sections.split(","))
     from render_cases import kp_rgba, rodent_scene
@@ -113,6 +130,8 @@ def main():
         res["mesh"] = mesh_section(args, r, fs, scene, cfg, dv, W, H)
     if "hierarchy" in sections:
         res["hierarchy"] = hierarchy_section(args, eng, W, H)
+    if "encoder" in sections:
+        res["encoder"] = encoder_section(args, eng, scene, fs, cfg, dv, W, H, tmp)
     if not {"viz", "cpu"} & sections:
         return finish(args, res)
 
@@ -150,6 +169,114 @@ def main():
     res["cpu_restatement_f32"] = {"frames": nc, "frames_per_s": nc / dt, "threads": int(os.environ.get("OMP_NUM_THREADS", "0") or 0)}
     print("cpu_restatement_f32", json.dumps(res["cpu_restatement_f32"]), flush=True)
     finish(args, res)
+
+
+def encoder_section(args, eng, scene, fs, cfg, dv, W, H, tmp):
+    """The viz job end to end, per encoder (see the module docstring)."""
+    from render_cases import kp_rgba
+    from stac_mjx_amd.render import Renderer
+    from stac_mjx_amd.video import JPEG_QUALITY, encode_jpegs, read_avi, write_avi
+
+    pairs = cfg["KEYPOINT_MODEL_PAIRS"]
+    r = Renderer(eng, scene, list(pairs), list(pairs.values()), kp_rgba(cfg), float(cfg["MARKER_SIZE"]))  # default budget
+    V = 50 if args.quick else args.viz_frames
+    qv, kv = np.tile(dv["qpos"], (V // 50 + 1, 1))[:V], np.tile(dv["kp_data"], (V // 50 + 1, 1))[:V]
+    t = fs.tables
+    fps = float(cfg["RENDER_FPS"])
+    kw = dict(qpos0=t.qpos0, parent=t.body_parentid, camera="close_profile", width=W, height=H)
+    encoders = args.encoders.split(",")
+    out = {"frames": V, "width": W, "height": H, "quality": JPEG_QUALITY, "io_threads": _io_threads(), "runs": {e: [] for e in encoders}}
+
+    def job(enc):
+        path = tmp / f"{enc}.avi"
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        if enc == "pil":
+            o = r.render(qv, kv, dv["offsets"], **kw)
+            frames = list(o["rgb"].numpy())
+            t1 = time.perf_counter()
+            jp = encode_jpegs(frames)
+            t2 = time.perf_counter()
+            write_avi(path, frames, fps, jpegs=jp)
+            t3 = time.perf_counter()
+            return {"total_s": t3 - t0, "render_and_d2h_s": t1 - t0, "encode_s": t2 - t1, "write_s": t3 - t2, "avi_bytes": path.stat().st_size}
+        o = r.render(qv, kv, dv["offsets"], want_jpeg=True, want_rgb=enc == "gpu", **kw)
+        frames = list(o["rgb"].numpy()) if enc == "gpu" else []
+        t1 = time.perf_counter()
+        write_avi(path, None, fps, jpegs=o["jpeg"], size=(W, H))
+        t3 = time.perf_counter()
+        return {"total_s": t3 - t0, "render_encode_d2h_s": t1 - t0, "write_s": t3 - t1, "avi_bytes": path.stat().st_size,
+                "frames_returned": len(frames)}
+
+    for enc in encoders:  # warm-up: allocator, page cache, thread pool
+        job(enc)
+    for k in range(args.runs):
+        for enc in encoders:
+            out["runs"][enc].append(job(enc))
+            print("encoder", enc, json.dumps(out["runs"][enc][-1]), flush=True)
+    for enc in encoders:
+        tot = [x["total_s"] for x in out["runs"][enc]]
+        out[enc + "_total_s_range"] = [min(tot), max(tot)]
+    if any(e.startswith("gpu") for e in encoders):
+        out["gpu_split"] = {e: gpu_split(r, qv, kv, dv, kw, W, H, e == "gpu") for e in encoders if e.startswith("gpu")}
+        print("encoder gpu_split", json.dumps(out["gpu_split"]), flush=True)
+        # bytes against Pillow's files without restart markers (what encoder="pil" writes), over the first 50 frames
+        o = r.render(qv[:50], kv[:50], dv["offsets"], want_jpeg=True, **kw)
+        pil = encode_jpegs(list(o["rgb"].numpy()))
+        out["bytes_first_50_frames"] = {"gpu_restart_one_mcu_row": sum(len(j) for j in o["jpeg"]), "pil_no_restart": sum(len(j) for j in pil),
+                                        "raw": 50 * W * H * 3}
+        print("encoder bytes", json.dumps(out["bytes_first_50_frames"]), flush=True)
+    r.close()
+    return out
+
+
+def gpu_split(r, qv, kv, dv, kw, W, H, want_rgb):
+    """One instrumented pass of the GPU-encoder job: a device synchronisation after every step of every chunk."""
+    from stac_mjx_amd import jpeg
+
+    dev = r.engine.device
+    t = {"fk_cameras_s": 0.0, "render_s": 0.0, "encode_kernels_s": 0.0, "jpeg_d2h_s": 0.0, "raw_d2h_s": 0.0}
+    sync = torch.cuda.synchronize
+    sync()
+    t0 = time.perf_counter()
+    N = len(qv)
+    q = torch.as_tensor(np.asarray(qv, np.float32)).to(dev)
+    kpt = torch.as_tensor(np.asarray(kv, np.float32)).to(dev).reshape(N, r.K, 3)
+    xpos, xquat, markers = r.poses(q, dv["offsets"])
+    cam, tanh = r.cameras(kw["camera"], xpos, xquat, kw["qpos0"], kw["parent"])
+    sync()
+    t["fk_cameras_s"] = time.perf_counter() - t0
+    R = jpeg.default_restart_mcus(W)
+    per_frame = H * W * 3 + jpeg.workspace_bytes(1, W, H, R) + jpeg.JpegEncoder.first_guess(1, W, H)
+    chunk = int(max(1, min(N, r.memory_budget // per_frame)))
+    enc = jpeg.JpegEncoder(chunk, W, H, jpeg.JPEG_QUALITY, R, dev)
+    dbuf = torch.empty((chunk, H, W, 3), dtype=torch.uint8, device=dev)
+    host = torch.empty((N, H, W, 3), dtype=torch.uint8) if want_rgb else None
+    total = 0
+    for lo in range(0, N, chunk):
+        hi = min(N, lo + chunk)
+        n = hi - lo
+        t0 = time.perf_counter()
+        r.handle.render(xpos[lo:hi], xquat[lo:hi], kpt[lo:hi], markers[lo:hi], False, cam[lo:hi], tanh, W, H, dbuf[:n])
+        sync()
+        t1 = time.perf_counter()
+        jpeg.encode_raw(dbuf[:n], enc.out, enc.frame_offset, enc.workspace, enc.quality, enc.R)
+        sync()
+        t2 = time.perf_counter()
+        off = enc.frame_offset[: n + 1].cpu().tolist()
+        assert off[n] <= enc.out.numel(), "first output buffer too small for these pictures"
+        data = enc.out[: off[n]].cpu().numpy().tobytes()
+        total += len(data)
+        t3 = time.perf_counter()
+        if want_rgb:
+            host[lo:hi].copy_(dbuf[:n])
+        t4 = time.perf_counter()
+        t["render_s"] += t1 - t0
+        t["encode_kernels_s"] += t2 - t1
+        t["jpeg_d2h_s"] += t3 - t2
+        t["raw_d2h_s"] += t4 - t3
+    t.update(chunk_frames=chunk, jpeg_bytes=total, restart_mcus=R)
+    return t
 
 
 def finish(args, res):

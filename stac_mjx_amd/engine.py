@@ -54,6 +54,7 @@ ABI_SYMBOLS = (
     "stac_model_info", "stac_set_site_pos", "stac_get_site_pos", "stac_fk", "stac_q_solve", "stac_q_phase",
     "stac_m_phase_workspace_floats", "stac_m_phase_partial", "stac_m_phase_finish",
     "stac_render_scene_create", "stac_render_scene_create_with_meshes", "stac_render_scene_destroy", "stac_render",
+    "stac_jpeg_header", "stac_jpeg_workspace_bytes", "stac_jpeg_encode",
 )  # fmt: skip
 
 

@@ -315,8 +315,12 @@ class Renderer:
         return cam.to(torch.float32).contiguous(), tanh
 
     def render(self, qpos, kp, offsets, *, qpos0, parent, camera=0, width=1920, height=1200, show_marker_error=False,
-               want_seg=False, want_depth=False):
-        """qpos [N, nq], kp [N, 3K] (NaN = missing keypoint) -> {"rgb": [N,H,W,3] uint8, "seg", "depth"} (CPU tensors)."""
+               want_seg=False, want_depth=False, want_jpeg=False, want_rgb=True, jpeg_quality=None, restart_mcus=None):
+        """qpos [N, nq], kp [N, 3K] (NaN = missing keypoint) -> {"rgb": [N,H,W,3] uint8, "seg", "depth"} (CPU tensors).
+
+        ``want_jpeg``: every chunk is also encoded on the device (``stac_mjx_amd.jpeg``) and ``out["jpeg"]`` is the list of
+        the frames' JPEG files (``jpeg_quality``: None = ``video.JPEG_QUALITY``; ``restart_mcus``: None = one MCU row).
+        ``want_rgb=False``: the raw frames stay on the device and ``out`` has no ``"rgb"``."""
         dev = self.engine.device
         q = torch.as_tensor(np.asarray(qpos, np.float32)).to(dev).reshape(-1, self.engine.nq)
         N = q.shape[0]
@@ -324,21 +328,38 @@ class Renderer:
         xpos, xquat, markers = self.poses(q, offsets)
         cam, tanh = self.cameras(camera, xpos, xquat, qpos0, parent)
         per_frame = height * width * (3 + 4 * want_seg + 4 * want_depth)
+        if want_jpeg:  # the encoder's workspace and its output buffer share the budget
+            from . import jpeg
+
+            quality = jpeg.JPEG_QUALITY if jpeg_quality is None else int(jpeg_quality)
+            R = jpeg.default_restart_mcus(width) if restart_mcus is None else int(restart_mcus)
+            per_frame += jpeg.workspace_bytes(1, width, height, R) + jpeg.JpegEncoder.first_guess(1, width, height)
         chunk = int(max(1, min(N, self.memory_budget // max(per_frame, 1))))
-        out = {"rgb": torch.empty((N, height, width, 3), dtype=torch.uint8)}
+        out = {}
+        if want_rgb:
+            out["rgb"] = torch.empty((N, height, width, 3), dtype=torch.uint8)
         if want_seg:
             out["seg"] = torch.empty((N, height, width), dtype=torch.int32)
         if want_depth:
             out["depth"] = torch.empty((N, height, width), dtype=torch.float32)
         dbuf = {k: torch.empty((chunk,) + v.shape[1:], dtype=v.dtype, device=dev) for k, v in out.items()}
+        if want_jpeg:
+            if not want_rgb:
+                dbuf["rgb"] = torch.empty((chunk, height, width, 3), dtype=torch.uint8, device=dev)
+            enc = jpeg.JpegEncoder(chunk, width, height, quality, R, dev)
+            jpegs = []
         for lo in range(0, N, chunk):
             hi = min(N, lo + chunk)
             n = hi - lo
             self.handle.render(xpos[lo:hi], xquat[lo:hi], kpt[lo:hi], markers[lo:hi], show_marker_error, cam[lo:hi], tanh,
-                               width, height, dbuf["rgb"][:n], dbuf["seg"][:n] if want_seg else None,
+                               width, height, dbuf["rgb"][:n] if "rgb" in dbuf else None, dbuf["seg"][:n] if want_seg else None,
                                dbuf["depth"][:n] if want_depth else None)
+            if want_jpeg:
+                jpegs.extend(enc.encode(dbuf["rgb"][:n]))
             for k in out:
                 out[k][lo:hi].copy_(dbuf[k][:n])
+        if want_jpeg:
+            out["jpeg"] = jpegs
         out["cam"], out["tan_half_fovy"] = cam, tanh
         out["xpos"], out["xquat"], out["markers"], out["kp"] = xpos, xquat, markers, kpt
         return out

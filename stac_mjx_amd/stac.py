@@ -246,10 +246,18 @@ class Stac:
         return self._renderer
 
     def render(self, qposes, kp_data, offsets, n_frames, save_path, start_frame=0, camera=0, height=1200, width=1920,
-               show_marker_error=False, *, geom_groups=None):
+               show_marker_error=False, *, geom_groups=None, encoder="pil", return_frames=True):
         """Render fitted results as a video (the reference's signature and checks, ``stac.py:569-658``); returns the list of
         H x W x 3 uint8 frames.  ``camera``: index, name, or -1 (free camera).  ``geom_groups``: the geom groups to draw
-        (None = the reference's rule, groups 0 and 2).  The engine's state is left as it was."""
+        (None = the reference's rule, groups 0 and 2).  The engine's state is left as it was.
+
+        ``encoder``: "pil" (default: frames go to the host and are encoded there) or "gpu" (``.avi`` only: the frames are
+        JPEG-encoded on the device, ``stac_mjx_amd.jpeg``, and only the compressed stream crosses to the host).
+        ``return_frames=False`` returns ``[]``; with the GPU encoder the raw frames then never leave the device."""
+        if encoder not in ("pil", "gpu"):
+            raise ValueError(f"unknown encoder {encoder!r}: 'pil' or 'gpu'")
+        if encoder == "gpu" and Path(save_path).suffix.lower() != ".avi":
+            raise ValueError(f"encoder='gpu' writes MJPEG .avi only (imageio needs raw frames): got {save_path}")
         qposes, kp_data = np.asarray(qposes), np.asarray(kp_data)
         if qposes.shape[0] != kp_data.shape[0]:
             raise ValueError(
@@ -266,8 +274,15 @@ class Stac:
 
         sl = slice(start_frame, start_frame + n_frames)
         t = self.setup.tables
+        if encoder == "gpu":
+            from .video import write_avi
+
+            out = r.render(qposes[sl], kp_data[sl], offsets, qpos0=t.qpos0, parent=t.body_parentid, camera=camera, width=width,
+                           height=height, show_marker_error=show_marker_error, want_jpeg=True, want_rgb=bool(return_frames))
+            write_avi(save_path, None, fps=float(self.cfg.model.RENDER_FPS), jpegs=out["jpeg"], size=(width, height))
+            return list(out["rgb"].numpy()) if return_frames else []
         out = r.render(qposes[sl], kp_data[sl], offsets, qpos0=t.qpos0, parent=t.body_parentid, camera=camera, width=width,
                        height=height, show_marker_error=show_marker_error)
         frames = list(out["rgb"].numpy())
         write_video(save_path, frames, fps=float(self.cfg.model.RENDER_FPS), log=self._log)
-        return frames
+        return frames if return_frames else []

@@ -44,14 +44,21 @@ def _list(kind: bytes, data: bytes) -> bytes:
     return b"LIST" + struct.pack("<I", len(data) + 4) + kind + data
 
 
-def write_avi(path, frames, fps: float, jpegs=None) -> Path:
-    """Write ``frames`` ([H, W, 3] uint8 each) as an MJPEG AVI at ``fps``.  ``jpegs``: already encoded frames."""
+def write_avi(path, frames, fps: float, jpegs=None, size=None) -> Path:
+    """Write ``frames`` ([H, W, 3] uint8 each) as an MJPEG AVI at ``fps``.  ``jpegs``: already encoded frames; with
+    ``size=(width, height)`` they are all it needs and ``frames`` may be None."""
     path = Path(path)
-    frames = list(frames)
-    if not frames:
-        raise ValueError("write_avi: no frames")
-    H, W = frames[0].shape[:2]
-    jpegs = encode_jpegs(frames) if jpegs is None else jpegs
+    frames = list(frames) if frames is not None else []
+    if size is not None and jpegs is not None:
+        W, H = int(size[0]), int(size[1])
+        jpegs = list(jpegs)
+        if not jpegs:
+            raise ValueError("write_avi: no frames")
+    else:
+        if not frames:
+            raise ValueError("write_avi: no frames")
+        H, W = frames[0].shape[:2]
+        jpegs = encode_jpegs(frames) if jpegs is None else jpegs
     n = len(jpegs)
     us = int(round(1e6 / float(fps)))
     biggest = max(len(j) for j in jpegs)

@@ -155,7 +155,14 @@ class Oracle:
         return out, float(err.value)
 
     def m_opt(self, keypoints, q, initial_offsets, is_regularized, reg_coef):
-        return self.m_finish(self.m_partial(keypoints, q), initial_offsets, is_regularized, reg_coef)
+        """m_finish(m_partial(...)) with the sums kept in the build's own precision: the same bits in float32; the float64 twin
+        does not round them to the float32 of the public partial on the way."""
+        kp, q, m0, d = _f32(keypoints), _f32(q), _f32(initial_offsets), _f32(is_regularized)
+        out = np.empty((self.K, 3), np.float32)
+        err = C.c_float()
+        self.lib.orc_m_opt(C.byref(self.m), _p(kp, _f32p), _p(q, _f32p), C.c_int32(kp.shape[0]), _p(m0, _f32p), _p(d, _f32p),
+                           C.c_float(reg_coef), _p(out, _f32p), C.byref(err))
+        return out, float(err.value)
 
     # -- drivers -------------------------------------------------------------------------
     def root_optimization(self, kp_clip, qpos, lb, ub, trunk_kps, root_kp_idx, root_dims=7, frame=0):

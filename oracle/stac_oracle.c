@@ -484,11 +484,12 @@ void orc_q_opt(const orc_model *m, const orc_pg_params *p, const float *kp,
 }
 
 /* ---- offset phase (stac_core.py:102-172) -------------------------------------------------- */
-void orc_m_partial(const orc_model *m, const float *keypoints, const float *q, int32_t T,
-                   float *partial) {
+/* The sums in `real`: s[3K], z2, T.  The public partial is float32 (it is what the ranks all-reduce); orc_m_opt, which needs no
+ * such boundary, keeps them in `real`, so that the float64 twin is float64 from the poses to the error. */
+static void m_partial_real(const orc_model *m, const float *keypoints, const float *q, int32_t T, real *s) {
     const int K = m->nsite, nq = m->nq;
     ws_t *w = ws_new(m);
-    real *s = (real *)calloc((size_t)3 * K + 2, sizeof(real));
+    for (int i = 0; i < 3 * K + 2; ++i) s[i] = R(0);
     real z2 = R(0);
     /* Summation order (XLA's is unspecified): per frame the K-site subtotal of |z|^2, then frames
      * accumulated in index order per component -- the order the HIP kernels reproduce exactly. */
@@ -507,20 +508,27 @@ void orc_m_partial(const orc_model *m, const float *keypoints, const float *q, i
         }
         z2 += z2t;
     }
-    for (int i = 0; i < 3 * K; ++i) partial[i] = (float)s[i];
-    partial[3 * K] = (float)z2;
-    partial[3 * K + 1] = (float)T;
-    free(s);
+    s[3 * K] = z2;
+    s[3 * K + 1] = R(T);
     ws_free(w);
 }
 
-void orc_m_finish(int32_t K, const float *partial, const float *initial_offsets,
-                  const float *is_regularized, float reg_coef, float *params_out,
-                  float *error_out) {
-    const real T = R(partial[3 * K + 1]), z2 = R(partial[3 * K]), lam = R(reg_coef);
+void orc_m_partial(const orc_model *m, const float *keypoints, const float *q, int32_t T,
+                   float *partial) {
+    const int n = 3 * m->nsite + 2;
+    real *s = (real *)calloc((size_t)n, sizeof(real));
+    m_partial_real(m, keypoints, q, T, s);
+    for (int i = 0; i < n; ++i) partial[i] = (float)s[i];
+    free(s);
+}
+
+static void m_finish_real(int32_t K, const real *partial, const float *initial_offsets,
+                          const float *is_regularized, float reg_coef, float *params_out,
+                          float *error_out) {
+    const real T = partial[3 * K + 1], z2 = partial[3 * K], lam = R(reg_coef);
     real ms = R(0), mm = R(0), reg = R(0);
     for (int i = 0; i < 3 * K; ++i) {
-        const real d = R(is_regularized[i]), s = R(partial[i]), m0 = R(initial_offsets[i]);
+        const real d = R(is_regularized[i]), s = partial[i], m0 = R(initial_offsets[i]);
         const real denom = T + lam * d;
         const real numer = s + lam * d * m0;
         /* no frame at all and an unregularised coordinate: keep the previous offset (the reference would divide 0 by 0) */
@@ -534,13 +542,23 @@ void orc_m_finish(int32_t K, const float *partial, const float *initial_offsets,
     if (error_out) *error_out = (float)((z2 - R(2) * ms + T * mm) + lam * reg);
 }
 
+void orc_m_finish(int32_t K, const float *partial, const float *initial_offsets,
+                  const float *is_regularized, float reg_coef, float *params_out,
+                  float *error_out) {
+    real *s = (real *)calloc((size_t)3 * K + 2, sizeof(real));
+    for (int i = 0; i < 3 * K + 2; ++i) s[i] = R(partial[i]);
+    m_finish_real(K, s, initial_offsets, is_regularized, reg_coef, params_out, error_out);
+    free(s);
+}
+
+/* partial and finish in one: in float32 the same bits as orc_m_finish on orc_m_partial's output. */
 void orc_m_opt(const orc_model *m, const float *keypoints, const float *q, int32_t T,
                const float *initial_offsets, const float *is_regularized, float reg_coef,
                float *params_out, float *error_out) {
-    float *partial = (float *)calloc((size_t)3 * m->nsite + 2, sizeof(float));
-    orc_m_partial(m, keypoints, q, T, partial);
-    orc_m_finish(m->nsite, partial, initial_offsets, is_regularized, reg_coef, params_out, error_out);
-    free(partial);
+    real *s = (real *)calloc((size_t)3 * m->nsite + 2, sizeof(real));
+    m_partial_real(m, keypoints, q, T, s);
+    m_finish_real(m->nsite, s, initial_offsets, is_regularized, reg_coef, params_out, error_out);
+    free(s);
 }
 
 

@@ -136,7 +136,8 @@ void orc_m_partial(const orc_model *m, const float *keypoints, const float *q, i
 void orc_m_finish(int32_t K, const float *partial, const float *initial_offsets,
                   const float *is_regularized, float reg_coef, float *params_out,
                   float *error_out);
-/* _m_opt = partial + finish. */
+/* _m_opt = partial + finish, the sums kept in the build's own precision in between (float32: the same bits as the two calls;
+ * the float64 twin does not round them to the float32 of `partial`). */
 void orc_m_opt(const orc_model *m, const float *keypoints, const float *q, int32_t T,
                const float *initial_offsets, const float *is_regularized, float reg_coef,
                float *params_out, float *error_out);

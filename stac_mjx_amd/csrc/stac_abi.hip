@@ -23,6 +23,7 @@ hipError_t launch_q_phase(const QArgs &a, const QInst &inst, int wpb, size_t lds
 hipError_t launch_q_phase_lm(const QArgs &a, const LmArgs &L, const QInst &inst, int wpb, size_t lds_bytes, hipStream_t s);
 hipError_t launch_fk(const FullModel &M, const float *qpos, int N, float *qn, float *xpos, float *xquat,
                      float *site_xpos, int normalize, hipStream_t s);
+int fk_max_slots();
 hipError_t launch_m_partial(const FullModel &M, const float *kp, const float *xpos, const float *xquat, int T,
                             float *contrib, float *partial, hipStream_t s);
 hipError_t launch_m_finish(int K, const float *partial, const float *m0, const float *dreg, float lam, float *out,
@@ -1142,11 +1143,23 @@ extern "C" int32_t stac_get_site_pos(const stac_model *m, float *out, void *stre
     return STAC_OK;
 }
 
+// fk_kernel holds the transforms that wait for a child further down the body list in LDS slots (build_fk_tables): a tree that
+// parks more of them at once than a workgroup's LDS holds is refused here, on the host, before anything is launched.
+static int fk_capacity(const stac_model *m, const char *who) {
+    const int cap = stac::fk_max_slots();
+    if (m->fk_nslots > cap)
+        return fail(STAC_ERR_CAPACITY, std::string(who) + ": the body tree keeps " + std::to_string(m->fk_nslots) +
+                                           " transforms parked at once (bodies with a child that does not follow them directly); "
+                                           "the kinematics kernel's LDS holds " + std::to_string(cap));
+    return STAC_OK;
+}
+
 static int fk_impl(const stac_model *mc, const float *qpos, int32_t N, float *qn, float *xpos, float *xquat,
                    float *site_xpos, int normalize, void *stream) {
     stac_model *m = const_cast<stac_model *>(mc);
     if (!m || !qpos || N < 0) return fail(STAC_ERR_INVALID, "stac_fk: bad argument");
     if (N == 0) return STAC_OK;
+    if (const int rc = fk_capacity(m, "stac_fk")) return rc;
     DeviceGuard dg(m);
     // (outputs the caller does not want are not written: the body transforms live in the kernel's LDS rows)
     HIP_TRY(launch_fk(m->full(), qpos, N, qn, xpos, xquat, site_xpos, normalize, (hipStream_t)stream));
@@ -1924,7 +1937,10 @@ extern "C" int32_t stac_m_phase_partial(const stac_model *m, const float *kp, co
     hipStream_t s = (hipStream_t)stream;
     const size_t nb = m->h.nbody;
     float *xpos = workspace, *xquat = workspace + (size_t)T * nb * 3, *contrib = workspace + (size_t)T * nb * 7;
-    if (T > 0) HIP_TRY(launch_fk(m->full(), q, T, nullptr, xpos, xquat, nullptr, 1, s));
+    if (T > 0) {
+        if (const int rc = fk_capacity(m, "stac_m_phase_partial")) return rc;
+        HIP_TRY(launch_fk(m->full(), q, T, nullptr, xpos, xquat, nullptr, 1, s));
+    }
     HIP_TRY(launch_m_partial(m->full(), kp, xpos, xquat, T, contrib, partial, s));
     return STAC_OK;
 }

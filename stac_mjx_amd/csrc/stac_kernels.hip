@@ -1975,11 +1975,17 @@ hipError_t launch_q_phase(const QArgs &a, const QInst &i, int wpb, size_t lds_by
     return hipErrorInvalidValue;
 }
 
+// LDS of an fk_kernel launch: the parking slots (7 words per lane each) and a staging row per lane; a workgroup may take the 160 KiB
+// of a CU, which is 83 slots.  The host refuses a tree that parks more at once by name (stac_abi.hip, fk_capacity) before it gets here.
+static size_t fk_lds_bytes(int nslots) { return ((size_t)std::max(nslots, 1) * 7 + kFkStride) * 64 * sizeof(float); }
+constexpr size_t kFkLdsCap = 160 * 1024;
+int fk_max_slots() { return (int)((kFkLdsCap / (64 * sizeof(float)) - kFkStride) / 7); }
+
 hipError_t launch_fk(const FullModel &M, const float *qpos, int N, float *qn, float *xpos, float *xquat,
                      float *site_xpos, int normalize, hipStream_t s) {
     if (N <= 0) return hipSuccess;
-    const size_t lds_bytes = ((size_t)std::max(M.fk_nslots, 1) * 7 + kFkStride) * 64 * sizeof(float);  // (rodent: 5.4 + 14.6 KB per wavefront)
-    if (lds_bytes > 160 * 1024) return hipErrorInvalidValue;  // (a tree with more than 83 open branch points)
+    const size_t lds_bytes = fk_lds_bytes(M.fk_nslots);  // (rodent: 5.4 + 14.6 KB per wavefront)
+    if (lds_bytes > kFkLdsCap) return hipErrorInvalidValue;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&fk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(fk_kernel, dim3((N + 63) / 64), dim3(64), lds_bytes, s, M, qpos, N, qn, xpos, xquat, site_xpos, normalize);

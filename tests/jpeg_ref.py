@@ -155,31 +155,36 @@ class _Bits:
             self.put((1 << (8 - self.n)) - 1, 8 - self.n)
 
 
-def _code_block(w, z, pred, dc, ac):
+def _lane_words(z, pred, dc, ac):
+    """The words of one coded block, one per coefficient that codes something (what one lane of the kernel forms):
+    ("dc", category, 0, bits, n), ("ac", symbol, ZRL codes in front, bits, n), ("eob", 0, 0, bits, n)."""
     d = int(z[0]) - pred
     s = abs(d).bit_length()
-    w.put(*dc[s])
-    if s:
-        w.put(d if d >= 0 else d - 1, s)
+    code, length = dc[s]
+    yield "dc", s, 0, (code << s) | ((d if d >= 0 else d - 1) & ((1 << s) - 1)), length + s
     run = 0
     for k in range(1, 64):
         v = int(z[k])
         if v == 0:
             run += 1
             continue
+        bits, n, chain = 0, 0, 0
         while run > 15:
-            w.put(*ac[0xF0])
+            code, length = ac[0xF0]
+            bits, n, chain = (bits << length) | code, n + length, chain + 1
             run -= 16
         s = abs(v).bit_length()
-        w.put(*ac[(run << 4) | s])
-        w.put(v if v >= 0 else v - 1, s)
+        code, length = ac[(run << 4) | s]
+        bits = (((bits << length) | code) << s) | ((v if v >= 0 else v - 1) & ((1 << s) - 1))
+        yield "ac", (run << 4) | s, chain, bits, n + length + s
         run = 0
     if run:
-        w.put(*ac[0x00])
+        yield ("eob", 0, 0) + ac[0x00]
 
 
-def scan(rgb, quality, restart_mcus=0):
-    """The entropy-coded data between SOS and EOI."""
+def _walk(rgb, quality, restart_mcus):
+    """The scan in stream order: ("rst", k) where a restart marker goes, ("mcu",) in front of every MCU and
+    ("block", table, z, pred) for every coded block (z: 64 quantised coefficients in zigzag order, pred: its DC prediction)."""
     H, W, _ = rgb.shape
     Y, Cb, Cr = planes(np.asarray(rgb))
     mw, mh = (W + 15) // 16, (H + 15) // 16
@@ -194,18 +199,15 @@ def scan(rgb, quality, restart_mcus=0):
     cy, ccb, ccr = coefficients(Y, q[0]), coefficients(Cb, q[1]), coefficients(Cr, q[1])
     real_y = ((W + 7) // 8, (H + 7) // 8)  # real blocks per row / column of the component; beyond them: dummy blocks
     real_c = (((W + 1) // 2 + 7) // 8, ((H + 1) // 2 + 7) // 8)
-    dc = [_codes(DC_LUMA), _codes(DC_CHROMA)]
-    ac = [_codes(AC_LUMA), _codes(AC_CHROMA)]
-    w = _Bits()
     pred, n, rst = [0, 0, 0], 0, 0
     for my in range(mh):
         for mx in range(mw):
             if restart_mcus and n and n % restart_mcus == 0:
-                w.flush()
-                w.out.extend([0xFF, 0xD0 + rst])
+                yield "rst", rst
                 rst = (rst + 1) & 7
                 pred = [0, 0, 0]
             n += 1
+            yield ("mcu",)
             blocks = [(0, cy, 2 * mx + bx, 2 * my + by, real_y) for by in range(2) for bx in range(2)]
             blocks += [(1, ccb, mx, my, real_c), (2, ccr, mx, my, real_c)]
             for comp, coef, X, Yb, real in blocks:
@@ -214,8 +216,23 @@ def scan(rgb, quality, restart_mcus=0):
                 else:  # not transformed: AC 0, DC = the DC coded just before
                     z = np.zeros(64, np.int64)
                     z[0] = pred[comp]
-                _code_block(w, z, pred[comp], dc[min(comp, 1)], ac[min(comp, 1)])
+                yield "block", min(comp, 1), z, pred[comp]
                 pred[comp] = int(z[0])
+
+
+def scan(rgb, quality, restart_mcus=0):
+    """The entropy-coded data between SOS and EOI."""
+    dc = [_codes(DC_LUMA), _codes(DC_CHROMA)]
+    ac = [_codes(AC_LUMA), _codes(AC_CHROMA)]
+    w = _Bits()
+    for item in _walk(np.asarray(rgb), quality, restart_mcus):
+        if item[0] == "rst":
+            w.flush()
+            w.out.extend([0xFF, 0xD0 + item[1]])
+        elif item[0] == "block":
+            _, t, z, pred = item
+            for _, _, _, bits, n in _lane_words(z, pred, dc[t], ac[t]):
+                w.put(bits, n)
     w.flush()
     return bytes(w.out)
 
@@ -259,3 +276,250 @@ def images():
     s[40:60, 100:150] = (0, 255, 255)
     out["shapes160x64"] = s
     return out
+
+
+# ---- what a stream exercises ---------------------------------------------------------------------------------------------
+LONG_WORD = 34  # a word of 34 bits or more reaches a third 32-bit word at some bit position
+
+
+def stats(rgb, quality, restart_mcus=0):
+    """What the scan of `encode(rgb, quality, restart_mcus)` exercises.  {"luma": t, "chroma": t, "mcu_bits": the most bits in
+    one MCU, "intervals": [the unstuffed bytes of every restart interval, padded]}, t = {"dc": set of DC categories, "ac": set of
+    AC symbols, "zrl": set of ZRL chain lengths in front of a symbol (0 included), "eob" / "no_eob": a block ended with / without
+    EOB, "longest": the longest word in bits, "long_at": set of (bit position mod 32 inside the interval's unstuffed stream) of
+    the words of LONG_WORD bits or more}."""
+    dc = [_codes(DC_LUMA), _codes(DC_CHROMA)]
+    ac = [_codes(AC_LUMA), _codes(AC_CHROMA)]
+    tabs = [dict(dc=set(), ac=set(), zrl=set(), eob=False, no_eob=False, longest=0, long_at=set()) for _ in range(2)]
+    intervals, acc, pos, mcu_start, mcu_bits = [], 0, 0, 0, 0
+
+    def close():
+        pad = -pos % 8
+        intervals.append((((acc << pad) | ((1 << pad) - 1)).to_bytes((pos + pad) // 8, "big")))
+
+    for item in _walk(np.asarray(rgb), quality, restart_mcus):
+        if item[0] == "rst":
+            mcu_bits = max(mcu_bits, pos - mcu_start)
+            close()
+            acc, pos, mcu_start = 0, 0, 0
+        elif item[0] == "mcu":
+            mcu_bits = max(mcu_bits, pos - mcu_start)
+            mcu_start = pos
+        else:
+            _, t, z, pred = item
+            T, ended = tabs[t], False
+            for kind, sym, chain, bits, n in _lane_words(z, pred, dc[t], ac[t]):
+                if kind == "dc":
+                    T["dc"].add(sym)
+                elif kind == "ac":
+                    T["ac"].add(sym)
+                    T["zrl"].add(chain)
+                else:
+                    ended = True
+                T["longest"] = max(T["longest"], n)
+                if n >= LONG_WORD:
+                    T["long_at"].add(pos % 32)
+                acc, pos = (acc << n) | bits, pos + n
+            T["eob" if ended else "no_eob"] = True
+    mcu_bits = max(mcu_bits, pos - mcu_start)
+    close()
+    return {"luma": tabs[0], "chroma": tabs[1], "mcu_bits": mcu_bits, "intervals": intervals}
+
+
+def restuffed(st):
+    """The scan bytes from stats()'s intervals: stuffing and restart markers put back (ties stats() to scan())."""
+    return b"".join((b"" if k == 0 else bytes([0xFF, 0xD0 + (k - 1) % 8])) + iv.replace(b"\xff", b"\xff\x00")
+                    for k, iv in enumerate(st["intervals"]))
+
+
+# ---- edge images ------------------------------------------------------------------------------------------------------------
+_C = np.array([[(0.5 if k else np.sqrt(0.125)) * np.cos((2 * x + 1) * k * np.pi / 16) for x in range(8)] for k in range(8)])
+BLUE, YELLOW, RED, CYAN = (0, 0, 255), (255, 255, 0), (255, 0, 0), (0, 255, 255)
+
+
+def idct(coef):
+    """[..., 8, 8] orthonormal DCT coefficients (natural order) -> samples, in floating point."""
+    return _C.T @ np.asarray(coef, np.float64) @ _C
+
+
+def _grey(y):
+    return np.repeat(np.clip(np.rint(y), 0, 255).astype(np.uint8)[..., None], 3, -1)
+
+
+def _tile(blocks):
+    """[by, bx, 8, 8] -> [8 by, 8 bx]."""
+    by, bx = blocks.shape[:2]
+    return blocks.swapaxes(1, 2).reshape(8 * by, 8 * bx)
+
+
+def _along(pattern, c0, c1):
+    """Colours between c0 and c1 (pattern -127.5 .. 127.5, 0 = half way) at 2 x 2 pixels per sample: one chroma component
+    swings over its whole range while the picture stays inside the RGB cube."""
+    t = np.clip(0.5 + np.asarray(pattern) / 255.0, 0, 1)
+    t = np.repeat(np.repeat(t, 2, 0), 2, 1)[..., None]
+    return np.rint(np.asarray(c0, np.float64) * (1 - t) + np.asarray(c1, np.float64) * t).astype(np.uint8)
+
+
+def _tail_block(amplitude):
+    c = np.zeros((8, 8))
+    c[7, 7] = amplitude
+    return idct(c)
+
+
+def luma_tail(by, bx):
+    """Grey, every block the (7, 7) basis function at amplitude 520: at quality 92 one coefficient of size 6 behind 62 zeros."""
+    return _grey(_tile(np.broadcast_to(_tail_block(520.0), (by, bx, 8, 8))) + 128)
+
+
+def chroma_tail(my, mx):
+    """Y = 128, Cb the (7, 7) basis function at amplitude 300 (one block per MCU), Cr = 128."""
+    cb = np.rint(_tile(np.broadcast_to(_tail_block(300.0), (my, mx, 8, 8))))
+    cb = np.repeat(np.repeat(cb, 2, 0), 2, 1)
+    rgb = np.stack([np.full_like(cb, 128.0), 128 - 0.344136 * cb, 128 + 1.772 * cb], -1)
+    return np.clip(np.rint(rgb), 0, 255).astype(np.uint8)
+
+
+def _behind_noise(tail, n_noise, seed):
+    """One row of MCUs: n_noise MCUs of noise, then the tail image's MCUs (their words then start at other bit positions)."""
+    out = np.concatenate([np.random.default_rng(seed).integers(0, 256, (tail.shape[0], 16 * n_noise, 3), dtype=np.uint8), tail], 1)
+    return np.ascontiguousarray(out)
+
+
+def _magnitude(rng, size):
+    return int(rng.integers(1 << (size - 1), 1 << size)) * int(rng.choice([-1, 1]))
+
+
+def sparse_blocks(rng, by, bx):
+    """[by, bx, 8, 8] samples about 0: per block a DC in +-1000 and 1-4 AC coefficients at random zigzag positions, their
+    magnitudes drawn per size category 1..10 (orthonormal scale: the quantised values at quality 100)."""
+    coef = np.zeros((by, bx, 64))
+    for b in coef.reshape(-1, 64):
+        b[0] = rng.integers(-1000, 1001)
+        for k in rng.choice(np.arange(1, 64), int(rng.integers(1, 5)), replace=False):
+            b[ZIGZAG[k]] = _magnitude(rng, int(rng.integers(1, 11)))
+    return idct(coef.reshape(by, bx, 8, 8))
+
+
+def symbol_blocks(rng):
+    """[20, 16, 8, 8] samples about 0 that aim at every AC symbol (run, size 1..10) twice: as the first coefficient of a block
+    (at zigzag run + 1), and behind a small coefficient at a random place.  The magnitude sits low in its category, since a
+    big coefficient clips; what comes out is what stats() says."""
+    coef = np.zeros((320, 64))
+    for run in range(16):
+        for size in range(1, 11):
+            m = max(1, int(round((1 << (size - 1)) * (1.12 if size > 8 else 1.3)))) * int(rng.choice([-1, 1]))
+            coef[run * 10 + size - 1, ZIGZAG[run + 1]] = m
+            b = coef[160 + run * 10 + size - 1]
+            k = int(rng.integers(1, 63 - run))
+            b[ZIGZAG[k]] = rng.choice([-2, 2])
+            b[ZIGZAG[k + run + 1]] = m
+    return idct(coef.reshape(20, 16, 8, 8))
+
+
+def _chroma_image(blocks, rng):
+    """Every block one MCU: the pattern along blue-yellow (Cb) or red-cyan (Cr), chosen per MCU."""
+    rows = []
+    for row in blocks:
+        rows.append(np.concatenate([_along(b, *((YELLOW, BLUE) if rng.integers(2) else (CYAN, RED))) for b in row], 1))
+    return np.ascontiguousarray(np.concatenate(rows, 0))
+
+
+def _columns(colours, width, height=32):
+    out = np.zeros((height, width, 3), np.uint8)
+    for k in range(width // 16):
+        out[:, 16 * k:16 * k + 16] = colours[k % len(colours)]
+    return out
+
+
+def stuffing_candidate(seed):
+    """(image, quality) number `seed` of the search for streams with 0xFF bytes in particular places: noise or saturated
+    noise of a random size below 65 x 65 at quality 95, 98 or 100."""
+    rng = np.random.default_rng(seed)
+    W, H = int(rng.integers(17, 65)), int(rng.integers(17, 65))
+    img = rng.integers(0, 256, (H, W, 3), dtype=np.uint8) if seed % 2 == 0 else (rng.integers(0, 2, (H, W, 3)) * 255).astype(np.uint8)
+    return img, int(rng.choice([100, 98, 95]))
+
+
+def stuffing(st):
+    """Which byte-stuffing situations the unstuffed intervals of a stats() hold: "pair" (two consecutive 0xFF), "last" (0xFF
+    as the last byte of an interval), "pos0".."pos3" (0xFF at that byte of a 32-bit word), "round" (0xFF as the last byte of
+    a pack round of 1024 bytes)."""
+    out = set()
+    for iv in st["intervals"]:
+        ff = np.flatnonzero(np.frombuffer(iv, np.uint8) == 255)
+        if len(ff):
+            out |= {f"pos{k}" for k in set(ff % 4)}
+            out |= {"pair"} if (np.diff(ff) == 1).any() else set()
+            out |= {"last"} if ff[-1] == len(iv) - 1 else set()
+            out |= {"round"} if (ff % 1024 == 1023).any() else set()
+    return out
+
+
+def edge_images():
+    """name -> ([H, W, 3] uint8, quality): inputs that reach what images() does not (tests/test_jpeg_host.py says what each
+    kind must emit): words of 55 and 51 bits behind three ZRL codes at every bit position, nearly every AC symbol, DC
+    categories 10 and 11, 0xFF bytes at the places where byte stuffing can go wrong."""
+    out = {"luma_tail": (luma_tail(2, 4), 92), "chroma_tail": (chroma_tail(2, 2), 93)}
+    for seed in range(3):  # the tail words at all 32 bit positions
+        out[f"luma_tail_behind_noise{seed}"] = (_behind_noise(luma_tail(2, 16), 1 + seed, seed), 92)
+        out[f"chroma_tail_behind_noise{seed}"] = (_behind_noise(chroma_tail(1, 22), 1 + seed, seed), 92)
+    rng = np.random.default_rng(0)
+    out["sparse_luma"] = (_grey(_tile(sparse_blocks(rng, 12, 12)) + 128), 100)
+    out["sparse_chroma"] = (_chroma_image(sparse_blocks(rng, 8, 8), rng), 100)
+    out["symbols_luma"] = (_grey(_tile(symbol_blocks(rng)) + 128), 100)
+    out["symbols_chroma"] = (_chroma_image(symbol_blocks(rng), rng), 100)
+    for q in (100, 90):  # DC differences of categories 11 and 10, in both tables
+        out[f"dc_black_white_q{q}"] = (_columns([(0, 0, 0), (255, 255, 255)], 64), q)
+        out[f"dc_colours_q{q}"] = (_columns([BLUE, YELLOW, RED, CYAN], 128), q)
+    out["stuffing_pair_last"] = stuffing_candidate(31)  # 43 x 60: 0xFF 0xFF, 0xFF at the end of an interval (R = 1)
+    out["stuffing_round"] = stuffing_candidate(27)  # 17 x 50: 0xFF as byte 1023 of an interval (R = 8 and more than all MCUs)
+    return out
+
+
+def restart_cases(W, H):
+    """The restart intervals of the parity tests: 1, 3, 8, one MCU row, more than all MCUs (DRI present, no marker)."""
+    mw, mh = (W + 15) // 16, (H + 15) // 16
+    return (1, 3, 8, mw, mw * mh + 5)
+
+
+# ---- seeded random cases (tests/test_jpeg_host.py, tests/test_gpu_jpeg.py, tests/fuzz_jpeg.py) ----------------------------------
+FAMILIES = ("noise", "saturated", "smooth", "shapes", "sparse")
+
+
+def content(rng, kind, H, W):
+    """[H, W, 3] uint8 of one family."""
+    if kind == "noise":
+        return rng.integers(0, 256, (H, W, 3), dtype=np.uint8)
+    if kind == "saturated":
+        return (rng.integers(0, 2, (H, W, 3)) * 255).astype(np.uint8)
+    if kind == "smooth":
+        yy, xx = np.mgrid[0:H, 0:W]
+        a = rng.integers(1, 8, 6)
+        return np.stack([(xx * a[0] + yy * a[1]) % 256, (xx * a[2] + yy * a[3]) % 256, (xx * a[4] + yy * a[5]) % 256], -1).astype(np.uint8)
+    if kind == "shapes":  # render-like: a flat background, a few flat rectangles
+        out = np.empty((H, W, 3), np.uint8)
+        out[:] = rng.integers(0, 256, 3) * int(rng.integers(2))
+        for _ in range(int(rng.integers(1, 6))):
+            y, x = int(rng.integers(H)), int(rng.integers(W))
+            out[y:y + int(rng.integers(1, H + 1)), x:x + int(rng.integers(1, W + 1))] = rng.integers(0, 256, 3)
+        return out
+    if kind == "sparse":
+        by, bx = (H + 7) // 8, (W + 7) // 8
+        blocks = sparse_blocks(rng, by, bx)
+        if rng.integers(2):
+            return np.ascontiguousarray(_grey(_tile(blocks) + 128)[:H, :W])
+        return np.ascontiguousarray(_chroma_image(blocks[:(by + 1) // 2, :(bx + 1) // 2], rng)[:H, :W])
+    raise ValueError(kind)
+
+
+def fuzz_case(seed, max_side=96):
+    """Case number `seed`: {"kind", "frames" [N, H, W, 3] (N 1..4), "quality" 1..100, "R" (1, small, one MCU row, more than
+    all MCUs, 65535), "offset": the odd byte offset (1 or 3) at which the GPU tests place the frames}."""
+    rng = np.random.default_rng(1000 + seed)
+    kind = FAMILIES[seed % len(FAMILIES)]
+    side = lambda: int(rng.integers(1, max_side + 1) if rng.integers(4) else rng.choice([1, 2, 7, 8, 9, 15, 16, 17, 31, 32, 33]))
+    W, H, N = side(), side(), int(rng.integers(1, 5))
+    mw, mh = (W + 15) // 16, (H + 15) // 16
+    R = int(rng.choice([1, 2, int(rng.integers(1, 20)), mw, mw * mh, mw * mh + 5, 65535]))
+    frames = np.stack([content(rng, kind, H, W) for _ in range(N)])
+    return dict(kind=kind, frames=frames, quality=int(rng.integers(1, 101)), R=R, offset=int(rng.choice([1, 3])))

@@ -1,5 +1,7 @@
 """The JPEG path on the host (no GPU): the numpy restatement tests/jpeg_ref.py equals Pillow byte for byte (so Pillow's bytes can
-be the yardstick of tests/test_gpu_jpeg.py), the library's header equals Pillow's, the entry points are exported and refuse bad
+be the yardstick of tests/test_gpu_jpeg.py) on the parity images, the edge images and a seeded sweep; the edge images make the
+streams that they are there for (jpeg_ref.stats: long words at every bit position, three ZRL codes, every DC category, all but
+a listed few AC symbols, 0xFF bytes where stuffing can go wrong); the library's header equals Pillow's, the entry points are exported and refuse bad
 arguments, Stac.render refuses bad encoder arguments before any device work, and write_avi takes pre-encoded frames alone."""
 
 import ctypes as C
@@ -26,6 +28,96 @@ def test_restatement_equals_pillow(name):
         for R in (0, 1, 3, 8):  # 0: plain save, no DRI
             got, want = jpeg_ref.encode(img, q, R), jpeg_ref.pillow(img, q, R)
             assert got == want, (name, q, R, len(got), len(want))
+
+
+EDGE = jpeg_ref.edge_images()
+# AC symbols (run << 4 | size, size 1..10) that no parity or edge image emits.  A long run in front of a coefficient of 9 or 10
+# bits needs a high-frequency amplitude that 8-bit pixels (chrominance: the RGB cube) do not hold.  The issue's caps: 8 and 34.
+MISSING_AC = {"luma": [0x5A, 0x7A, 0xC9, 0xE7, 0xE9, 0xEA], "chroma": [0xC8, 0xC9, 0xCA, 0xE4, 0xEA]}
+
+
+@pytest.mark.parametrize("name", list(EDGE))
+def test_restatement_equals_pillow_on_edge_images(name):
+    img, q = EDGE[name]
+    for R in (0,) + jpeg_ref.restart_cases(img.shape[1], img.shape[0]):
+        got, want = jpeg_ref.encode(img, q, R), jpeg_ref.pillow(img, q, R)
+        assert got == want, (name, q, R, len(got), len(want))
+        assert jpeg_ref.restuffed(jpeg_ref.stats(img, q, R)) == jpeg_ref.scan(img, q, R), (name, R)  # stats() sees that stream
+
+
+def _union(stats):
+    out = {k: dict(dc=set(), ac=set(), zrl=set(), eob=False, no_eob=False, longest=0, long_at=set()) for k in ("luma", "chroma")}
+    for st in stats:
+        for k, u in out.items():
+            for f in ("dc", "ac", "zrl", "long_at"):
+                u[f] |= st[k][f]
+            u["eob"], u["no_eob"], u["longest"] = u["eob"] or st[k]["eob"], u["no_eob"] or st[k]["no_eob"], max(u["longest"], st[k]["longest"])
+    return out
+
+
+@pytest.fixture(scope="module")
+def exercised():
+    """stats() of every case that tests/test_gpu_jpeg.py gives the encoder from images() and edge_images(): name -> [stats]."""
+    out = {}
+    for name, img in IMAGES.items():
+        out[name] = [jpeg_ref.stats(img, q, R) for q in QUALITIES for R in jpeg_ref.restart_cases(img.shape[1], img.shape[0])]
+    for name, (img, q) in EDGE.items():
+        out[name] = [jpeg_ref.stats(img, q, R) for R in jpeg_ref.restart_cases(img.shape[1], img.shape[0])]
+    return out
+
+
+def test_tail_images_make_the_long_words(exercised):
+    luma, chroma = exercised["luma_tail"][0]["luma"], exercised["chroma_tail"][0]["chroma"]
+    assert luma["ac"] == {0xE6} and luma["zrl"] == {3} and luma["longest"] == 55 and luma["no_eob"] and not luma["eob"]
+    assert 0xE5 in chroma["ac"] and 3 in chroma["zrl"] and chroma["longest"] == 51 and chroma["no_eob"]
+    # behind noise, one interval (R more than all MCUs): a word that needs a third 32-bit word at every bit position, 0 included
+    for table in ("luma", "chroma"):
+        at = set()
+        for seed in range(3):
+            st = exercised[f"{table}_tail_behind_noise{seed}"][-1]
+            assert len(st["intervals"]) == 1
+            at |= st[table]["long_at"]
+        assert at == set(range(32)), (table, sorted(set(range(32)) - at))
+
+
+def test_what_the_images_exercise(exercised):
+    u = _union(st for sts in exercised.values() for st in sts)
+    for table in ("luma", "chroma"):
+        assert u[table]["dc"] == set(range(12)), table
+        assert {1, 2, 3} <= u[table]["zrl"], table
+        assert u[table]["eob"] and u[table]["no_eob"], table
+    assert u["luma"]["longest"] >= 54 and u["chroma"]["longest"] >= 50
+    assert max(st["mcu_bits"] for sts in exercised.values() for st in sts) > 4096  # an MCU over many staged words
+    stuffing = set().union(*(jpeg_ref.stuffing(st) for sts in exercised.values() for st in sts))
+    assert stuffing == {"pair", "last", "pos0", "pos1", "pos2", "pos3", "round"}
+    # the seeded stuffing images hold them on their own
+    assert {"pair", "last"} <= jpeg_ref.stuffing(exercised["stuffing_pair_last"][0])  # R = 1
+    assert "round" in jpeg_ref.stuffing(exercised["stuffing_round"][-1])  # one interval
+
+
+def test_ac_symbols_missing_are_the_listed_ones(exercised):
+    u = _union(st for sts in exercised.values() for st in sts)
+    assert len(MISSING_AC["luma"]) <= 8 and len(MISSING_AC["chroma"]) <= 34
+    for table in ("luma", "chroma"):
+        missing = sorted(set((r << 4) | s for r in range(16) for s in range(1, 11)) - u[table]["ac"])
+        assert missing == MISSING_AC[table], (table, [hex(m) for m in missing])
+
+
+def test_restatement_equals_pillow_on_a_seeded_sweep():
+    """The yardstick of the GPU fuzz is itself checked: quality 1..100, sides below 64, R 0..19, every content family."""
+    n = 0
+    for seed in range(300):
+        rng = np.random.default_rng(seed)
+        kind = jpeg_ref.FAMILIES[seed % len(jpeg_ref.FAMILIES)]
+        img = jpeg_ref.content(rng, kind, int(rng.integers(1, 64)), int(rng.integers(1, 64)))
+        q, R = int(rng.integers(1, 101)), int(rng.integers(0, 20))
+        assert jpeg_ref.encode(img, q, R) == jpeg_ref.pillow(img, q, R), (seed, kind, img.shape, q, R)
+        n += 1
+    for seed in range(40):  # and the cases of the GPU fuzz as they are
+        c = jpeg_ref.fuzz_case(seed)
+        for f in c["frames"]:
+            assert jpeg_ref.encode(f, c["quality"], c["R"]) == jpeg_ref.pillow(f, c["quality"], c["R"]), (seed, c["kind"])
+    assert n == 300
 
 
 def _sos_end(data):

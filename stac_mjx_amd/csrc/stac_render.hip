@@ -185,6 +185,11 @@ __device__ float intersect(const float *r, const float *o, const float *d, float
         const float w[3] = {R[2], R[5], R[8]};
         const float hl = sz[1], rad = sz[0];
         const float oz = dot3(oc, w), dz = dot3(d, w);
+        // an origin inside the capsule does not see it: nearer to the axis point at oz clamped to the segment than rad
+        const float ozc = fminf(fmaxf(oz, -hl), hl);
+        const float oq[3] = {oc[0] - w[0] * ozc, oc[1] - w[1] * ozc, oc[2] - w[2] * ozc};
+        const float in2 = rad * rad - dot3(oq, oq);
+        if (in2 > 0.0f) return -1.0f;
         const float op[3] = {oc[0] - w[0] * oz, oc[1] - w[1] * oz, oc[2] - w[2] * oz};
         const float dp[3] = {d[0] - w[0] * dz, d[1] - w[1] * dz, d[2] - w[2] * dz};
         const float a = dot3(dp, dp);

@@ -1,7 +1,8 @@
 """Scenes and shared helpers of the render tests (tests/test_render_host.py, tests/test_gpu_render.py and their mesh
 siblings): the rodent of the reference's fixtures with the stored demo_viz fit, the synth model, seeded random scenes of
 every primitive type, the scenes whose pictures are pinned, the checker (tests/tools/build_render_ref.py) and the
-comparisons against it."""
+comparisons against it; and the constructed scenes on which checker and kernel are held to tests/render_rule.py
+(``rule_cases``: every type from outside and from inside, ties, degenerate segments, lights) with that comparison."""
 
 from __future__ import annotations
 
@@ -237,3 +238,335 @@ def assert_same(got, want, what=""):
             g, w = g.view(np.uint32), w.view(np.uint32)  # bit for bit, +inf included
         bad = np.argwhere(g != w)
         assert bad.size == 0, f"{what} {name}: {len(bad)} values differ, first at {bad[:3].tolist()}: {g[tuple(bad[0])]} vs {w[tuple(bad[0])]}"
+
+
+# ---- the scenes held to tests/render_rule.py (tests/test_render_rule_host.py, tests/test_gpu_render_rule.py) ---------------
+RULE_SIZES = ((96, 64), (97, 61))  # a partial last tile in both directions
+RULE_NBODY = 67  # the rodent's body count: the GPU tests create their scenes on its engine
+TAN45 = math.tan(math.radians(45) / 2)
+_f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32)
+
+
+class RuleCase:
+    """One scene of the rule tests: ``args`` is the argument list of ``RenderRef.render`` up to ``tan_half_fovy`` (W and H
+    follow).  ``single``: every image shows one primitive (the cap on excluded pixels then counts hit pixels); ``hidden``:
+    per frame the id of the solid that holds the camera and must not be seen (the other frames: None)."""
+
+    def __init__(self, name, t, xpos, xquat, kp, markers, show, cams, single=False, hidden=None, tanh=TAN45):
+        self.name, self.single, self.hidden = name, single, hidden
+        self.args = (t, xpos.shape[1], _f32(xpos), _f32(xquat), kp, markers, show, _f32(cams), tanh)
+
+
+def rule_tables(types, body, size, pos, quat, rgb, flags, rgb2=None, tex=None, kp_rgb=(), lights=((0, 0, -1),),
+                diffuse=((0.7, 0.7, 0.7),), marker_radius=0.01, segment_radius=0.002):
+    P = len(types)
+    one = lambda a: np.concatenate([np.reshape(a, (-1, 3)), np.ones((len(a), 1))], 1) if len(a) else np.zeros((0, 4))
+    return dict(
+        prim_type=np.ascontiguousarray(types, np.int32), prim_body=np.ascontiguousarray(body, np.int32),
+        prim_flags=np.ascontiguousarray(flags, np.int32), prim_size=_f32(np.reshape(size, (P, 3))),
+        prim_pos=_f32(np.reshape(pos, (P, 3))), prim_quat=_f32(np.reshape(quat, (P, 4))), prim_rgba=_f32(one(rgb)),
+        prim_rgb2=_f32(np.zeros((P, 3)) if rgb2 is None else rgb2), prim_texrepeat=_f32(np.ones((P, 2)) if tex is None else tex),
+        kp_rgba=_f32(one(kp_rgb)), marker_rgba=_f32([0, 0, 0, 1]), segment_rgba=_f32([1, 0, 0, 1]),
+        marker_radius=np.float32(marker_radius), segment_radius=np.float32(segment_radius),
+        light_dir=_f32(np.reshape(lights, (-1, 3))), light_diffuse=_f32(np.reshape(diffuse, (-1, 3))),
+        head_ambient=_f32([0.1, 0.1, 0.1]), head_diffuse=_f32([0.4, 0.4, 0.4]), alpha=np.float32(0.3),
+        background=_f32([0.1, 0.1, 0.12]), names=[f"p{i}" for i in range(P)],
+    )
+
+
+def _rot(q):
+    from render_rule import quat_matrix
+
+    return quat_matrix(np.asarray(q, np.float32))
+
+
+def _still_bodies(n_frames, nbody):
+    xquat = np.zeros((n_frames, nbody, 4))
+    xquat[..., 0] = 1.0
+    return np.zeros((n_frames, nbody, 3)), xquat
+
+
+OUTSIDE_KINDS = ("plane", "plane_checker", "plane_checker_texuniform", "sphere", "capsule", "ellipsoid", "cylinder", "box")
+
+
+def outside_case(kind, nbody=RULE_NBODY):
+    """Eight primitives of one type with anisotropic sizes, primitive k on body k + 1; frame f shows primitive f at a random
+    pose from a random side (a plane from its +z side) and has the others behind the camera.  Capsule and cylinder: frame 6
+    looks along the axis of a turned solid, frame 7 along the axis of an axis-aligned one, where the centre pixel of an
+    odd-sized image has a direction exactly parallel to the axis (the side term's a == 0)."""
+    rng = np.random.default_rng(100 + OUTSIDE_KINDS.index(kind))
+    n = 8
+    ty = {"plane": 0, "plane_checker": 0, "plane_checker_texuniform": 0, "sphere": 2, "capsule": 3, "ellipsoid": 4,
+          "cylinder": 5, "box": 6}[kind]
+    size = rng.uniform(0.04, 0.15, size=(n, 3))
+    if ty == 0:
+        size[:, :2] = rng.uniform(0.2, 0.6, size=(n, 2))
+    if ty in (3, 5):
+        size[:, 1] = rng.uniform(0.05, 0.2, size=n)
+    flags = np.full(n, {"plane_checker": 2, "plane_checker_texuniform": 6}.get(kind, 0))
+    pos, quat = rng.uniform(-0.05, 0.05, size=(n, 3)), _unit_quat(rng, n)
+    xpos, xquat = _still_bodies(n, nbody)
+    cams = np.zeros((n, 12), np.float32)
+    axis_view = ty in (3, 5)
+    if axis_view:
+        pos[7], quat[7] = 0.0, [1, 0, 0, 0]
+    for f in range(n):
+        xpos[f, f + 1], xquat[f, f + 1] = rng.uniform(-0.1, 0.1, 3), _unit_quat(rng, 1)[0]
+        if axis_view and f == 7:
+            xpos[f, f + 1], xquat[f, f + 1] = 0.0, [1, 0, 0, 0]
+        Rb = _rot(xquat[f, f + 1])
+        R = Rb @ _rot(quat[f])
+        c = _f32(xpos[f, f + 1]).astype(np.float64) + Rb @ _f32(pos[f]).astype(np.float64)
+        brad = {0: np.hypot(*size[f, :2]), 2: size[f, 0], 3: size[f, 0] + size[f, 1], 4: size[f].max(),
+                5: np.hypot(*size[f, :2]), 6: np.linalg.norm(size[f])}[ty]
+        D = brad / rng.uniform(0.22, 0.32)
+        side = rng.normal(size=3)
+        if ty == 0:  # within 60 degrees of the plane's normal
+            nz = R[:, 2] / np.linalg.norm(R[:, 2])
+            tang = np.cross(nz, side)
+            a = rng.uniform(0.0, math.radians(60))
+            side = nz * math.cos(a) + tang / np.linalg.norm(tang) * math.sin(a)
+        side /= np.linalg.norm(side)
+        if axis_view and f == 7:
+            cams[f] = np.concatenate([[0, 0, D], np.eye(3).reshape(9)])
+        else:
+            if axis_view and f == 6:
+                side = R[:, 2] / np.linalg.norm(R[:, 2])
+            cams[f] = look_at(c + D * side, c, up=(0.2, 0.3, 0.9))
+        back = cams[f, 3:].astype(np.float64).reshape(3, 3)[:, 2]
+        for k in range(n):
+            if k != f:
+                xpos[f, k + 1] = cams[f, :3] + back * (20.0 + 2.0 * k)
+    t = rule_tables([ty] * n, np.arange(1, n + 1), size, pos, quat, rng.uniform(0.2, 1.0, (n, 3)), flags,
+                    rgb2=rng.uniform(0.0, 1.0, (n, 3)), tex=rng.uniform(1.0, 4.0, (n, 2)),
+                    lights=((0, 0, -1), (0.6, 0, -0.8)), diffuse=((0.5, 0.5, 0.5), (0.3, 0.2, 0.1)))
+    return RuleCase(f"outside_{kind}", t, xpos, xquat, None, None, False, cams, single=True)
+
+
+INSIDE_KINDS = ("sphere", "capsule", "ellipsoid", "cylinder", "box")
+CAPSULE_INSIDE_VIEWS = {  # frame -> what the view is (r = 0.05, hl = 0.2)
+    0: "centre, along the axis", 1: "centre, across the axis",
+    2: "cylindrical part outside both cap spheres, along the axis", 3: "cylindrical part outside both cap spheres, across the axis",
+    4: "inside a cap sphere beyond the segment's end, towards the other end", 5: "inside a cap sphere beyond the segment's end, outwards",
+    6: "inside a cap sphere within the segment, towards the other end",
+}
+
+
+def inside_views(kind):
+    """(size, [(origin, direction)]) in the solid's own frame: the camera inside the solid."""
+    if kind == "sphere":
+        r = 0.11
+        return [r, 0, 0], [((0, 0, 0), (0.3, -0.5, 0.8)), ((0.9 * r, 0, 0), (1, 0.1, 0)), ((0, -0.9 * r, 0), (0.1, 1, 0.2))]
+    if kind == "capsule":
+        r, hl = 0.05, 0.2
+        return [r, hl, 0], [((0, 0, 0), (0, 0, 1)), ((0, 0, 0), (1, 0, 0)), ((0.5 * r, 0, 0.3 * hl), (0, 0, 1)),
+                            ((0.5 * r, 0, 0.3 * hl), (0, 1, 0.1)), ((0, 0, hl + 0.5 * r), (0, 0, -1)),
+                            ((0, 0, hl + 0.5 * r), (0.3, 0, 1)), ((0, 0.3 * r, hl - 0.5 * r), (0, 0, -1))]
+    if kind == "ellipsoid":
+        s = (0.06, 0.1, 0.18)
+        return list(s), [((0, 0, 0), (0.5, 0.5, 0.7)), ((0, 0, 0.9 * s[2]), (0, 0, 1)), ((0, 0, 0.9 * s[2]), (0, 0.1, -1)),
+                         ((0.9 * s[0], 0, 0), (1, 0, 0))]
+    if kind == "cylinder":
+        r, hl = 0.06, 0.15
+        return [r, hl, 0], [((0, 0, 0), (0, 0, 1)), ((0, 0, 0), (1, 0, 0)), ((0.3 * r, 0, 0.9 * hl), (0, 0, 1)),
+                            ((0.3 * r, 0, 0.9 * hl), (0.1, 0, -1)), ((0.9 * r, 0, 0), (1, 0, 0.2))]
+    s = (0.05, 0.09, 0.16)
+    return list(s), [((0, 0, 0), (0.4, 0.5, 0.7)), ((0.9 * s[0], 0, 0), (1, 0, 0)), ((0.9 * s[0], 0, 0), (-1, 0.1, 0)),
+                     ((0.9 * s[0], 0.9 * s[1], 0.9 * s[2]), (1, 1, 1))]
+
+
+def inside_case(kind, transparent, nbody=RULE_NBODY):
+    """The camera inside solid 0 (body 1, a random pose per frame), an opaque sphere (id 1, body 2) 0.8 ahead of it: the
+    solid must not be seen and the sphere must."""
+    rng = np.random.default_rng(200 + INSIDE_KINDS.index(kind))
+    ty = {"sphere": 2, "capsule": 3, "ellipsoid": 4, "cylinder": 5, "box": 6}[kind]
+    size, views = inside_views(kind)
+    n = len(views)
+    pos, quat = _f32(rng.uniform(-0.05, 0.05, (2, 3))), _f32(_unit_quat(rng, 2))
+    pos[1] = 0.0
+    xpos, xquat = _still_bodies(n, nbody)
+    cams = np.zeros((n, 12), np.float32)
+    for f, (o, d) in enumerate(views):
+        xpos[f, 1], xquat[f, 1] = rng.uniform(-0.2, 0.2, 3), _unit_quat(rng, 1)[0]
+        Rb = _rot(xquat[f, 1])
+        R = Rb @ _rot(quat[0])
+        c = _f32(xpos[f, 1]).astype(np.float64) + Rb @ pos[0].astype(np.float64)
+        ow, dw = c + R @ np.asarray(o, np.float64), R @ (np.asarray(d, np.float64) / np.linalg.norm(d))
+        cams[f] = look_at(ow, ow + dw, up=(0.3, 0.5, 0.8))
+        xpos[f, 2] = ow + 0.8 * dw
+    t = rule_tables([ty, 2], [1, 2], [size, [0.3, 0, 0]], pos, quat, [[0.9, 0.5, 0.2], [0.3, 0.7, 0.9]],
+                    [1 if transparent else 0, 0])
+    return RuleCase(f"inside_{kind}_{'transparent' if transparent else 'opaque'}", t, xpos, xquat, None, None, False, cams,
+                    hidden=[0] * n)
+
+
+def beyond_end_case(nbody=RULE_NBODY):
+    """An origin beyond the end of a capsule (id 0) or cylinder (id 1) but inside the infinite cylinder sees the cap: frames
+    0, 1 from beyond the +z ends, frames 2, 3 from beyond the -z ends."""
+    rng = np.random.default_rng(300)
+    size = [[0.05, 0.2, 0], [0.06, 0.15, 0]]
+    pos, quat = _f32(rng.uniform(-0.05, 0.05, (2, 3))), _f32(_unit_quat(rng, 2))
+    xpos, xquat = _still_bodies(4, nbody)
+    cams = np.zeros((4, 12), np.float32)
+    for f in range(4):
+        xpos[f, 1], xpos[f, 2] = rng.uniform(-0.1, 0.1, 3), rng.uniform(-0.1, 0.1, 3) + [1.5, 0, 0]
+        xquat[f, 1], xquat[f, 2] = _unit_quat(rng, 2)
+        i, sgn = f % 2, 1.0 if f < 2 else -1.0
+        Rb = _rot(xquat[f, 1 + i])
+        R = Rb @ _rot(quat[i])
+        c = _f32(xpos[f, 1 + i]).astype(np.float64) + Rb @ pos[i].astype(np.float64)
+        r, hl = size[i][0], size[i][1]
+        ow = c + R @ np.array([0.3 * r, 0.0, sgn * (hl + (r if i == 0 else 0.0) + 0.15)])
+        cams[f] = look_at(ow, ow - sgn * R[:, 2], up=(0.3, 0.5, 0.8))
+    t = rule_tables([3, 5], [1, 2], size, pos, quat, [[0.9, 0.5, 0.2], [0.3, 0.7, 0.9]], [0, 0])
+    return RuleCase("beyond_end", t, xpos, xquat, None, None, False, cams)
+
+
+TIE_CLEAR, TIE_OPAQUE = (14, 15), (17, 18)  # the two pairs of equal records in transparency_case
+
+
+def transparency_case(nbody=RULE_NBODY):
+    """Camera at the origin looking along +x.  Ids 0-11: twelve transparent spheres in a row (more than the 8 layers) in front
+    of the opaque sphere 12; 13: an opaque box; 14, 15: two transparent spheres with one and the same record (an exactly
+    equal entry depth; the tie goes by id) in front of it; 16: a transparent ellipsoid behind the box, showing beside it;
+    17, 18: two opaque spheres with the same record."""
+    rng = np.random.default_rng(400)
+    ty, size, pos, flags = [], [], [], []
+    row = np.array([1.0, 0.15, 0.05]) / np.linalg.norm([1.0, 0.15, 0.05])  # a ray of the camera
+    for j in range(12):
+        ty.append(2), size.append([0.05 + 0.004 * j, 0, 0]), flags.append(1)
+        pos.append((0.5 + 0.12 * j) * row + rng.normal(scale=0.004, size=3))
+    ty.append(2), size.append([0.3, 0, 0]), pos.append(2.4 * row), flags.append(0)
+    ty.append(6), size.append([0.05, 0.2, 0.25]), pos.append([1.6, -0.3, 0.1]), flags.append(0)
+    for _ in range(2):
+        ty.append(2), size.append([0.032, 0, 0]), pos.append([1.0, -0.25, 0.2]), flags.append(1)
+    ty.append(4), size.append([0.2, 0.3, 0.15]), pos.append([2.1, -0.45, 0.1]), flags.append(1)
+    for _ in range(2):
+        ty.append(2), size.append([0.032, 0, 0]), pos.append([1.0, -0.25, -0.25]), flags.append(0)
+    P = len(ty)
+    quat = _unit_quat(rng, P)
+    for a, b in (TIE_CLEAR, TIE_OPAQUE):
+        quat[b] = quat[a]
+    xpos, xquat = _still_bodies(1, nbody)
+    cams = look_at((0, 0, 0), (1, 0, 0.02))[None]
+    rgb = rng.uniform(0.1, 1.0, (P, 3))
+    rgb[[14, 17]], rgb[[15, 18]] = [0.9, 0.2, 0.1], [0.1, 0.3, 0.9]  # far apart: the order within a tie shows
+    t = rule_tables(ty, [0] * P, size, pos, quat, rgb, flags)
+    return RuleCase("transparency", t, xpos, xquat, None, None, False, cams)
+
+
+def error_segment_case(nbody=RULE_NBODY):
+    """Error segments (radius 0.012, wider than the 0.005 keypoint and marker spheres) seen from 0.25 away: keypoint 0 and its
+    marker coincide (a segment of length 0), 1: 1e-6 apart (these two, flagged ambiguous all over, from 0.45 away), 2: a NaN in the keypoint, 3: a NaN in the marker, 4 and 5:
+    ordinary segments; behind them an opaque plane facing the camera."""
+    rng = np.random.default_rng(500)
+    K = 6
+    kp = np.array([[0.45, -0.18, 0.09], [0.45, -0.09, -0.09], [0.25, 0.0, 0.06], [0.25, 0.04, -0.05], [0.25, 0.08, 0.03],
+                   [0.27, -0.02, 0.0]])
+    step = rng.normal(size=3)
+    mk = kp.copy()
+    mk[1] += 1e-6 * step / np.linalg.norm(step)
+    mk[2] += [0.0, 0.01, 0.02]
+    mk[3] += [0.0, 0.01, -0.02]
+    mk[4] += [0.02, 0.03, -0.07]
+    mk[5] += [-0.06, -0.03, 0.05]
+    kp[2, 1] = np.nan
+    mk[3, 2] = np.nan
+    h = math.sqrt(0.5)
+    t = rule_tables([0], [0], [[0.4, 0.4, 0.01]], [[0.5, 0, 0]], [[h, 0, -h, 0]], [[0.6, 0.6, 0.5]], [0],
+                    kp_rgb=rng.uniform(0.2, 1.0, (K, 3)), marker_radius=0.005, segment_radius=0.012)
+    xpos, xquat = _still_bodies(1, nbody)
+    cams = look_at((0, 0, 0), (1, 0, 0))[None]
+    return RuleCase("error_segments", t, xpos, xquat, _f32(kp[None]), _f32(mk[None]), True, cams)
+
+
+def lights_case(lit, nbody=RULE_NBODY):
+    """A sphere, an ellipsoid, a box and a cylinder over a plane, from above and from below.  ``lit`` False: no <light>, the
+    headlight alone; True: two lights whose sum with the headlight exceeds 1 on the upper sides, while every normal of the
+    undersides seen from below faces away from both."""
+    rng = np.random.default_rng(600)
+    ty = [0, 2, 4, 6, 5]
+    size = [[0.6, 0.6, 0.01], [0.1, 0, 0], [0.08, 0.14, 0.05], [0.07, 0.1, 0.05], [0.06, 0.09, 0]]
+    pos = [[0, 0, -0.2], [-0.2, 0.15, 0], [0.15, 0.2, 0.02], [0.2, -0.15, 0], [-0.15, -0.2, 0.03]]
+    quat = _unit_quat(rng, 5)
+    quat[0] = [1, 0, 0, 0]
+    lights = ((0, 0, -1), (0.6, 0, -0.8)) if lit else np.zeros((0, 3))
+    diffuse = ((0.8, 0.8, 0.8), (0.7, 0.6, 0.5)) if lit else np.zeros((0, 3))
+    t = rule_tables(ty, [0] * 5, size, pos, quat, rng.uniform(0.3, 1.0, (5, 3)), [0] * 5, lights=lights, diffuse=diffuse)
+    xpos, xquat = _still_bodies(2, nbody)
+    cams = np.stack([look_at((0.5, -0.6, 0.7), (0, 0, 0)), look_at((0.3, 0.4, -0.9), (0, 0, 0))])
+    return RuleCase(f"lights_{'two' if lit else 'none'}", t, xpos, xquat, None, None, False, cams)
+
+
+def rule_cases(nbody=RULE_NBODY) -> dict:
+    """name -> RuleCase: every constructed scene of the rule tests (the random scenes and the rodent are added by the tests)."""
+    cases = [outside_case(k, nbody) for k in OUTSIDE_KINDS]
+    cases += [inside_case(k, tr, nbody) for k in INSIDE_KINDS for tr in (False, True)]
+    cases += [beyond_end_case(nbody), transparency_case(nbody), error_segment_case(nbody), lights_case(False, nbody),
+              lights_case(True, nbody)]
+    return {c.name: c for c in cases}
+
+
+_RULE_PICTURES = {}
+
+
+def rule_picture(name, args, W, H):
+    """``render_rule.render`` of a scene, computed once per (name, size) and shared by the tests of a run (read only)."""
+    import render_rule
+
+    if (name, W, H) not in _RULE_PICTURES:
+        out = render_rule.render(*args, W, H)
+        for a in out:
+            a.setflags(write=False)
+        _RULE_PICTURES[(name, W, H)] = out
+    return _RULE_PICTURES[(name, W, H)]
+
+
+def excluded_share(mask, hit, single):
+    """Share of an image's pixels that ``mask`` takes out of a comparison; for a single-primitive image of which fewer than
+    20 % of the pixels hit anything, the share of the hit pixels (the cap would otherwise hide a thin primitive entirely)."""
+    if single and hit.mean() < 0.2:
+        return (mask & hit).sum() / max(int(hit.sum()), 1)
+    return mask.mean()
+
+
+def eroded(m):
+    """The pixels of a mask whose four neighbours are in it too."""
+    out = m.copy()
+    out[1:] &= m[:-1]
+    out[:-1] &= m[1:]
+    out[:, 1:] &= m[:, :-1]
+    out[:, :-1] &= m[:, 1:]
+    out[0] = out[-1] = False
+    out[:, 0] = out[:, -1] = False
+    return out
+
+
+def compare_with_rule(got, rule, amb, single=False, depth_rtol=1e-5, what=""):
+    """rgb, seg, depth of a build (or of the kernel) against ``render_rule`` on every pixel that neither the double build's
+    ``amb`` nor the rule's ``edge`` marks: seg and hit / no-hit equal, rgb within one quantisation step, depth within
+    ``depth_rtol`` relative.  The excluded pixels are at most AMB_CAP of each image (``excluded_share``).  Returns the
+    largest relative depth difference and the largest excluded share."""
+    rgb, seg, depth = got[:3]
+    r_rgb, r_seg, r_depth, edge = rule
+    worst_rel, worst_share = 0.0, 0.0
+    for f in range(len(seg)):
+        mask = amb[f].astype(bool) | edge[f]
+        share = excluded_share(mask, r_seg[f] >= 0, single)
+        worst_share = max(worst_share, share)
+        assert share <= AMB_CAP, f"{what} frame {f}: {share:.4f} of the pixels are excluded"
+        ok = ~mask
+        bad = np.argwhere((seg[f] != r_seg[f]) & ok)
+        first = tuple(bad[0]) if bad.size else None
+        assert bad.size == 0, f"{what} frame {f} seg: {len(bad)} pixels differ, first (y, x) {first}: {seg[f][first]} vs rule {r_seg[f][first]}"
+        assert (np.isinf(depth[f]) == np.isinf(r_depth[f]))[ok].all(), f"{what} frame {f}: hit / no hit differs"
+        diff = np.abs(rgb[f].astype(int) - r_rgb[f].astype(int)).max(-1)
+        bad = np.argwhere((diff > 1) & ok)
+        first = tuple(bad[0]) if bad.size else None
+        assert bad.size == 0, f"{what} frame {f} rgb: {len(bad)} pixels off by more than 1, first (y, x) {first}: {rgb[f][first]} vs rule {r_rgb[f][first]}"
+        fin = ok & np.isfinite(r_depth[f])
+        if fin.any():
+            rel = np.abs(depth[f][fin].astype(np.float64) - r_depth[f][fin]) / r_depth[f][fin]
+            worst_rel = max(worst_rel, float(rel.max()))
+            assert rel.max() <= depth_rtol, f"{what} frame {f} depth: relative difference {rel.max():.3e} > {depth_rtol:.1e}"
+    return worst_rel, worst_share

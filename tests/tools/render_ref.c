@@ -186,6 +186,12 @@ static real intersect(const rec_t *r, const real *o, const real *d, real dd, int
         const real w[3] = {R[2], R[5], R[8]};
         const real hl = sz[1], rad = sz[0];
         const real oz = dot3(oc, w), dz = dot3(d, w);
+        /* an origin inside the capsule does not see it: nearer to the axis point at oz clamped to the segment than rad */
+        const real ozc = rmin(rmax(oz, -hl), hl);
+        const real oq[3] = {oc[0] - w[0] * ozc, oc[1] - w[1] * ozc, oc[2] - w[2] * ozc};
+        const real in2 = rad * rad - dot3(oq, oq);
+        flag(amb, (double)in2, ocn * (double)rad);
+        if (in2 > 0) return -1;
         const real op[3] = {oc[0] - w[0] * oz, oc[1] - w[1] * oz, oc[2] - w[2] * oz};
         const real dp[3] = {d[0] - w[0] * dz, d[1] - w[1] * dz, d[2] - w[2] * dz};
         const real a = dot3(dp, dp);

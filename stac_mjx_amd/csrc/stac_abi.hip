@@ -348,6 +348,7 @@ static std::vector<int32_t> build_fk_program(const stac_model *m, const char *ne
 struct Fk3Program {
     std::vector<int32_t> words;   // T1 [16 (cap1 + 2)] (cap1 / 2 + 3 records of 24 words), T2 [cap2][4], T3 [cap3 * 4] (cap3 + 12 used), site words [K], joint words [naj]
     int n1 = 0, n2 = 0, n3 = 0;
+    int nrot = 0;                 // rotations of P2 before the padding (n2: with the no-op tasks that fill its last round)
 };
 struct Fk3Op { int prev; int height; int t = -1, pp = -1; bool restart = false; };
 // B, D: an operation may restart only in a step t with t % B == 0, and only from a predecessor finished in a step <= t - D (the
@@ -495,13 +496,13 @@ static bool build_fk3_program(const stac_model *m, const PlanHeader &h3, const c
     if (n1 > 0) n1 = (n1 + 1) & ~1;  // P1 runs whole blocks of two steps
     int n3 = fk3_schedule(o3, 4, 5);
     if (n3 > 0) n3 = (n3 + 3) & ~3;  // P3 runs whole blocks of four steps
-    const int n2 = ((int)o3.size() + 31) & ~31;
+    const int n2 = ((int)o3.size() + 15) & ~15;  // P2 runs whole rounds of 16 lanes (32-lane groups: the area's no-ops behind them, cap2)
     if (n1 < 0 || n3 < 0 || n1 > 254 || n3 > 252 || n1 > cap1 || n3 > cap3 || n2 > cap2) return false;  // (eight bits each in PlanHeader::fk3_n)
     const int root_slot = cap3 * 4, sink_slot = cap3 * 4 + 1;
     auto pbw = [&](int op) { return h3.c3_pb + 3 * (op < 0 ? root_slot : o3[op].t * 4 + o3[op].pp); };
     auto qbw = [&](int node) { return h3.c3_qb + 4 * node; };
     if (h3.stride3 >= 65536) return false;
-    out.n1 = std::max(n1, 0); out.n2 = n2; out.n3 = n3;
+    out.n1 = std::max(n1, 0); out.n2 = n2; out.n3 = n3; out.nrot = (int)o3.size();
     // T1, blocks of two steps, 24 words per record: [24 r + 4 pp] = {ql word of step 2 r, of step 2 r + 1, out word of step 2 r - 2, of
     // 2 r - 1}, [24 r + 16 + 2 pp] = {restart entry of block r - 1, of block r} -- record r + 1 is what block r works from (its out words,
     // its restart flag, the next block's ql and restart words), record 0 the prologue.  A restart entry: the word of the quaternion the
@@ -861,8 +862,8 @@ static int build_plan(stac_model *m, const stac_model_tables *t) {
             g.c3_qb = 0; g.c3_pb = 0; g.c3_ql = 0; g.c3_bq = 0; g.nbq = nbq; g.stride3 = 1;
             ok = build_fk3_program(m, g, nullptr, 254, 4096, 252, probe);
             if (ok) {
-                // (cap1 even, >= 10: the table area 16 (cap1 + 2) holds cap1 / 2 + 3 records of 24 words; cap3: whole blocks)
-                g.fk3_cap1 = std::max(probe.n1, 10); g.fk3_cap2 = std::max(probe.n2, 32); g.fk3_cap3 = std::max(probe.n3, 4);
+                // (cap1 even, >= 10: the table area 16 (cap1 + 2) holds cap1 / 2 + 3 records of 24 words; cap2: whole rounds of 32 lanes; cap3: whole blocks)
+                g.fk3_cap1 = std::max(probe.n1, 10); g.fk3_cap2 = std::max((probe.n2 + 31) & ~31, 32); g.fk3_cap3 = std::max(probe.n3, 4);
                 int o3 = 0;
                 g.c3_qb = o3; o3 += (naj + 1 + nbq) * 4;                 // (+ 1: the sink of idle P1 positions; then the oriented bodies' nodes)
                 g.c3_pb = o3; o3 += ((g.fk3_cap3 * 4 + 4) * 3 + 3) & ~3;  // (step, position) slots, root position, sink, slack of the prefetch
@@ -1406,8 +1407,9 @@ static int plan_q(const stac_model *m, const stac_q_params *p, const QArgs &req,
         const int free0b = free0_ordinal_p1(m, kLatG), flags_b = with_hinges(m, flags & ~2, free0b);
         const bool lean_b = lean_launch(flags_b, free0b) && lean_holds(mh, kLatLean, kLatG, kLatR);
         const PlanHeader hb = lean_b ? lean_header(false) : mh;
-        // Straggler hand-off: chains take very different numbers of iterations (the slowest of 10 000 about 1.6x the
-        // mean), so the launch would end on a few waves per CU.  Once all but `hcap` chains are done, the rest move to
+        // Straggler hand-off: chains differ in the iterations of their two root solves only (about 120 to 540 per frame, 310 on average, on
+        // the bench's keypoints; the full-body solve runs to its bound of 400 for every frame and the part solves are short:
+        // profiles/r07/throughput_phases.md), so the launch would end on a few waves per CU.  Once all but `hcap` chains are done, the rest move to
         // the latency kernel at their next iteration boundary (QArgs::ctl).
         const bool can_hand = !req.single && !(flags & 3) && (lean_b || mh.max_width <= kLatG) && lat_one_wave_ok(mh);
         const int spec_cap = can_hand ? (int)pick_spec_shape(hb, kLatG, nkinds, cus, -1, kLatR).resident : 0;
@@ -1738,6 +1740,16 @@ static int run_q_lm(stac_model *m, const stac_q_params *p, QArgs a, int nchains,
     return STAC_OK;
 }
 
+// The active bodies a root pass needs: the ancestors of the weighted (trunk) keypoints' bodies.  Returns their number.
+static int root_pass_bodies(const stac_model *m, const uint8_t *trunk_kps, std::vector<char> &need) {
+    need.assign(m->h.nab, 0);
+    int n_need = 0;
+    for (int k = 0; k < m->h.K; ++k)
+        if (trunk_kps[k])
+            for (int sl = m->h_site_slot[k]; sl >= 0 && !need[sl]; sl = m->h_ab_parent[sl] - 1) { need[sl] = 1; ++n_need; }
+    return n_need;
+}
+
 // Root passes weigh the trunk keypoints only: every other site contributes exact zeros there, so the kinematics of
 // the bodies that carry no trunk keypoint are not needed.  Builds the FK program of the needed bodies into the
 // blob's second program area; the kernel runs it when every chain of a wavefront is in a root pass.
@@ -1746,11 +1758,8 @@ static int fill_root_program(stac_model *m, const uint8_t *trunk_kps, bool enabl
     m->n_mlev_root = 0;
     m->fk3r = 0;
     if (!enable || m->dbg.noprune) return STAC_OK;
-    std::vector<char> need(h.nab, 0);
-    int n_need = 0;
-    for (int k = 0; k < h.K; ++k)
-        if (trunk_kps[k])
-            for (int sl = m->h_site_slot[k]; sl >= 0 && !need[sl]; sl = m->h_ab_parent[sl] - 1) { need[sl] = 1; ++n_need; }
+    std::vector<char> need;
+    const int n_need = root_pass_bodies(m, trunk_kps, need);
     if (n_need == 0 || n_need == h.nab) return STAC_OK;  // nothing to prune (or nothing weighted at all)
     int n_mlev = 0;
     // Only the root joints' gradients are evaluated in a pruned trip: every other joint's {anchor, pre-joint quaternion}
@@ -2227,5 +2236,32 @@ extern "C" int32_t stac_jpeg_encode(int64_t N, int32_t width, int32_t height, in
     jpeg_make_header(width, height, quality, restart_mcus, &h);
     const hipError_t e = launch_jpeg_encode(c, h, (hipStream_t)stream);
     if (e != hipSuccess) return fail(STAC_ERR_HIP, std::string("stac_jpeg_encode: ") + hipGetErrorString(e));
+    return STAC_OK;
+}
+
+
+// Diagnostics, not part of include/stac_hip.h (tests/test_fk3_rounds_host.py, tests/test_gpu_fk3_rounds.py): the split-kinematics
+// program of a model, built on the host alone -- no device is touched.  trunk_kps == NULL: the full program; else the pruned program
+// of the root passes for these trunk keypoints.  info[12] = {1 if the model takes the split kinematics, n1, n2, n3, rotations before
+// the padding, cap2, the no-op task's quaternion word, the sink word of P2, distinct site ranges, PlanHeader::rsplit, active bodies,
+// bodies the program evaluates}; t2 (may be NULL): the first min(cap2, cap_tasks) tasks of
+// the program's T2 area, four words each.  Returns STAC_OK, or an error if the plan cannot be built.
+extern "C" int32_t stac_debug_fk3_program(const stac_model_tables *t, const uint8_t *trunk_kps, int32_t *info, int32_t *t2, int32_t cap_tasks) {
+    if (!t || !info) return fail(STAC_ERR_INVALID, "null argument");
+    stac_model m;
+    m.dbg.read_env();
+    if (const int rc = build_plan(&m, t)) return rc;
+    for (int i = 0; i < 12; ++i) info[i] = 0;
+    info[8] = m.h.nrange; info[9] = m.h.rsplit; info[10] = m.h.nab;
+    if (!m.h.fk3) return STAC_OK;
+    const PlanHeader &h = m.h;
+    Fk3Program pr;
+    std::vector<char> need;
+    info[11] = trunk_kps ? root_pass_bodies(&m, trunk_kps, need) : h.nab;
+    if (!build_fk3_program(&m, m.h3, trunk_kps ? need.data() : nullptr, h.fk3_cap1, h.fk3_cap2, h.fk3_cap3, pr))
+        return fail(STAC_ERR_CAPACITY, "the split-kinematics program does not fit the model's program area");
+    info[0] = 1; info[1] = pr.n1; info[2] = pr.n2; info[3] = pr.n3; info[4] = pr.nrot; info[5] = h.fk3_cap2;
+    info[6] = m.h3.c3_qb; info[7] = m.h3.c3_pb + 3 * (h.fk3_cap3 * 4 + 1);
+    if (t2) std::memcpy(t2, pr.words.data() + 16 * (h.fk3_cap1 + 2), sizeof(int32_t) * 4 * (size_t)std::max(0, std::min(h.fk3_cap2, cap_tasks)));
     return STAC_OK;
 }

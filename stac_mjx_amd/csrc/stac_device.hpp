@@ -1046,13 +1046,15 @@ __device__ __forceinline__ void fk3_p1(const float *T1, const int nb, float *CBc
         base[Rb.w] = fk3_qmul(q1, qb, L);
     }
 }
-// P2.  T2: tasks {v.x, v.y, v.z, quaternion word | result word << 16}, n2 a multiple of 32 (no-op tasks at the end).  PAIR (throughput
-// kernels at 16 lanes): two rounds of lanes at once -- their loads in flight together, their arithmetic, chains of dependent
-// instructions, interleaved (a lone wavefront of the latency kernels pays per instruction, dependent or not: one round at a time).
+// P2.  T2: tasks {v.x, v.y, v.z, quaternion word | result word << 16}, n2 a multiple of 16 (no-op tasks at the end; the table behind
+// them holds no-ops up to the next multiple of 32).  PAIR (throughput kernels at 16 lanes): two rounds of lanes at once -- their loads
+// in flight together, their arithmetic, chains of dependent instructions, interleaved -- and one single round behind them where the
+// count of rounds is odd (a lone wavefront of the latency kernels pays per instruction, dependent or not: one round at a time).
 template <bool PAIR>
 __device__ __forceinline__ void fk3_p2(const float *T2, const int n2, float *CBc, const int lf, const int gf) {
     if constexpr (PAIR) {
-        for (int i0 = 0; i0 < n2; i0 += 2 * gf) {  // (whole rounds: no lane-dependent trip count; 2 gf = 32 divides n2)
+        const int n2p = n2 & ~(2 * gf - 1);
+        for (int i0 = 0; i0 < n2p; i0 += 2 * gf) {  // (whole rounds: no lane-dependent trip count)
             const float4 ta = lds4(T2 + 4 * (i0 + lf));
             const float4 tb = lds4(T2 + 4 * (i0 + gf + lf));
             const int wa = __builtin_bit_cast(int, ta.w), wb = __builtin_bit_cast(int, tb.w);
@@ -1063,14 +1065,23 @@ __device__ __forceinline__ void fk3_p2(const float *T2, const int n2, float *CBc
             oa[0] = ra.x; oa[1] = ra.y; oa[2] = ra.z;
             ob[0] = rb.x; ob[1] = rb.y; ob[2] = rb.z;
         }
+        if (n2 & gf) {  // (wave-uniform: n2 is the program's, the same for every chain of the launch's pass)
+            const float4 ta = lds4(T2 + 4 * (n2p + lf));
+            const int wa = __builtin_bit_cast(int, ta.w);
+            const float4 qa = lds4(CBc + (wa & 0xFFFF));
+            const V3 ra = rotate(V3{ta.x, ta.y, ta.z}, Q4{qa.x, qa.y, qa.z, qa.w});
+            float *oa = CBc + (int)((unsigned)wa >> 16);
+            oa[0] = ra.x; oa[1] = ra.y; oa[2] = ra.z;
+        }
     } else {
         // (a lone wavefront waits out every LDS round trip: a round's task comes two rounds ahead, its quaternion one; the rounds
-        //  behind the last one read the last round again)
+        //  behind the last one read the last round again.  Whole rounds of gf lanes: at 32 lanes the last one may end in the table's no-ops)
+        const int n2r = gf > 16 ? (n2 + gf - 1) & ~(gf - 1) : n2;
         const float *tp = T2 + 4 * lf;
-        const int last = n2 - gf;
+        const int last = n2r - gf;
         float4 tk = lds4(tp), tn = lds4(tp + 4 * min(gf, last));
         float4 q4 = lds4(CBc + (__builtin_bit_cast(int, tk.w) & 0xFFFF));  // (w, x, y, z)
-        for (int i0 = 0; i0 < n2; i0 += gf) {
+        for (int i0 = 0; i0 < n2r; i0 += gf) {
             const float4 tnn = lds4(tp + 4 * min(i0 + 2 * gf, last));
             const float4 qn = lds4(CBc + (__builtin_bit_cast(int, tn.w) & 0xFFFF));
             const V3 r = rotate(V3{tk.x, tk.y, tk.z}, Q4{q4.x, q4.y, q4.z, q4.w});

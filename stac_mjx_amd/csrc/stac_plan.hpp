@@ -190,7 +190,7 @@ struct PlanHeader {
                            // build_fk3_program, stac_abi.hip), T2 [cap2][4] {v.x, v.y, v.z, q word | out word << 16}, T3 [cap3 * 4]: per block of
                            // four steps and position the restart entry (word of the value, or bit 31 | a valid word), then the site and joint words
     int32_t off3_root;     // same layout: the pruned program of the root passes (filled per call)
-    int32_t fk3_n;         // full program: steps of P1 (even) | steps of P3 (a multiple of 4) << 8 | tasks of P2 (padded to a multiple of 32 with no-ops) << 16
+    int32_t fk3_n;         // full program: steps of P1 (even) | steps of P3 (a multiple of 4) << 8 | tasks of P2 (padded to a multiple of 16 with no-ops) << 16
     int32_t fk3_cap1, fk3_cap2, fk3_cap3;  // capacity of either program area (steps / tasks): where T2, T3 and the site words start
     int32_t c3_ql;         // [naj * 4] joint-local quaternions (w, x, y, z) by active joint; the range sums of a full trip alias it
     int32_t c3_qb;         // [naj * 4] quaternion AFTER every active joint (w, x, y, z); entry 0 = the free root's

@@ -1509,15 +1509,15 @@ static int run_q(const stac_model *m, const stac_q_params *p, QArgs a, int nchai
     if (rc != STAC_OK) return rc;
 #ifdef STAC_PROFILE
     static unsigned long long *d_prof = nullptr;
-    if (!d_prof) { (void)hipMalloc(reinterpret_cast<void **>(&d_prof), 16 * sizeof(unsigned long long)); }
-    (void)hipMemsetAsync(d_prof, 0, 16 * sizeof(unsigned long long), s);
+    if (!d_prof) { (void)hipMalloc(reinterpret_cast<void **>(&d_prof), 24 * sizeof(unsigned long long)); }
+    (void)hipMemsetAsync(d_prof, 0, 24 * sizeof(unsigned long long), s);
     a.prof = d_prof;
 #endif
     rc = launch_plan(m, a, pl, nullptr, s);
     if (rc != STAC_OK) return rc;
 #ifdef STAC_PROFILE
     {
-        unsigned long long h[16];
+        unsigned long long h[24];
         (void)hipStreamSynchronize(s);
         (void)hipMemcpy(h, a.prof, sizeof(h), hipMemcpyDeviceToHost);
         static const char *names[] = {"loop", "stage", "fk", "sites", "loss_sum", "zero_gg", "joint_grad", "trans_sums", "accept_fused", "end_solve", "prepass", "-"};
@@ -1528,6 +1528,13 @@ static int run_q(const stac_model *m, const stac_q_params *p, QArgs a, int nchai
         fprintf(stderr, " total_wave_cycles=%.3g wave_trips=%.4g cycles_per_wave_trip=%.0f fk_cycles_per_wave_trip=%.0f pure_root_trips=%.4g cycles_per_pure_root_trip=%.0f cycles_per_other_trip=%.0f\n", (double)tot, (double)h[11],
                 (double)tot / (double)(h[11] ? h[11] : 1), (double)h[2] / (double)(h[11] ? h[11] : 1), (double)h[13],
                 (double)h[12] / (double)(h[13] ? h[13] : 1), (double)(tot - h[12]) / (double)(h[11] - h[13] ? h[11] - h[13] : 1));
+        // the sub-stamps inside "stage" (stamps 0 -> 1; PROF_SUB): mean cycles per wave-trip of the selected trip class
+        static const char *subs[] = {"kernarg_views", "handoff", "root_queue_votes", "staging_stores", "free_root_prepass"};
+        const double trips = (double)(h[11] ? h[11] : 1);
+        unsigned long long sub_tot = 0;
+        fprintf(stderr, "[stac profile head] stage=%.0f", (double)h[1] / trips);
+        for (int i = 0; i < 5; ++i) { fprintf(stderr, " %s=%.0f", subs[i], (double)h[16 + i] / trips); sub_tot += h[16 + i]; }
+        fprintf(stderr, " rest=%.0f loop=%.0f\n", ((double)h[1] - (double)sub_tot) / trips, (double)h[0] / trips);
     }
 #endif
     return STAC_OK;

@@ -85,6 +85,12 @@ __device__ __forceinline__ float xor_partner(float v) {
     else r = __shfl_xor(i, 32, 64);
     return __builtin_bit_cast(float, r);
 }
+// The value held by lane L of the caller's 16-lane row, in every lane of the row (DPP row_newbcast: one VALU move, no LDS round trip)
+template <int L>
+__device__ __forceinline__ float row_bcast(float v) {
+    const int i = __builtin_bit_cast(int, v);
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(i, i, 0x150 + L, 0xF, 0xF, true));
+}
 // Pairwise-tree sum over the elements e = r*G + lane_in_group of a striped vector (zeros beyond nq):
 // lane butterflies for the levels below G, then the registers.  Every lane of the group gets the sum.
 // (Round 6 tried gfx950's v_permlane16_swap / v_permlane32_swap for the two levels that cross a 16-lane row, instead of ds_swizzle /
@@ -241,13 +247,26 @@ enum : int { ST_VG_Y = 0, ST_LS = 1, ST_VG_X = 2, ST_DONE = 3, ST_SPEC = 4, ST_W
 // In-kernel phase stamps: diagnostic build only (-DSTAC_PROFILE -> libstac_hip_prof.so); the stamps
 // go to a buffer of their own and feed no output.  Read the SHARES, not the run time.
 #ifdef STAC_PROFILE
+constexpr int kProfSub = 5;
 // -DSTAC_PROFILE_SEL=1: only root fast (lite) trips are accumulated; =0: only the others; undefined: all trips
-#define PROF_DECL unsigned long long pt0 = __builtin_readcyclecounter(), pacc[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, ptmp[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; unsigned long long ptrip0 = pt0
+#define PROF_DECL unsigned long long pt0 = __builtin_readcyclecounter(), pacc[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, ptmp[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; unsigned long long ptrip0 = pt0; \
+    unsigned long long ps0 = pt0, psub[kProfSub] = {0, 0, 0, 0, 0}, psacc[kProfSub] = {0, 0, 0, 0, 0}
 #define PROF_TICK(i)                                             \
     do {                                                         \
         const unsigned long long pt1 = __builtin_readcyclecounter(); \
         ptmp[i] += pt1 - pt0;                                    \
         pt0 = pt1;                                               \
+        ps0 = pt1;                                               \
+    } while (0)
+// Sub-stamps inside the phase 0 -> 1 (round 8): cycles since the previous stamp or sub-stamp.  They do not move pt0, so the phase's own
+// figure stays what it was; what the sub-stamps leave of it is the stretch behind the last of them.
+//   0 = kernarg views, 1 = hand-off block, 2 = root phase, chain queue and the votes up to `lite`, 3 = staging stores,
+//   4 = the free root's pre-pass and its wave_sync()
+#define PROF_SUB(k)                                              \
+    do {                                                         \
+        const unsigned long long pq_ = __builtin_readcyclecounter(); \
+        psub[k] += pq_ - ps0;                                    \
+        ps0 = pq_;                                               \
     } while (0)
 #define PROF_TRIP
 #ifdef STAC_PROFILE_SEL
@@ -256,7 +275,8 @@ enum : int { ST_VG_Y = 0, ST_LS = 1, ST_VG_X = 2, ST_DONE = 3, ST_SPEC = 4, ST_W
 #define PROF_KEEP(isroot) true
 #endif
 #define PROF_ROOT(isroot) do { const unsigned long long pq = __builtin_readcyclecounter(); if (isroot) { pacc[12] += pq - ptrip0; pacc[13] += 1; } ptrip0 = pq; \
-        const bool keep_ = PROF_KEEP(isroot); for (int i_ = 0; i_ < 11; ++i_) { if (keep_) pacc[i_] += ptmp[i_]; ptmp[i_] = 0; } if (keep_) pacc[11] += 1; } while (0)
+        const bool keep_ = PROF_KEEP(isroot); for (int i_ = 0; i_ < 11; ++i_) { if (keep_) pacc[i_] += ptmp[i_]; ptmp[i_] = 0; } if (keep_) pacc[11] += 1; \
+        for (int i_ = 0; i_ < kProfSub; ++i_) { if (keep_) psacc[i_] += psub[i_]; psub[i_] = 0; } } while (0)
 // (the LM kernel keeps the plain accumulation: it has no trip classes)
 #define PROF_LM_END do { for (int i_ = 0; i_ < 12; ++i_) { pacc[i_] += ptmp[i_]; ptmp[i_] = 0; } } while (0)
 #define PROF_FLUSH(a)                                                                     \
@@ -264,20 +284,29 @@ enum : int { ST_VG_Y = 0, ST_LS = 1, ST_VG_X = 2, ST_DONE = 3, ST_SPEC = 4, ST_W
         if (a.prof && lane == 0)                                                          \
             for (int i = 0; i < 14; ++i) atomicAdd(a.prof + i, pacc[i]);                  \
     } while (0)
+#define PROF_FLUSH_SUB(a)                                                                 \
+    do {                                                                                  \
+        if (a.prof && lane == 0)                                                          \
+            for (int i = 0; i < kProfSub; ++i) atomicAdd(a.prof + 16 + i, psacc[i]);      \
+    } while (0)
 #elif defined(STAC_MARK)  // developer builds: phase boundaries as comments in the assembly listing (no instruction)
 #define PROF_DECL
 #define PROF_TRIP
 #define PROF_ROOT(isroot)
 #define PROF_LM_END
 #define PROF_TICK(i) asm volatile("; TICK " #i)
+#define PROF_SUB(k) asm volatile("; SUB " #k)
 #define PROF_FLUSH(a)
+#define PROF_FLUSH_SUB(a)
 #else
 #define PROF_DECL
 #define PROF_TRIP
 #define PROF_ROOT(isroot)
 #define PROF_LM_END
 #define PROF_TICK(i)
+#define PROF_SUB(k)
 #define PROF_FLUSH(a)
+#define PROF_FLUSH_SUB(a)
 #endif
 enum : int { JFREE = 0, JBALL = 1, JSLIDE = 2, JHINGE = 3 };
 

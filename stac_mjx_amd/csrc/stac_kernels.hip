@@ -484,6 +484,25 @@ void q_phase_kernel(const QArgs a_in) {
     const HotArgs hot_a = pin_args<kVPin>(a);
 #endif
     const int cb_words = (int)(CB - lds);
+    // Throughput kernels: what the head of a trip decides is decided by the launch, not by the trip -- is the hand-off armed (`ctl` given and
+    // this is not the resume launch), does the chain queue hand out chains for root fast trips, how many coordinates a root pass moves, the
+    // pruned program's counts.  Four scalar loads per trip (root_fast, resume, the ctl pointer, and fk3r_n, which had a wait of its own in
+    // the middle of the head) and the compares behind them become two pinned scalars: the head tests bits, and the cold fields (ctl, hand, C)
+    // are fetched inside the branch that uses them.  (profiles/r08/NOTES.md)
+#ifndef STAC_NO_CTLWORD
+    constexpr bool kCtlWord = SPEC == 0 && LEAN;  // (the generic kernels spill scalars already: two more pinned ones cost them six spills)
+#else
+    constexpr bool kCtlWord = false;
+#endif
+    enum : uint32_t { CW_ROOT_FAST = 0xFFu, CW_HAND = 1u << 8, CW_QUEUE = 1u << 9 };
+    uint32_t ctl_word = 0;
+    int32_t fk3r_pin = 0;
+    if constexpr (kCtlWord) {
+        ctl_word = ((uint32_t)a.root_fast & CW_ROOT_FAST) | ((a.ctl && !a.resume) ? (uint32_t)CW_HAND : 0u) |
+                   ((a.queue_slots > 0 && a.root_fast > 0) ? (uint32_t)CW_QUEUE : 0u);
+        fk3r_pin = a.fk3r_n;
+        asm volatile("" : "+s"(ctl_word), "+s"(fk3r_pin));
+    }
     while (__any(st != ST_DONE)) {
         PROF_TICK(0);  // loop control
         PROF_TRIP;
@@ -498,6 +517,7 @@ void q_phase_kernel(const QArgs a_in) {
             __builtin_assume(4 * H_t.max_width <= G);
             __builtin_assume(H_t.K <= NSR * G);
         }
+        if constexpr (kCtlWord) a_t.root_fast = (int32_t)(ctl_word & CW_ROOT_FAST);
         const TripArgs &a = a_t;
         const TripHeader &H = H_t;
 #else
@@ -527,7 +547,8 @@ void q_phase_kernel(const QArgs a_in) {
         const TripCtx cx{lg, nq, K, kpl, lbv, ubv, P + H.off_qpos0, MB};
         // lean kernels (split kinematics, PlanHeader::fk3): word of the root position inside a chain's region (behind the slots of P3)
         const int root_w = LEAN ? H.c3_pb + 12 * H.fk3_cap3 : 0;
-        if (!SPEC && a.ctl && !a.resume) {
+        PROF_SUB(0);  // kernarg views
+        if (kCtlWord ? (ctl_word & CW_HAND) != 0 : (!SPEC && a.ctl && !a.resume)) {
             // hand-off: a chain about to start an iteration after most chains of the launch are done goes to the
             // latency kernel (its state is complete at this point: x, y, q0 and a dozen scalars)
             // (looked at every eighth iteration: the counter lives in L2)
@@ -560,6 +581,7 @@ void q_phase_kernel(const QArgs a_in) {
             }
             if (!__any(st != ST_DONE)) break;
         }
+        PROF_SUB(1);  // hand-off look
         if constexpr (!SPEC) {
             // wave-synchronous root phase: chains that have finished their root solves go on when no chain of the
             // wavefront is in one any more
@@ -569,7 +591,7 @@ void q_phase_kernel(const QArgs a_in) {
             // chain queue with root fast trips: the groups of a wavefront take their next chains TOGETHER, when all of them
             // have finished (ST_NEXT), so that the root solves of the new chains run as fast trips too (the queue hands the
             // chains out in the order of their expected length: the four of a wavefront finish close to each other)
-            if (a.queue_slots > 0 && a.root_fast > 0) {
+            if (kCtlWord ? (ctl_word & CW_QUEUE) != 0 : (a.queue_slots > 0 && a.root_fast > 0)) {
                 const bool busy = st != ST_DONE && st != ST_NEXT;
                 if (!__any(busy) && __any(st == ST_NEXT)) {
                     if (st == ST_NEXT) {
@@ -624,7 +646,7 @@ void q_phase_kernel(const QArgs a_in) {
         // root passes weigh the trunk keypoints only: when every live chain of the wave is in one, the kinematics stop at
         // the ancestors of those keypoints (the other sites contribute exact zeros, written as such below)
         const bool root_pass = !a.single && kind < 2;
-        const int n_mlev_root_a = LEAN ? a.fk3r_n : a.n_mlev_root;  // (lean: the pruned split-kinematics program, if the call has one)
+        const int n_mlev_root_a = LEAN ? (kCtlWord ? fk3r_pin : (int)a.fk3r_n) : a.n_mlev_root;  // (lean: the pruned split-kinematics program, if the call has one)
         const int n_ml_root = (n_mlev_root_a > 0 && !__any(live_in && !root_pass)) ? n_mlev_root_a : 0;
         // root fast trip: only the root coordinates are staged and only the root joint's local transform is refreshed
         // (lite) once the other joints' local quaternions sit untouched in their ja entries
@@ -642,6 +664,7 @@ void q_phase_kernel(const QArgs a_in) {
             tail_ok = ok;
         }
         const bool lite = fast_trip && !__any(live_in && !ql_fresh);
+        PROF_SUB(2);  // root phase, chain queue, votes
 
         // the world entry of the transform array (the gradient pass of the previous trip left its range sums there)
         if (!LEAN && lg == 0) { st_tpos(bx, V3{0.f, 0.f, 0.f}); st_tquat(bx, Q4{1.f, 0.f, 0.f, 0.f}); }
@@ -655,7 +678,17 @@ void q_phase_kernel(const QArgs a_in) {
         // of the pre-pass's first round.)
         auto free0_prepass = [&](const float v, const int qord) {
             const int gb = lane - lg;
-            const float qw = __shfl(v, gb + 3, 64), qx = __shfl(v, gb + 4, 64), qy = __shfl(v, gb + 5, 64), qz = __shfl(v, gb + 6, 64);
+            float qw, qx, qy, qz;
+#ifndef STAC_NO_ROWBCAST
+            if constexpr (LEAN && SPEC == 0 && G == 16) {
+                // (a 16-lane group is one DPP row: lanes 3 .. 6 of the row broadcast inside it, four moves instead of four trips
+                //  through the LDS crossbar that the norm below waits for)
+                qw = row_bcast<3>(v); qx = row_bcast<4>(v); qy = row_bcast<5>(v); qz = row_bcast<6>(v);
+            } else
+#endif
+            {
+                qw = __shfl(v, gb + 3, 64); qx = __shfl(v, gb + 4, 64); qy = __shfl(v, gb + 5, 64); qz = __shfl(v, gb + 6, 64);
+            }
             const float n = __builtin_sqrtf(FMA(qz, qz, FMA(qy, qy, FMA(qx, qx, qw * qw))));
             const float dn = n + (n == 0.0f ? 1e-6f : 0.0f);
             if constexpr (LEAN) {
@@ -690,7 +723,9 @@ void q_phase_kernel(const QArgs a_in) {
             // root fast trip on a free root: staging and the pre-pass in one go
             const float pt = (st_in == ST_VG_Y) ? y[0] : ((st_in == ST_LS) ? CAND(0, lg) : x[0]);
             const float mi = (mbits & 1u) ? 1.0f : 0.0f;
-            free0_prepass((1.0f - mi) * q0[0] + mi * pt, a.free0p - 1);
+            const float v = (1.0f - mi) * q0[0] + mi * pt;
+            PROF_SUB(3);  // staging (root fast trip: the point selection; the stores are the pre-pass's)
+            free0_prepass(v, a.free0p - 1);
         } else if (lite) {
             if (lg < a.root_fast) {  // (the root coordinates are elements 0 .. root_fast - 1 <= G: register 0)
                 const float pt = (st_in == ST_VG_Y) ? y[0] : ((st_in == ST_LS) ? CAND(0, lg) : x[0]);
@@ -729,9 +764,11 @@ void q_phase_kernel(const QArgs a_in) {
                 if (e < nq && !(a.free0p && e < 7)) qe[e] = v;
             }
         }
+        PROF_SUB(3);  // staging stores
         if (a.free0p) free0_prepass(v0, a.free0p - 1);
         }
         wave_sync();
+        PROF_SUB(4);  // the free root's pre-pass, wave_sync()
         PROF_TICK(1);  // stage
 
         if (!(lite && a.free0p)) {  // (a root fast trip on a free root has nothing else to prepare)
@@ -1653,6 +1690,7 @@ void q_phase_kernel(const QArgs a_in) {
         PROF_ROOT(lite);
     }
     PROF_FLUSH(a);
+    PROF_FLUSH_SUB(a);
 }
 
 // ------------------------------------------------------------------------------------------------

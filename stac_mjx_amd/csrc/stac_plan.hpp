@@ -279,7 +279,7 @@ struct QArgs {
     float *err_out;         // [C,F]      (single: state_out [N,4])
     uint32_t *counters_out; // [C,F,4] or null
     float *q_carry_out;     // [C,nq] or null
-    unsigned long long *prof;  // diagnostic builds (-DSTAC_PROFILE) only: [16] per-phase cycle sums
+    unsigned long long *prof;  // diagnostic builds (-DSTAC_PROFILE) only: [16] per-phase cycle sums (+ [8] sub-stamps of the loop head: PG kernel)
 };
 
 // ---- optional LM solver (stac_lm.hip): per solve-kind tables in one global-memory blob of 32-bit words -----

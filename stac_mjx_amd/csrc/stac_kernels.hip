@@ -494,6 +494,21 @@ void q_phase_kernel(const QArgs a_in) {
 #else
     constexpr bool kCtlWord = false;
 #endif
+    // Lean throughput kernels: the rounds of lanes that a phase runs "at once" are written loads first, stores last (a store to
+    // LDS between two rounds keeps the second round's loads behind it, and so does a branch).  The latency kernels keep the round-by-round
+    // code: a lone wavefront pays per instruction.  STAC_SBS selects the parts in experiment builds: 1 pre-pass, 2 joint gradients, 4 site
+    // pass, 8 the root fast trip's wrench sum, 16 the lane's entries of the gradient vector.  (profiles/r09/NOTES.md)
+#ifndef STAC_SBS
+#define STAC_SBS 31
+#endif
+#ifndef STAC_SBS_GRAD_T
+#define STAC_SBS_GRAD_T 2  // (rounds of the joint gradients whose data are in flight together: three at once need 195 registers)
+#endif
+    constexpr bool kSbsPre = LEAN && SPEC == 0 && (STAC_SBS & 1);
+    constexpr bool kSbsGrad = LEAN && SPEC == 0 && (STAC_SBS & 2);
+    constexpr bool kSbsSite = SITEPIN && LEAN && SPEC == 0 && G == 16 && (STAC_SBS & 4);  // (the rounds' records are the pinned ones)
+    constexpr bool kSbsRoot = LEAN && SPEC == 0 && (STAC_SBS & 8);
+    constexpr bool kSbsGnew = LEAN && SPEC == 0 && (STAC_SBS & 16);
     enum : uint32_t { CW_ROOT_FAST = 0xFFu, CW_HAND = 1u << 8, CW_QUEUE = 1u << 9 };
     uint32_t ctl_word = 0;
     int32_t fk3r_pin = 0;
@@ -779,7 +794,21 @@ void q_phase_kernel(const QArgs a_in) {
                 // joint again: the same value to the same words.
                 // (throughput kernels: a lone wavefront of the latency kernels pays per instruction, dependent or not)
                 constexpr int U = SPEC != 0 ? (G == 32 ? 2 : 1) : (G == 16 ? 3 : 2);
-                if constexpr (PREPIN) {  // (the lane's joints of the first PJ rounds out of registers: LATPIN, above)
+                if constexpr (PREPIN && kSbsPre) {
+                    // the pinned rounds side by side: every round's coordinate is read before any round stores (a store to LDS and a
+                    // later read through another pointer may alias, so a store between two rounds' reads keeps them in order), and no
+                    // branch between the rounds (the scheduler does not move instructions across one).  The pins of a lane whose
+                    // round has no joint hold the last joint's record: the same value to the same words.
+                    float qv[PJ], sn[PJ], cs[PJ];
+#pragma unroll
+                    for (int u = 0; u < PJ; ++u) qv[u] = qe[pin_jad[u]];
+                    __builtin_amdgcn_sched_barrier(0);  // (every read is issued before the first chain starts)
+#pragma unroll
+                    for (int u = 0; u < PJ; ++u) sincos_((qv[u] - pin_jq0[u]) * 0.5f, &sn[u], &cs[u]);
+#pragma unroll
+                    for (int u = 0; u < PJ; ++u)
+                        *reinterpret_cast<float4 *>(CB + pin_jout[u]) = float4{cs[u], pin_jax[u][0] * sn[u], pin_jax[u][1] * sn[u], pin_jax[u][2] * sn[u]};
+                } else if constexpr (PREPIN) {  // (the lane's joints of the first PJ rounds out of registers: LATPIN, above)
 #pragma unroll
                     for (int u = 0; u < PJ; ++u) {
                         if (u > 0 && 1 + u * G >= H.naj) break;  // (wave-uniform: no joint left for any lane)
@@ -790,6 +819,27 @@ void q_phase_kernel(const QArgs a_in) {
                     }
                 }
                 for (int j0 = lg + 1 + (PREPIN ? PJ * G : 0); j0 < H.naj; j0 += U * G) {
+                    if constexpr (kSbsPre) {  // (the same shape: records, coordinates, the sincos chains, then the stores)
+                        int jj[U], ad[U];
+                        float q0j[U], ang[U], sn[U], cs[U];
+                        float4 ax[U];
+#pragma unroll
+                        for (int u = 0; u < U; ++u) {
+                            jj[u] = min(j0 + u * G, H.naj - 1);
+                            const float *jr = jrec + 12 * jj[u];
+                            ad[u] = reinterpret_cast<const int *>(jr)[1];
+                            q0j[u] = lds4(jr + 4).w;  // pos, q0
+                            ax[u] = lds4(jr + 8);     // axis, range id
+                        }
+#pragma unroll
+                        for (int u = 0; u < U; ++u) ang[u] = qe[ad[u]] - q0j[u];
+#pragma unroll
+                        for (int u = 0; u < U; ++u) sincos_(ang[u] * 0.5f, &sn[u], &cs[u]);
+#pragma unroll
+                        for (int u = 0; u < U; ++u)
+                            *reinterpret_cast<float4 *>(CB + H.c3_ql + 4 * jj[u]) = float4{cs[u], ax[u].x * sn[u], ax[u].y * sn[u], ax[u].z * sn[u]};
+                        continue;
+                    }
 #pragma unroll
                     for (int u = 0; u < U; ++u) {
                         const int j = min(j0 + u * G, H.naj - 1);
@@ -926,6 +976,54 @@ void q_phase_kernel(const QArgs a_in) {
                 }
 #pragma unroll
                 for (int r = 0; r < NSR; ++r) term[r] = r == trunk_r ? v : 0.0f;
+            } else if constexpr (kSbsSite) {
+                // the rounds of sites side by side: site_term's operations in its order, but every round's body position and quaternion
+                // are read before any round stores its wrench, and the stores sit under one test.  A lane whose round has no site reads
+                // the last site's body (its pins hold that record) and neither stores nor contributes a term.
+                V3 bp[NSR], sx[NSR];
+                float4 bq[NSR];
+                float rx[NSR], ry[NSR], rz[NSR];
+                bool wz[NSR];
+                int s3[NSR];
+#pragma unroll
+                for (int r = 0; r < NSR; ++r) s3[r] = pin_s3[r];
+                if (n_ml_root > 0) {  // (wave-uniform: a root pass ran the pruned program -- one branch in front of the rounds, none between them)
+#pragma unroll
+                    for (int r = 0; r < NSR; ++r) s3[r] = site3[min(r * G + lg, K - 1)];
+                }
+#pragma unroll
+                for (int r = 0; r < NSR; ++r) {
+                    bp[r] = ld3(CB + (s3[r] & 0xFFFF));
+                    bq[r] = lds4(CB + (int)((unsigned)s3[r] >> 16));
+                }
+#pragma unroll
+                for (int r = 0; r < NSR; ++r) {
+                    const float4 sr = pin_sr[r];
+                    sx[r] = add3(bp[r], rotate(V3{sr.x, sr.y, sr.z}, Q4{bq[r].x, bq[r].y, bq[r].z, bq[r].w}));
+                    const float w = trunk_w ? (((kpw_bits >> r) & 1u) ? 1.f : 0.f) : 1.f;
+                    wz[r] = w == 0.0f;
+                    rx[r] = wz[r] ? 0.0f : (kpr[r][0] - sx[r].x) * w;
+                    ry[r] = wz[r] ? 0.0f : (kpr[r][1] - sx[r].y) * w;
+                    rz[r] = wz[r] ? 0.0f : (kpr[r][2] - sx[r].z) * w;
+                    term[r] = r * G + lg < K ? FMA(rz[r], rz[r], FMA(ry[r], ry[r], rx[r] * rx[r])) : 0.0f;
+                }
+                if (any_grad) {
+                    V3 f[NSR], tq[NSR];
+#pragma unroll
+                    for (int r = 0; r < NSR; ++r) {
+                        f[r] = V3{-2.0f * rx[r], -2.0f * ry[r], -2.0f * rz[r]};
+                        tq[r] = cross3(sub3(sx[r], cref), f[r]);
+                        if (wz[r]) tq[r] = V3{0.0f, 0.0f, 0.0f};
+                    }
+#pragma unroll
+                    for (int r = 0; r < NSR; ++r) {
+                        if (r * G + lg < K) {
+                            const int sp = __builtin_bit_cast(int, pin_sr[r].w) >> 16;
+                            st_tpos(sw + kXf * sp, f[r]);
+                            st_tvec2(sw + kXf * sp, tq[r]);
+                        }
+                    }
+                }
             } else {
 #pragma unroll
             for (int r = 0; r < NSR; ++r) {
@@ -1165,8 +1263,34 @@ void q_phase_kernel(const QArgs a_in) {
                 const int co = lg < 3 ? lg : kXq + lg - 3;
                 const float *src = sw + co;
                 float acc = 0.f;
+                if constexpr (kSbsRoot) {
+                    // eight weighted sites per LDS round trip instead of one: the sites of the batch come out of the (wave-uniform) masks
+                    // in scalar code, their reads are issued together and added in ascending site order, as the loops below add them.  A
+                    // short batch reads its last weighted site again and drops the addition (never the entry of an unweighted site: a
+                    // root fast trip does not write those).
+                    constexpr int RB = 8;
+                    uint64_t m = (uint64_t)a.root_trunk_lo | ((uint64_t)a.root_trunk_hi << 32);
+                    while (m) {
+                        int idx[RB];
+                        bool on[RB];
+                        int last = 0;
+#pragma unroll
+                        for (int u = 0; u < RB; ++u) {
+                            on[u] = m != 0;
+                            if (on[u]) { last = __builtin_ctzll(m); m &= m - 1; }
+                            idx[u] = last;
+                        }
+                        float v[RB];
+#pragma unroll
+                        for (int u = 0; u < RB; ++u) v[u] = src[kXf * idx[u]];
+                        __builtin_amdgcn_sched_barrier(0);  // (the batch's reads are all issued before the first addition waits for one)
+#pragma unroll
+                        for (int u = 0; u < RB; ++u) acc = on[u] ? acc + v[u] : acc;
+                    }
+                } else {
                 for (uint32_t m = a.root_trunk_lo; m; m &= m - 1) acc = acc + src[kXf * __builtin_ctz(m)];
                 for (uint32_t m = a.root_trunk_hi; m; m &= m - 1) acc = acc + src[kXf * (32 + __builtin_ctz(m))];
+                }
                 CB[(LEAN ? H.c3_rw0 : H.c_rw + kXf * rid0) + co] = acc;  // (lean: beside the joint-local quaternions, which a fast trip keeps)
             }
             wave_sync();
@@ -1217,9 +1341,52 @@ void q_phase_kernel(const QArgs a_in) {
                 if constexpr (LEAN && SPEC == 0) {
                     // three rounds of lanes at once, as in the pre-pass (a lane without a joint left repeats the last one)
                     constexpr int U = G == 16 ? 3 : 2;
+                    if constexpr (kSbsGrad) {
+                        // joint_gradient's hinge path in three steps over the U rounds -- the records, then the data they point to, then
+                        // the formulas -- and the U stores behind all of it: the operands and the order of operations of every value are
+                        // joint_gradient's, and two LDS round trips are in series instead of two per round
+                        const int *jw3 = reinterpret_cast<const int *>(P + H.off3_site) + K;
+                        constexpr int T = STAC_SBS_GRAD_T;  // rounds whose data are in flight together
+                        for (int jb = lg + j0; jb < naj_g; jb += U * G) {
+                            int ad[U], jw[U];
+                            float4 ax[U];
+#pragma unroll
+                            for (int u = 0; u < U; ++u) {
+                                const int j = min(jb + u * G, naj_g - 1);
+                                const float *jr = jrec + 12 * j;
+                                ad[u] = reinterpret_cast<const int *>(jr)[1];
+                                ax[u] = lds4(jr + 8);  // axis, range id
+                                jw[u] = jw3[j];
+                            }
+#pragma unroll
+                            for (int u0 = 0; u0 < U; u0 += T) {
+                                constexpr int TT = T < U ? T : U;
+                                float4 pq[TT];
+                                V3 Fs[TT], T0[TT], an[TT];
+                                float gv[TT];
+#pragma unroll
+                                for (int u = u0; u < u0 + T && u < U; ++u) {
+                                    const float *rw = CB + H.c_rw + kXf * __builtin_bit_cast(int, ax[u].w);
+                                    Fs[u - u0] = ld_tpos(rw);
+                                    T0[u - u0] = ld_tvec2(rw);
+                                    an[u - u0] = ld3(CB + (jw[u] & 0xFFFF));
+                                    pq[u - u0] = lds4(CB + (int)((unsigned)jw[u] >> 16));
+                                }
+#pragma unroll
+                                for (int u = u0; u < u0 + T && u < U; ++u) {
+                                    const int v = u - u0;
+                                    const V3 tau = sub3(T0[v], cross3(sub3(an[v], cref), Fs[v]));
+                                    gv[v] = dot3(rotate(V3{ax[u].x, ax[u].y, ax[u].z}, Q4{pq[v].x, pq[v].y, pq[v].z, pq[v].w}), tau);
+                                }
+#pragma unroll
+                                for (int u = u0; u < u0 + T && u < U; ++u) gg[ad[u]] = gv[u - u0];
+                            }
+                        }
+                    } else {
                     for (int jb = lg + j0; jb < naj_g; jb += U * G) {
 #pragma unroll
                         for (int u = 0; u < U; ++u) joint_gradient(min(jb + u * G, naj_g - 1), CB, cref, gg);
+                    }
                     }
                 } else {
                     for (int j = lg + j0; j < naj_g; j += G) joint_gradient(j, CB, cref, gg);
@@ -1227,6 +1394,19 @@ void q_phase_kernel(const QArgs a_in) {
             }
             wave_sync();
             const uint32_t abits = SPEC ? mbits : ((LEAN ? act_bits : MB[nkinds * G + lg]) & mbits);  // optimised coordinates that HAVE a gradient entry
+            if constexpr (kSbsGnew) {
+                // the lane's NQR entries of the gradient vector in one LDS round trip: read side by side, then selected.  (Written as
+                // "read, then select" alone -- below -- the compiler sinks every read into a branch on its select's condition: NQR round
+                // trips in series.  The empty statement makes the values opaque, so the reads stay where they are.)
+                float gv[NQR];
+#pragma unroll
+                for (int r = 0; r < NQR; ++r) { const int e = r * G + lg; gv[r] = gg[e < nq ? e : 0]; }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int r = 0; r < NQR; ++r) asm volatile("" : "+v"(gv[r]));
+#pragma unroll
+                for (int r = 0; r < NQR; ++r) gnew[r] = (r * G + lg < nq && ((abits >> r) & 1u)) ? gv[r] : gnew[r];
+            } else {
 #pragma unroll
             for (int r = 0; r < NQR; ++r) {
                 const int e = r * G + lg;
@@ -1236,6 +1416,7 @@ void q_phase_kernel(const QArgs a_in) {
                 } else {
                     if (e < nq && ((abits >> r) & 1u)) gnew[r] = gg[e];
                 }
+            }
             }
             if (a.free0p) {  // the free root joint: one component per lane, its four divisions side by side
                 const float gv = free0_gradient(CB, cref, CB + H.c_rw + kXf * __builtin_bit_cast(int, jrec[11]), a.free0p - 1, lg);

@@ -260,6 +260,31 @@ int32_t stac_jpeg_encode(int64_t N, int32_t width, int32_t height, int32_t quali
                          uint8_t *out, int64_t out_capacity, int64_t *frame_offset, void *workspace, int64_t workspace_bytes,
                          void *stream);
 
+/* ---- Post-processing of a continuous run on the device (no stac_model needed; the current device is used) ----------
+ * DESIGN.md "Post-processing on the GPU".  Row-major float32 arrays; D = the flattened trailing size of a frame. */
+
+/* HOST.  Rows of the stitched array of C clip windows of F + overlap frames: R = F + overlap + max(C-2, 0) * F +
+ * max(F - overlap, 0) (0 for C == 0); that is C * F when C >= 2 and F >= overlap.  Negative (STAC_ERR_INVALID) for C < 0,
+ * F < 1 or overlap outside 1..32. */
+int64_t stac_post_stitch_rows(int64_t C, int32_t F, int32_t overlap);
+
+/* utils.handle_edge_effects on one array (stac_mjx/utils.py:393-461): src[C, F+overlap, D] -> dst[dst_rows, D], where
+ * dst_rows must equal stac_post_stitch_rows(C, F, overlap).  Rows: clip 0 whole; clips 1..C-2 from frame `overlap` on;
+ * clip C-1 frames overlap..F-1 (for C == 1 that is clip 0 again, as the reference slices).  A row from (c, t) with t >= F
+ * and c < C-1 is (float)((1 - m[t-F]) * (double)src[c,t] + m[t-F] * (double)src[c+1,t-F]), every other row a copy; all
+ * reads are of unfaded values.  mask_host: HOST double[overlap], the fade weights (copied during the call).  src and dst
+ * must not overlap.  C == 0: nothing is done. */
+int32_t stac_post_stitch(const float *src, int64_t C, int32_t F, int32_t overlap, int32_t D, const double *mask_host,
+                         float *dst, int64_t dst_rows, void *stream);
+
+/* utils.compute_velocity_from_kinematics on every clip of F frames (stac_mjx/utils.py:302-347, called per clip by
+ * main.py:118-133): qpos[N, nq] with N % F == 0 -> qvel[N, nq - (freejoint ? 1 : 0)].  The last frame of a clip differences
+ * against itself.  Free joint (nq >= 7): columns 0..2 translation, 3..5 the root gyro from the normalised quaternion
+ * difference (float32 product and norm, axis-angle in double), 6.. joints clipped to +-max_qvel; without one every
+ * column is a clipped difference.  dt and max_qvel are rounded to float32 as numpy does.  N == 0: nothing is done. */
+int32_t stac_post_qvel(const float *qpos, int64_t N, int32_t nq, int32_t F, double dt, int32_t freejoint, double max_qvel,
+                       float *qvel, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,8 +30,9 @@ _STAC_REQUIRED = (
 _STAC_OPTIONAL = ("num_clips",)
 _MUJOCO_REQUIRED = ("solver", "iterations", "ls_iterations")
 # Engine extensions (not in the reference schema); all optional.  (lm_maxiter: accepted steps per solve of solver = lm, default 20
-# -- 40 until round 3; gather: auto | rank0 | all | none, resolved per run by main.run_stac, the caller's config is never modified)
-_STAC_EXTENSIONS = ("solver", "lanes_per_chain", "device", "time_indices", "fit_frames_per_clip", "reference_marker_order", "gather", "gather_max_bytes", "lm_maxiter")
+# -- 40 until round 3; gather: auto | rank0 | all | none, resolved per run by main.run_stac, the caller's config is never modified;
+# postprocess: host (default) | gpu -- where the cross-fade stitch and qvel of a run happen, read from the caller's config)
+_STAC_EXTENSIONS = ("solver", "lanes_per_chain", "device", "time_indices", "fit_frames_per_clip", "reference_marker_order", "gather", "gather_max_bytes", "lm_maxiter", "postprocess")
 _MODEL_EXTENSIONS = ("KP_NAMES_LABEL3D_PATH",)
 
 
@@ -175,6 +176,8 @@ def validate_config(cfg: dict) -> ConfigNode:
     for k in ("skip_fit_offsets", "skip_ik_only", "infer_qvels", "continuous"):
         if not isinstance(stac[k], bool):
             raise ConfigError(f"stac.{k} must be a bool")
+    if stac.get("postprocess", "host") not in ("host", "gpu"):
+        raise ConfigError(f"stac.postprocess must be host or gpu, not {stac['postprocess']!r}")
     return _wrap({"model": model, "stac": stac})
 
 

@@ -17,6 +17,7 @@
 #include "stac_shapes.hpp"
 #include "stac_render.hpp"
 #include "stac_jpeg.hpp"
+#include "stac_post.hpp"
 
 namespace stac {
 hipError_t launch_q_phase(const QArgs &a, const QInst &inst, int wpb, size_t lds_bytes, hipStream_t s);
@@ -33,6 +34,10 @@ hipError_t launch_chain_order(const float *kp, int C, int F, int K, const float 
                               float rx, float ry, float rz, uint32_t *hist, uint32_t *keybits, int32_t *perm, int32_t *place,
                               hipStream_t s);
 hipError_t launch_jpeg_encode(const JpegCall &C, const JpegHeader &Hd, hipStream_t s);
+hipError_t launch_post_stitch(const float *src, float *dst, int64_t C, int32_t F, int32_t ov, int32_t D, int64_t R, const PostMask &M,
+                              hipStream_t s);
+hipError_t launch_post_qvel(const float *qpos, float *qvel, int64_t N, int32_t nq, int32_t F, int32_t freejoint, float dt,
+                            float max_qvel, hipStream_t s);
 }  // namespace stac
 
 using namespace stac;
@@ -2246,6 +2251,43 @@ extern "C" int32_t stac_jpeg_encode(int64_t N, int32_t width, int32_t height, in
     return STAC_OK;
 }
 
+
+// ---- Post-processing of a continuous run (stac_post.hip): every argument is checked before the device is touched --------
+extern "C" int64_t stac_post_stitch_rows(int64_t C, int32_t F, int32_t overlap) {
+    const int64_t R = post_stitch_rows(C, F, overlap);
+    if (R < 0) return fail(STAC_ERR_INVALID, "stac_post_stitch_rows: C >= 0, F >= 1, overlap 1..32");
+    return R;
+}
+
+extern "C" int32_t stac_post_stitch(const float *src, int64_t C, int32_t F, int32_t overlap, int32_t D, const double *mask_host,
+                                    float *dst, int64_t dst_rows, void *stream) {
+    const int64_t R = post_stitch_rows(C, F, overlap);
+    if (R < 0 || D < 1) return fail(STAC_ERR_INVALID, "stac_post_stitch: C >= 0, F >= 1, overlap 1..32, D >= 1");
+    if (dst_rows != R)
+        return fail(STAC_ERR_INVALID, "stac_post_stitch: dst_rows = " + std::to_string(dst_rows) + ", the stitched array has " +
+                                          std::to_string(R) + " rows (stac_post_stitch_rows)");
+    if (C == 0) return STAC_OK;
+    if (!src || !dst || !mask_host) return fail(STAC_ERR_INVALID, "stac_post_stitch: null src / dst / mask_host");
+    PostMask M{};
+    for (int k = 0; k < overlap; ++k) M.m[k] = mask_host[k];
+    const hipError_t e = launch_post_stitch(src, dst, C, F, overlap, D, R, M, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(STAC_ERR_HIP, std::string("stac_post_stitch: ") + hipGetErrorString(e));
+    return STAC_OK;
+}
+
+extern "C" int32_t stac_post_qvel(const float *qpos, int64_t N, int32_t nq, int32_t F, double dt, int32_t freejoint, double max_qvel,
+                                  float *qvel, void *stream) {
+    if (N < 0 || F < 1 || nq < 1 || (freejoint && nq < 7))
+        return fail(STAC_ERR_INVALID, "stac_post_qvel: N >= 0, F >= 1, nq >= 1 (nq >= 7 with a free joint)");
+    if (N % F != 0)
+        return fail(STAC_ERR_INVALID, "stac_post_qvel: " + std::to_string(N) + " rows are not whole clips of " + std::to_string(F));
+    if (dt == 0.0) return fail(STAC_ERR_INVALID, "stac_post_qvel: dt == 0");
+    if (N == 0) return STAC_OK;
+    if (!qpos || !qvel) return fail(STAC_ERR_INVALID, "stac_post_qvel: null qpos / qvel");
+    const hipError_t e = launch_post_qvel(qpos, qvel, N, nq, F, freejoint ? 1 : 0, (float)dt, (float)max_qvel, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(STAC_ERR_HIP, std::string("stac_post_qvel: ") + hipGetErrorString(e));
+    return STAC_OK;
+}
 
 // Diagnostics, not part of include/stac_hip.h (tests/test_fk3_rounds_host.py, tests/test_gpu_fk3_rounds.py): the split-kinematics
 // program of a model, built on the host alone -- no device is touched.  trunk_kps == NULL: the full program; else the pruned program

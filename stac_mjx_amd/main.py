@@ -24,7 +24,8 @@ def run_stac(cfg, kp_data, kp_names, base_path=None, *, setup=None, device=None)
 
     Returns ``(fit_offsets_path, ik_only_path or None)``.  Raises ``ValueError`` when ``kp_data`` columns
     do not match ``3 * len(kp_names)`` or ``n_frames_per_clip`` does not divide the frame count.
-    ``infer_qvels`` runs the reference's finite-difference post-processing on the host.
+    ``infer_qvels`` runs the reference's finite-difference post-processing on the host, or, like the
+    cross-fade of a continuous run, on the device with ``stac.postprocess: gpu`` (DESIGN.md "Post-processing on the GPU").
     """
     base_path = Path.cwd() if base_path is None else Path(base_path)
     kp_data = np.asarray(kp_data)
@@ -46,6 +47,15 @@ def run_stac(cfg, kp_data, kp_names, base_path=None, *, setup=None, device=None)
         if fit_cfg.stac.continuous:
             raise ValueError("stac.gather = none writes per-rank shards, but stac.continuous cross-fades neighbouring "
                              "clips across shard borders: use gather = rank0 (or all, or auto) for continuous runs")
+
+    # stac.postprocess (engine extension, read from the caller's config like gather): "host" (default) = the numpy functions
+    # of utils.py below; "gpu" = ik_only stitches and infers qvel on the device (post.py) and the two host steps are skipped
+    post_gpu = _postprocess_mode(cfg) == "gpu"
+    if post_gpu and not cfg.stac.skip_ik_only and bool(cfg.stac.get("reference_marker_order", False)):
+        fit_cfg = cfg if not cfg.stac.skip_fit_offsets else io.load_stac_data(fit_offsets_path)[0]
+        if fit_cfg.stac.continuous:
+            raise ValueError("stac.postprocess = gpu cannot cross-fade marker_sites in the reference's frame-major row order "
+                             "(stac.reference_marker_order: true): only postprocess = host reproduces fading across it")
 
     if not cfg.stac.skip_fit_offsets:
         kps = kp_data[: cfg.stac.n_fit_frames]
@@ -80,14 +90,15 @@ def run_stac(cfg, kp_data, kp_names, base_path=None, *, setup=None, device=None)
     if sharded and cfg.stac.continuous:  # (explicit gather = none with a fit file whose config turned out continuous)
         raise ValueError("stac.gather = none writes per-rank shards, but stac.continuous cross-fades neighbouring "
                          "clips across shard borders: use gather = rank0 (or all, or auto) for continuous runs")
-    ik_data = stac.ik_only(kp_data, fit_data.offsets, gather=mode)
+    post = {"continuous": bool(cfg.stac.continuous), "n_frames_per_clip": F, "infer_qvels": bool(cfg.stac.infer_qvels)} if post_gpu else None
+    ik_data = stac.ik_only(kp_data, fit_data.offsets, gather=mode, **({"post": post} if post_gpu else {}))
     if rank != 0 and not sharded and mode != "all":
         dist.barrier()  # this rank holds its own shard only: rank 0 post-processes and writes the gathered result
         return fit_offsets_path, io.resolve_output_path(ik_only_path)
-    if cfg.stac.continuous:
+    if cfg.stac.continuous and post is None:
         ik_data = utils.handle_edge_effects(ik_data, F)
     print(f"Final qpos shape: {ik_data.qpos.shape}")
-    if cfg.stac.infer_qvels and ik_data.qpos.shape[0]:  # main.py:118-133: per clip of n_frames_per_clip frames
+    if post is None and cfg.stac.infer_qvels and ik_data.qpos.shape[0]:  # main.py:118-133: per clip of n_frames_per_clip frames
         batched = ik_data.qpos.reshape((-1, F, ik_data.qpos.shape[-1]))
         qvels = [utils.compute_velocity_from_kinematics(c, dt=stac._timestep, freejoint=stac._freejoint) for c in batched]
         ik_data.qvel = np.stack(qvels).reshape(-1, qvels[0].shape[-1])
@@ -112,6 +123,14 @@ def run_stac(cfg, kp_data, kp_names, base_path=None, *, setup=None, device=None)
     dist.barrier()
     print(f"Saved ik_only to {ik_only_path}. Finished in {(time.time() - start) / 60:.2f} minutes")
     return fit_offsets_path, ik_only_path
+
+
+def _postprocess_mode(cfg) -> str:
+    """``stac.postprocess``: "host" (default) | "gpu"."""
+    mode = str(cfg.stac.get("postprocess", "host") or "host")
+    if mode not in ("host", "gpu"):
+        raise ValueError(f"stac.postprocess must be host or gpu, not {mode!r}")
+    return mode
 
 
 GATHER_AUTO_MAX_BYTES = 1 << 30  # above this much output a multi-GPU run keeps per-rank shard files ("auto")

@@ -141,10 +141,17 @@ class Stac:
         return self._package_data(res, kp_np.reshape(kp_np.shape[0] * n_per, kp_np.shape[-1]), batched=fpc > 0)
 
     # -- ik_only (stac.py:356-454) --------------------------------------------------------------------------
-    def ik_only(self, kp_data, offsets, gather=None) -> StacData:
+    def ik_only(self, kp_data, offsets, gather=None, *, post=None) -> StacData:
         """Inverse kinematics with fixed offsets; clips are independent chains, sharded over ranks.  ``gather`` (multi-GPU
-        result placement: "rank0" | "all" | "none") overrides ``stac.gather`` for this call (run_stac resolves "auto")."""
+        result placement: "rank0" | "all" | "none") overrides ``stac.gather`` for this call (run_stac resolves "auto").
+
+        ``post`` (``stac.postprocess: gpu``, engine extension): ``{"continuous", "n_frames_per_clip", "infer_qvels"}`` as the fit
+        file's config decided them.  The cross-fade stitch of ``utils.handle_edge_effects`` and the ``qvel`` of
+        ``utils.compute_velocity_from_kinematics`` then run on the device (``post.py``), wherever the full tensors are, only
+        the stitched arrays cross to the host and the returned ``StacData`` carries ``qvel``.  None: nothing of that."""
         eng = self.engine
+        if post is not None:
+            post = self._check_post(post, gather)
         tick = self._tick
         tick(None)
         batched = utils.batch_kp_data(np.asarray(kp_data, dtype=np.float32), int(self.cfg.stac.n_frames_per_clip),
@@ -164,9 +171,46 @@ class Stac:
         _, mean, std = self._get_error_stats(res["frame_error"].cpu().numpy())
         self._log(f"Mean: {mean}\nStandard deviation: {std}")
         self._offsets = eng.get_site_pos()
-        data = self._package_data(res, batched, batched=True)
+        extra = None
+        if post is not None and not (dist.is_dist() and self._gather_mode(gather) == "rank0" and dist.world()[0] != 0):
+            # (a rank that kept only its shard of a rank0 gather has nothing to post-process: rank 0 does it)
+            extra = self._postprocess_gpu(res, batched if dist.is_dist() else kp, post)
+            tick("postprocess_s")
+        data = self._package_data(res, batched, batched=True, post=extra)
         tick("d2h_and_packing_s")
         return data
+
+    def _check_post(self, post, gather):
+        """The ``post`` argument of ik_only, checked before any work is done."""
+        out = {"continuous": bool(post["continuous"]), "n_frames_per_clip": int(post["n_frames_per_clip"]),
+               "infer_qvels": bool(post["infer_qvels"])}
+        if out["n_frames_per_clip"] < 1:
+            raise ValueError(f"post: n_frames_per_clip = {out['n_frames_per_clip']}")
+        if out["continuous"] and bool(self.cfg.stac.get("reference_marker_order", False)):
+            raise ValueError("stac.postprocess = gpu cannot cross-fade marker_sites in the reference's frame-major row order "
+                             "(stac.reference_marker_order: true): only the host path reproduces fading across it")
+        if out["continuous"] and dist.world()[1] > 1 and self._gather_mode(gather) == "none":
+            raise ValueError("stac.gather = none keeps per-rank shards, but a continuous run cross-fades neighbouring clips "
+                             "across shard borders: gather (rank0 or all) for continuous runs")
+        return out
+
+    def _postprocess_gpu(self, res, kp_clips, post):
+        """Stitch (continuous) and qvel (infer_qvels) of the flattened outputs on the device -> {name: device tensor}."""
+        from . import post as gpost
+
+        F, ov = post["n_frames_per_clip"], utils.CONTINUOUS_BATCH_OVERLAP
+        nq, nb, K = self.setup.tables.nq, self.setup.tables.nbody, self.setup.tables.nsite
+        kp_dev = torch.as_tensor(kp_clips).to(device=self.engine.device, dtype=torch.float32)
+        out = {"qpos": res["qpos"].reshape(-1, nq), "xpos": res["xpos"].reshape(-1, nb, 3), "xquat": res["xquat"].reshape(-1, nb, 4),
+               "marker_sites": res["marker_sites"].reshape(-1, K, 3), "kp_data": kp_dev.reshape(-1, kp_dev.shape[-1])}
+        if post["continuous"]:
+            for name, a in out.items():  # the flat rows as windows of F + 10, as handle_edge_effects reshapes them
+                if a.shape[0] % (F + ov) != 0:
+                    raise ValueError(f"cannot reshape {a.shape[0]} rows of {name} into windows of {F + ov} frames")
+                out[name] = gpost.stitch(a.reshape((-1, F + ov) + tuple(a.shape[1:])), F, ov)
+        if post["infer_qvels"] and out["qpos"].shape[0]:
+            out["qvel"] = gpost.infer_qvel(out["qpos"], F, self._timestep, self._freejoint)
+        return out
 
     def _tick(self, name):
         """Phase clock of ik_only for `bench.py --mode run` (``self.timings = {}`` switches it on; it synchronises the device
@@ -181,15 +225,19 @@ class Stac:
             self.timings[name] = self.timings.get(name, 0.0) + now - self._t_last
         self._t_last = now
 
-    def _gather(self, res, kp_clips, n_clips, lo, hi, mode=None):
-        """Multi-GPU result placement, ``stac.gather`` (engine extension): "rank0" (default) -- rank 0 packages every
-        clip, the other ranks keep (and return) their own shard; "all" -- every rank gets every clip (small runs,
-        tests); "none" -- every rank keeps its shard.  Returns (results, the keypoint clips that go with them)."""
+    def _gather_mode(self, mode=None) -> str:
         mode = str(mode or self.cfg.stac.get("gather", "rank0") or "rank0")
         if mode == "auto":  # run_stac resolves "auto" by output size before it calls ik_only; direct callers get rank0
             mode = "rank0"
         if mode not in ("rank0", "all", "none"):
             raise ValueError(f"stac.gather must be auto, rank0, all or none, not {mode!r}")
+        return mode
+
+    def _gather(self, res, kp_clips, n_clips, lo, hi, mode=None):
+        """Multi-GPU result placement, ``stac.gather`` (engine extension): "rank0" (default) -- rank 0 packages every
+        clip, the other ranks keep (and return) their own shard; "all" -- every rank gets every clip (small runs,
+        tests); "none" -- every rank keeps its shard.  Returns (results, the keypoint clips that go with them)."""
+        mode = self._gather_mode(mode)
         tensors = {k: v for k, v in res.items() if isinstance(v, torch.Tensor)}
         if mode == "all":
             return {k: dist.all_gather_clips(v, n_clips) for k, v in tensors.items()}, kp_clips
@@ -200,7 +248,7 @@ class Stac:
         return tensors, kp_clips[lo:hi]
 
     # -- packing (stac.py:456-503) ---------------------------------------------------------------------------
-    def _package_data(self, res, kp_data, batched=False) -> StacData:
+    def _package_data(self, res, kp_data, batched=False, post=None) -> StacData:
         """Clip-major flatten of every field.
 
         The reference flattens ``marker_sites`` frame-major when C > 1 and F > 1 (``stac.py:486``: a C-order
@@ -209,6 +257,13 @@ class Stac:
         ``stac.reference_marker_order: true`` reproduces the reference's row order of ``marker_sites`` exactly
         (row j = frame j // C of clip j % C) for consumers that undo it themselves."""
         nq, nb, K = self.setup.tables.nq, self.setup.tables.nbody, self.setup.tables.nsite
+        if post is not None:  # stac.postprocess = gpu: the arrays are stitched and flat already (_postprocess_gpu)
+            host = {k: v.cpu().numpy() for k, v in post.items()}
+            if batched and bool(self.cfg.stac.get("reference_marker_order", False)):  # (never a continuous run: _check_post)
+                ms = res["marker_sites"]
+                host["marker_sites"] = (ms.transpose(0, 1) if ms.dim() == 4 else ms).reshape(-1, K, 3).cpu().numpy()
+            return StacData(offsets=np.asarray(torch.as_tensor(self._offsets).cpu()).reshape(K, 3), names_qpos=self._part_names,
+                            names_xpos=self._body_names, kp_names=self._kp_names, **host)
         qpos = res["qpos"].reshape(-1, nq).cpu().numpy()
         xpos = res["xpos"].reshape(-1, nb, 3).cpu().numpy()
         xquat = res["xquat"].reshape(-1, nb, 4).cpu().numpy()

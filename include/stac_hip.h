@@ -285,6 +285,30 @@ int32_t stac_post_stitch(const float *src, int64_t C, int32_t F, int32_t overlap
 int32_t stac_post_qvel(const float *qpos, int64_t N, int32_t nq, int32_t F, double dt, int32_t freejoint, double max_qvel,
                        float *qvel, void *stream);
 
+/* ---- Filling missing keypoints before the fit (no stac_model needed; the current device is used) --------------------
+ * DESIGN.md "Filling missing keypoints".  Replaces the gap filling that every user of the reference writes by hand in
+ * front of stac_mjx.main.run_stac (stac_mjx/main.py:33-139 takes kp_data as it comes and has no answer to a NaN: the
+ * residual of q_loss, stac_mjx/stac_core.py:27-62, times a zero weight stays NaN). */
+enum { STAC_PREP_LINEAR = 0, STAC_PREP_HOLD = 1 };
+
+/* HOST.  Bytes of device workspace that stac_prep_fill needs for a series of n_frames x n_kp keypoints; it grows with
+ * both.  Negative (STAC_ERR_INVALID) for n_frames < 1 or n_kp < 1.  Replaces nothing in the reference: the workspace
+ * belongs to the caller like every buffer of this ABI. */
+int64_t stac_prep_fill_workspace(int64_t n_frames, int32_t n_kp);
+
+/* kp[n_frames, 3 * n_kp] -> out[n_frames, 3 * n_kp], gap[n_frames, n_kp] (int32), every element of both written once.
+ * Keypoint k is missing in frame t iff one of its three coordinates is NaN or +-inf.  Every track k on its own, with p
+ * the last valid frame before t and n the first valid frame after it: a valid keypoint is copied bit for bit, gap 0;
+ * a missing one becomes, per coordinate, (float)((double)a + ((double)b - (double)a) * ((double)(t-p) / (double)(n-p)))
+ * of the values a at p and b at n (STAC_PREP_LINEAR) or the value at the nearer of p and n, a tie to p (STAC_PREP_HOLD);
+ * with only one of p, n the value there; a track with no valid frame stays as it is.  gap = the length of the missing
+ * run the frame belongs to (n - p - 1; n for a leading run; n_frames - 1 - p for a trailing one; n_frames for an empty
+ * track; saturated to INT32_MAX).  workspace: device, 8-byte aligned, at least stac_prep_fill_workspace bytes, its
+ * contents do not matter; it may be reused once the call has finished on `stream`.  kp, out, gap and workspace must
+ * not overlap (STAC_ERR_INVALID).  Three launches on `stream`; no workgroup waits for another. */
+int32_t stac_prep_fill(const float *kp, int64_t n_frames, int32_t n_kp, int32_t mode, float *out, int32_t *gap,
+                       void *workspace, int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,8 +31,9 @@ _STAC_OPTIONAL = ("num_clips",)
 _MUJOCO_REQUIRED = ("solver", "iterations", "ls_iterations")
 # Engine extensions (not in the reference schema); all optional.  (lm_maxiter: accepted steps per solve of solver = lm, default 20
 # -- 40 until round 3; gather: auto | rank0 | all | none, resolved per run by main.run_stac, the caller's config is never modified;
-# postprocess: host (default) | gpu -- where the cross-fade stitch and qvel of a run happen, read from the caller's config)
-_STAC_EXTENSIONS = ("solver", "lanes_per_chain", "device", "time_indices", "fit_frames_per_clip", "reference_marker_order", "gather", "gather_max_bytes", "lm_maxiter", "postprocess")
+# postprocess: host (default) | gpu -- where the cross-fade stitch and qvel of a run happen, read from the caller's config;
+# fill_missing: off (default) | linear | hold -- missing keypoints are filled along time before the fit, read from the caller's config)
+_STAC_EXTENSIONS = ("solver", "lanes_per_chain", "device", "time_indices", "fit_frames_per_clip", "reference_marker_order", "gather", "gather_max_bytes", "lm_maxiter", "postprocess", "fill_missing")
 _MODEL_EXTENSIONS = ("KP_NAMES_LABEL3D_PATH",)
 
 
@@ -178,6 +179,11 @@ def validate_config(cfg: dict) -> ConfigNode:
             raise ConfigError(f"stac.{k} must be a bool")
     if stac.get("postprocess", "host") not in ("host", "gpu"):
         raise ConfigError(f"stac.postprocess must be host or gpu, not {stac['postprocess']!r}")
+    fill = stac.get("fill_missing", "off")
+    if fill is False:  # a bare `off` in YAML 1.1 is the boolean
+        stac["fill_missing"] = fill = "off"
+    if not isinstance(fill, str) or fill not in ("off", "linear", "hold"):
+        raise ConfigError(f"stac.fill_missing must be off, linear or hold, not {fill!r}")
     return _wrap({"model": model, "stac": stac})
 
 

@@ -18,6 +18,7 @@
 #include "stac_render.hpp"
 #include "stac_jpeg.hpp"
 #include "stac_post.hpp"
+#include "stac_prep.hpp"
 
 namespace stac {
 hipError_t launch_q_phase(const QArgs &a, const QInst &inst, int wpb, size_t lds_bytes, hipStream_t s);
@@ -38,6 +39,8 @@ hipError_t launch_post_stitch(const float *src, float *dst, int64_t C, int32_t F
                               hipStream_t s);
 hipError_t launch_post_qvel(const float *qpos, float *qvel, int64_t N, int32_t nq, int32_t F, int32_t freejoint, float dt,
                             float max_qvel, hipStream_t s);
+hipError_t launch_prep_fill(const float *kp, int64_t T, int32_t K, int32_t mode, float *out, int32_t *gap, void *workspace,
+                            hipStream_t s);
 }  // namespace stac
 
 using namespace stac;
@@ -2286,6 +2289,40 @@ extern "C" int32_t stac_post_qvel(const float *qpos, int64_t N, int32_t nq, int3
     if (!qpos || !qvel) return fail(STAC_ERR_INVALID, "stac_post_qvel: null qpos / qvel");
     const hipError_t e = launch_post_qvel(qpos, qvel, N, nq, F, freejoint ? 1 : 0, (float)dt, (float)max_qvel, (hipStream_t)stream);
     if (e != hipSuccess) return fail(STAC_ERR_HIP, std::string("stac_post_qvel: ") + hipGetErrorString(e));
+    return STAC_OK;
+}
+
+// ---- Filling missing keypoints before the fit (stac_prep.hip): every argument is checked before the device is touched -----------
+extern "C" int64_t stac_prep_fill_workspace(int64_t n_frames, int32_t n_kp) {
+    const int64_t b = prep_workspace_bytes(n_frames, n_kp);
+    if (b < 0) return fail(STAC_ERR_INVALID, "stac_prep_fill_workspace: n_frames >= 1, n_kp >= 1 (and a workspace size within int64)");
+    return b;
+}
+
+extern "C" int32_t stac_prep_fill(const float *kp, int64_t n_frames, int32_t n_kp, int32_t mode, float *out, int32_t *gap,
+                                  void *workspace, int64_t workspace_bytes, void *stream) {
+    const int64_t need = prep_workspace_bytes(n_frames, n_kp);
+    if (need < 0 || n_frames > (((int64_t)1 << 59) / n_kp))
+        return fail(STAC_ERR_INVALID, "stac_prep_fill: n_frames >= 1, n_kp >= 1 (and array sizes within int64)");
+    if (mode != STAC_PREP_LINEAR && mode != STAC_PREP_HOLD)
+        return fail(STAC_ERR_INVALID, "stac_prep_fill: mode " + std::to_string(mode) + " is neither STAC_PREP_LINEAR nor STAC_PREP_HOLD");
+    if (!kp || !out || !gap || !workspace) return fail(STAC_ERR_INVALID, "stac_prep_fill: null kp / out / gap / workspace");
+    if (workspace_bytes < need)
+        return fail(STAC_ERR_INVALID, "stac_prep_fill: workspace_bytes = " + std::to_string(workspace_bytes) + ", " +
+                                          std::to_string(need) + " are needed (stac_prep_fill_workspace)");
+    if ((uintptr_t)workspace % 8 != 0 || (uintptr_t)kp % 4 != 0 || (uintptr_t)out % 4 != 0 || (uintptr_t)gap % 4 != 0)
+        return fail(STAC_ERR_INVALID, "stac_prep_fill: kp / out / gap must be 4-byte aligned, workspace 8-byte aligned");
+    const int64_t kp_bytes = n_frames * n_kp * 12, gap_bytes = n_frames * n_kp * 4;
+    const struct { const char *name; uintptr_t lo; int64_t bytes; } buf[4] = {
+        {"kp", (uintptr_t)kp, kp_bytes}, {"out", (uintptr_t)out, kp_bytes}, {"gap", (uintptr_t)gap, gap_bytes},
+        {"workspace", (uintptr_t)workspace, need}};
+    for (int i = 0; i < 4; ++i)
+        for (int j = i + 1; j < 4; ++j)
+            if (buf[i].lo < buf[j].lo + (uintptr_t)buf[j].bytes && buf[j].lo < buf[i].lo + (uintptr_t)buf[i].bytes)
+                return fail(STAC_ERR_INVALID, std::string("stac_prep_fill: ") + buf[i].name + " and " + buf[j].name +
+                                                  " overlap: source, outputs and workspace are distinct buffers");
+    const hipError_t e = launch_prep_fill(kp, n_frames, n_kp, mode, out, gap, workspace, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(STAC_ERR_HIP, std::string("stac_prep_fill: ") + hipGetErrorString(e));
     return STAC_OK;
 }
 

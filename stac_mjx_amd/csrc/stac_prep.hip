@@ -1,0 +1,211 @@
+// Filling missing keypoints along time (rule and shared functions: stac_prep.hpp; entry points: stac_abi.hip).
+//
+// A staged scan over tiles of 64 frames, three launches on the caller's stream, no workgroup ever waits for another:
+//   1. prep_summary_kernel: per tile and keypoint the first and last valid frame of the tile          -> first, last [K][tiles]
+//   2. prep_carry_kernel:   per keypoint an exclusive prefix (last valid frame before the tile) and an
+//                           exclusive suffix (first valid frame after it) over the tile summaries       -> prev, next  [K][tiles]
+//   3. prep_fill_kernel:    re-reads the tile, finishes p / n inside it from the tile's validity masks,
+//                           gathers the two source values and writes out and gap
+// Kernels 1 and 3 work on one (tile, chunk of up to 64 keypoints) at a time.  A thread owns (frame, keypoint) pairs in the
+// order of memory -- consecutive lanes read the three floats of consecutive keypoints of a frame row, then of the next row --
+// so with K <= 64 a tile is one contiguous block of 64 * 3K floats, read and written in whole lines.  The validity of a
+// pair goes to LDS as a byte; a wavefront whose lane l reads the byte of frame l then has the keypoint's 64-bit validity mask
+// of the tile in one ballot.  Rows are 4-byte aligned only, hence dword accesses; offsets are 64-bit element offsets.
+#include <hip/hip_runtime.h>
+
+#include "stac_prep.hpp"
+
+namespace stac {
+
+namespace {
+
+constexpr int kPrepThreads = 256;
+constexpr int kPrepWaves = kPrepThreads / 64;
+constexpr int kPrepChunk = 64;                                            // keypoints of a chunk
+constexpr int kPrepPairs = kPrepTileFrames * kPrepChunk / kPrepThreads;  // (frame, keypoint) pairs of a thread: 16
+constexpr int kPrepFlagRow = kPrepChunk + 4;  // bytes of a frame's flags in LDS: 17 dwords, so the 64 rows a ballot reads differ in bank
+constexpr int kCarryThreads = 1024;
+
+static_assert(kPrepTileFrames == 64, "a tile is what one 64-lane ballot covers");
+
+struct PrepShared {
+    uint8_t flags[kPrepTileFrames][kPrepFlagRow];
+    unsigned long long mask[kPrepChunk];
+};
+
+// Walks the pairs of this thread in (tile, chunk): pair e = i * 256 + threadIdx.x is frame e / kc, keypoint e % kc of the chunk
+struct PrepWalk {
+    uint32_t f, k, qf, qk, kc;
+    __device__ PrepWalk(uint32_t kc_) : kc(kc_) {
+        f = threadIdx.x / kc;
+        k = threadIdx.x - f * kc;
+        qf = kPrepThreads / kc;
+        qk = kPrepThreads - qf * kc;
+    }
+    __device__ void next() {
+        f += qf;
+        k += qk;
+        if (k >= kc) {
+            k -= kc;
+            ++f;
+        }
+    }
+};
+
+// Stage A + B of kernels 1 and 3: loads the pairs of (tile at frame t0, keypoints k0 .. k0 + kc - 1) into v and leaves the
+// validity mask of every keypoint of the chunk (bit f = frame t0 + f is valid; frames >= T are not) in sh.mask.
+__device__ __forceinline__ void prep_tile_masks(const float *__restrict__ kp, int64_t T, int64_t K3, int64_t t0, int32_t k0, int32_t kc,
+                                                float (&v)[kPrepPairs][3], PrepShared &sh) {
+    PrepWalk w((uint32_t)kc);
+#pragma unroll
+    for (int i = 0; i < kPrepPairs; ++i) {
+        v[i][0] = v[i][1] = v[i][2] = 0.0f;
+        if (w.f < (uint32_t)kPrepTileFrames) {
+            const int64_t t = t0 + w.f;
+            bool ok = false;
+            if (t < T) {
+                const float *s = kp + t * K3 + 3 * (int64_t)(k0 + (int32_t)w.k);
+                v[i][0] = s[0];
+                v[i][1] = s[1];
+                v[i][2] = s[2];
+                ok = !prep_missing(v[i][0], v[i][1], v[i][2]);
+            }
+            sh.flags[w.f][w.k] = ok ? 1 : 0;
+        }
+        w.next();
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    for (int k = threadIdx.x >> 6; k < kc; k += kPrepWaves) {
+        const unsigned long long m = __ballot(sh.flags[lane][k] != 0);
+        if (lane == 0) sh.mask[k] = m;
+    }
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(kPrepThreads) void prep_summary_kernel(const float *__restrict__ kp, int64_t T, int32_t K, int64_t tiles,
+                                                                   int32_t chunks, int64_t *__restrict__ first,
+                                                                   int64_t *__restrict__ last) {
+    __shared__ PrepShared sh;
+    const int64_t K3 = 3 * (int64_t)K, work = tiles * chunks;
+    for (int64_t wk = blockIdx.x; wk < work; wk += gridDim.x) {
+        const int64_t tile = wk / chunks;
+        const int32_t k0 = (int32_t)(wk - tile * chunks) * kPrepChunk;
+        const int32_t kc = K - k0 < kPrepChunk ? K - k0 : kPrepChunk;
+        const int64_t t0 = tile * kPrepTileFrames;
+        float v[kPrepPairs][3];
+        prep_tile_masks(kp, T, K3, t0, k0, kc, v, sh);
+        if ((int)threadIdx.x < kc) {
+            const unsigned long long m = sh.mask[threadIdx.x];
+            const int64_t at = (int64_t)(k0 + (int)threadIdx.x) * tiles + tile;
+            first[at] = m ? t0 + (__ffsll(m) - 1) : -1;
+            last[at] = m ? t0 + 63 - __clzll(m) : -1;
+        }
+        __syncthreads();  // sh is written again in the next sweep
+    }
+}
+
+// One workgroup per keypoint, the tiles cut into one contiguous segment per thread: a combine over the segment, a scan over the
+// 1024 segment summaries in LDS (forwards and backwards at once), then the segment again with the carried value.
+__global__ __launch_bounds__(kCarryThreads) void prep_carry_kernel(const int64_t *__restrict__ first, const int64_t *__restrict__ last,
+                                                                  int64_t *__restrict__ prev, int64_t *__restrict__ next,
+                                                                  int64_t tiles) {
+    __shared__ PrepSummary fwd[kCarryThreads], bwd[kCarryThreads];
+    const int i = threadIdx.x;
+    const int64_t base = (int64_t)blockIdx.x * tiles;
+    const int64_t S = (tiles + kCarryThreads - 1) / kCarryThreads;
+    const int64_t lo = i * S < tiles ? i * S : tiles, hi = lo + S < tiles ? lo + S : tiles;
+    PrepSummary s = prep_none();
+    for (int64_t j = lo; j < hi; ++j) s = prep_combine(s, PrepSummary{first[base + j], last[base + j]});
+    fwd[i] = s;  // -> combine of the segments 0 .. i
+    bwd[i] = s;  // -> combine of the segments i .. 1023
+    __syncthreads();
+    for (int off = 1; off < kCarryThreads; off <<= 1) {
+        const PrepSummary a = i >= off ? prep_combine(fwd[i - off], fwd[i]) : fwd[i];
+        const PrepSummary b = i + off < kCarryThreads ? prep_combine(bwd[i], bwd[i + off]) : bwd[i];
+        __syncthreads();
+        fwd[i] = a;
+        bwd[i] = b;
+        __syncthreads();
+    }
+    PrepSummary run = i > 0 ? fwd[i - 1] : prep_none();
+    for (int64_t j = lo; j < hi; ++j) {
+        prev[base + j] = run.last;
+        run = prep_combine(run, PrepSummary{first[base + j], last[base + j]});
+    }
+    run = i + 1 < kCarryThreads ? bwd[i + 1] : prep_none();
+    for (int64_t j = hi - 1; j >= lo; --j) {
+        next[base + j] = run.first;
+        run = prep_combine(PrepSummary{first[base + j], last[base + j]}, run);
+    }
+}
+
+__global__ __launch_bounds__(kPrepThreads) void prep_fill_kernel(const float *__restrict__ kp, int64_t T, int32_t K, int32_t mode,
+                                                                int64_t tiles, int32_t chunks, const int64_t *__restrict__ prev,
+                                                                const int64_t *__restrict__ next, float *__restrict__ out,
+                                                                int32_t *__restrict__ gap) {
+    __shared__ PrepShared sh;
+    const int64_t K3 = 3 * (int64_t)K, work = tiles * chunks;
+    for (int64_t wk = blockIdx.x; wk < work; wk += gridDim.x) {
+        const int64_t tile = wk / chunks;
+        const int32_t k0 = (int32_t)(wk - tile * chunks) * kPrepChunk;
+        const int32_t kc = K - k0 < kPrepChunk ? K - k0 : kPrepChunk;
+        const int64_t t0 = tile * kPrepTileFrames;
+        float v[kPrepPairs][3];
+        prep_tile_masks(kp, T, K3, t0, k0, kc, v, sh);
+        PrepWalk w((uint32_t)kc);
+#pragma unroll
+        for (int i = 0; i < kPrepPairs; ++i) {
+            const int64_t t = t0 + w.f;
+            if (w.f < (uint32_t)kPrepTileFrames && t < T) {
+                const int64_t kk = k0 + (int32_t)w.k;
+                const unsigned long long m = sh.mask[w.k];
+                float x = v[i][0], y = v[i][1], z = v[i][2];
+                int32_t g = 0;
+                if (!((m >> w.f) & 1ull)) {
+                    const unsigned long long below = m & ((1ull << w.f) - 1ull);
+                    const unsigned long long above = w.f == 63u ? 0ull : m >> (w.f + 1u);
+                    const int64_t p = below ? t0 + 63 - __clzll(below) : prev[kk * tiles + tile];
+                    const int64_t n = above ? t + 1 + (__ffsll(above) - 1) : next[kk * tiles + tile];
+                    g = prep_gap(p, n, T);
+                    if (p >= 0 || n >= 0) {  // (an empty track stays as it is)
+                        const float *a = kp + (p >= 0 ? p : n) * K3 + 3 * kk;
+                        const float *b = kp + (n >= 0 ? n : p) * K3 + 3 * kk;
+                        x = prep_fill(mode, t, p, n, a[0], b[0]);
+                        y = prep_fill(mode, t, p, n, a[1], b[1]);
+                        z = prep_fill(mode, t, p, n, a[2], b[2]);
+                    }
+                }
+                float *o = out + t * K3 + 3 * kk;
+                o[0] = x;
+                o[1] = y;
+                o[2] = z;
+                gap[t * K + kk] = g;
+            }
+            w.next();
+        }
+        __syncthreads();  // sh is written again in the next sweep
+    }
+}
+
+}  // namespace
+
+hipError_t launch_prep_fill(const float *kp, int64_t T, int32_t K, int32_t mode, float *out, int32_t *gap, void *workspace,
+                            hipStream_t s) {
+    const int64_t tiles = prep_tiles(T, kPrepTileFrames);
+    const int32_t chunks = (K + kPrepChunk - 1) / kPrepChunk;
+    int64_t *first = (int64_t *)workspace, *last = first + (int64_t)K * tiles, *prev = last + (int64_t)K * tiles,
+            *next = prev + (int64_t)K * tiles;
+    const int64_t work = tiles * chunks;
+    const unsigned grid = (unsigned)(work < kPrepMaxBlocks ? work : kPrepMaxBlocks);
+    hipLaunchKernelGGL(prep_summary_kernel, dim3(grid), dim3(kPrepThreads), 0, s, kp, T, K, tiles, chunks, first, last);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(prep_carry_kernel, dim3((unsigned)K), dim3(kCarryThreads), 0, s, first, last, prev, next, tiles);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(prep_fill_kernel, dim3(grid), dim3(kPrepThreads), 0, s, kp, T, K, mode, tiles, chunks, prev, next, out, gap);
+    return hipGetLastError();
+}
+
+}  // namespace stac

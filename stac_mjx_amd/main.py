@@ -26,6 +26,8 @@ def run_stac(cfg, kp_data, kp_names, base_path=None, *, setup=None, device=None)
     do not match ``3 * len(kp_names)`` or ``n_frames_per_clip`` does not divide the frame count.
     ``infer_qvels`` runs the reference's finite-difference post-processing on the host, or, like the
     cross-fade of a continuous run, on the device with ``stac.postprocess: gpu`` (DESIGN.md "Post-processing on the GPU").
+    ``stac.fill_missing: linear | hold`` fills missing keypoints (NaN / infinite) of the whole series on the GPU before the fit
+    and adds ``kp_gap`` to both files (DESIGN.md "Filling missing keypoints"); a keypoint without any valid frame is a ``ValueError``.
     """
     base_path = Path.cwd() if base_path is None else Path(base_path)
     kp_data = np.asarray(kp_data)
@@ -57,10 +59,24 @@ def run_stac(cfg, kp_data, kp_names, base_path=None, *, setup=None, device=None)
             raise ValueError("stac.postprocess = gpu cannot cross-fade marker_sites in the reference's frame-major row order "
                              "(stac.reference_marker_order: true): only postprocess = host reproduces fading across it")
 
+    # stac.fill_missing (engine extension, read from the caller's config): "off" (default) = kp_data goes to the fit as it came;
+    # "linear" / "hold" = the WHOLE series is filled once, here, on the GPU (every rank fills it itself: same bits), so a missing
+    # run that crosses n_fit_frames or a clip border is filled from its true neighbours, and both phases see the filled array
+    kp_gap = None
+    fill_mode = _fill_missing_mode(cfg)
+    if fill_mode != "off":
+        kp_data, kp_gap = stac.fill_missing(kp_data, fill_mode)
+        n_fit = min(int(cfg.stac.n_fit_frames), kp_gap.shape[0])
+        if not cfg.stac.skip_fit_offsets and n_fit > 0:  # (the offset phase fits filled positions like observed ones: DESIGN.md §10)
+            print(f"fill_missing: {100.0 * np.count_nonzero(kp_gap[:n_fit]) / kp_gap[:n_fit].size:.3f} % of the keypoints of the "
+                  f"{n_fit} fit frames are filled values")
+
     if not cfg.stac.skip_fit_offsets:
         kps = kp_data[: cfg.stac.n_fit_frames]
         print(f"Running fit. Mocap data shape: {kps.shape}")
         fit_data = stac.fit_offsets(kps)
+        if kp_gap is not None:  # (the rows of the fit file are the first rows of the series, in order)
+            fit_data.kp_gap = kp_gap[: fit_data.kp_data.shape[0]]
         if dist.world()[0] == 0:  # multi-GPU: rank 0 holds the gathered result and writes it
             io.save_data_to_h5(config=cfg, file_path=fit_offsets_path, **fit_data.as_dict())
         fit_offsets_path = io.resolve_output_path(fit_offsets_path)
@@ -102,6 +118,9 @@ def run_stac(cfg, kp_data, kp_names, base_path=None, *, setup=None, device=None)
         batched = ik_data.qpos.reshape((-1, F, ik_data.qpos.shape[-1]))
         qvels = [utils.compute_velocity_from_kinematics(c, dt=stac._timestep, freejoint=stac._freejoint) for c in batched]
         ik_data.qvel = np.stack(qvels).reshape(-1, qvels[0].shape[-1])
+    if kp_gap is not None:  # rows of the input series, not passed through the cross-fade; a shard file carries the rows of its clips
+        lo, hi = dist.shard_range(kp_data.shape[0] // F) if sharded else (0, kp_data.shape[0] // F)
+        ik_data.kp_gap = kp_gap[lo * F:hi * F]
     if sharded:
         # every rank writes ITS clips under a shard name (never a partial result under the full-run name); rank 0 adds
         # the manifest that io.load_sharded_stac_data() reads the run back through
@@ -130,6 +149,15 @@ def _postprocess_mode(cfg) -> str:
     mode = str(cfg.stac.get("postprocess", "host") or "host")
     if mode not in ("host", "gpu"):
         raise ValueError(f"stac.postprocess must be host or gpu, not {mode!r}")
+    return mode
+
+
+def _fill_missing_mode(cfg) -> str:
+    """``stac.fill_missing``: "off" (default) | "linear" | "hold"."""
+    mode = cfg.stac.get("fill_missing", "off")
+    mode = "off" if mode in (None, False) else mode
+    if mode not in ("off", "linear", "hold"):
+        raise ValueError(f"stac.fill_missing must be off, linear or hold, not {mode!r}")
     return mode
 
 

@@ -74,6 +74,32 @@ class Stac:
             root_dims=s.root_dims, do_root_opt=do_root_opt, q_init=q_init, want_bodies=want_outputs,
             want_markers=want_outputs)
 
+    # -- fill_missing (engine extension; DESIGN.md "Filling missing keypoints") ----------------------------------------
+    def fill_missing(self, kp_data, mode=None):
+        """Fills the missing keypoints (a NaN or infinite coordinate) of the whole series ``kp_data`` [T, 3K] along time on the
+        GPU (``prep.fill_missing``) -> ``(filled [T, 3K] float32, gap [T, K] int32)`` as numpy arrays; ``gap`` is 0 where the
+        keypoint was observed, else the length of the missing run.  ``mode``: "linear" | "hold" (None: ``stac.fill_missing`` of
+        the config).  One log line per keypoint that had gaps.  A keypoint without a single valid frame cannot be filled: a
+        ``ValueError`` that names every such keypoint."""
+        from . import prep
+
+        mode = str(self.cfg.stac.get("fill_missing", "off") or "off") if mode is None else mode
+        prep.mode_code(mode)
+        kp = np.asarray(kp_data, dtype=np.float32)
+        if kp.ndim != 2 or kp.shape[1] != 3 * len(self._kp_names):
+            raise ValueError(f"fill_missing: kp_data must be [frames, {3 * len(self._kp_names)}], got {kp.shape}")
+        if not kp.flags.writeable:  # (torch does not wrap a read-only array)
+            kp = kp.copy()
+        filled, gap = prep.fill_missing(torch.as_tensor(kp).to(self.engine.device), mode)
+        info = prep.summary(gap)
+        if info["empty"]:
+            raise ValueError("fill_missing: no valid frame at all for keypoint(s) "
+                             + ", ".join(f"{self._kp_names[k]} (index {k})" for k in info["empty"]) + ": nothing to fill them from")
+        for k in np.flatnonzero(info["missing"]):
+            self._log(f"fill_missing ({mode}): {self._kp_names[k]}: {int(info['missing'][k])} of {kp.shape[0]} frames filled, "
+                      f"longest run {int(info['longest'][k])}")
+        return filled.cpu().numpy(), gap.cpu().numpy()
+
     # -- fit_offsets (stac.py:253-354) ------------------------------------------------------------------
     def fit_offsets(self, kp_data, time_indices=None) -> StacData:
         """Alternate pose and offset optimisation.

@@ -309,6 +309,27 @@ int64_t stac_prep_fill_workspace(int64_t n_frames, int32_t n_kp);
 int32_t stac_prep_fill(const float *kp, int64_t n_frames, int32_t n_kp, int32_t mode, float *out, int32_t *gap,
                        void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- Rejecting keypoint outliers before the fit (no stac_model needed; the current device is used) -------------------
+ * DESIGN.md "Rejecting keypoint outliers".  The reference has no counterpart: stac_mjx.main.run_stac
+ * (stac_mjx/main.py:33-139) fits kp_data as it comes, and q_loss (stac_mjx/stac_core.py:27-62) squares the residual of
+ * a keypoint that is finite and wrong (an identity swap, a triangulation jump) like any other.
+ *
+ * kp[n_frames, 3 * n_kp] -> out[n_frames, 3 * n_kp], flag[n_frames, n_kp] (uint8), every element of both written once.
+ * The Hampel identifier per track and coordinate.  Keypoint k is missing in frame t iff one of its three coordinates is
+ * NaN or +-inf (as in stac_prep_fill).  For a keypoint that is not missing, per coordinate: the window is the frames
+ * max(0, t - half_window) .. min(n_frames - 1, t + half_window) in which k is not missing, n their number; n < 3 decides
+ * nothing; with s the window values in ascending order, med = 0.5 * ((double)s[(n-1)/2] + (double)s[n/2]),
+ * d_j = fabs((double)x_j - med), D the d_j in ascending order, mad = 0.5 * (D[(n-1)/2] + D[n/2]): the coordinate is an
+ * outlier iff d_centre > thr * mad and d_centre > min_dev (both strict).  A keypoint with an outlier coordinate is
+ * rejected: its three coordinates leave as the quiet NaN 0x7FC00000 and its flag as 1.  Everything else passes bit for
+ * bit with flag 0 (missing keypoints included).  Every decision reads kp only.  A run of wrong values longer than
+ * half_window frames is its window's majority and is not rejected.
+ * half_window in 1 .. 16; thr and min_dev finite and >= 0 (the conventional thr is 3 * 1.4826); kp and out 4-byte
+ * aligned; kp, out and flag must not overlap -- in place is not possible (STAC_ERR_INVALID, before any launch).
+ * One launch on `stream`, no workspace; no workgroup waits for another. */
+int32_t stac_prep_reject(const float *kp, int64_t n_frames, int32_t n_kp, int32_t half_window, double thr, double min_dev,
+                         float *out, uint8_t *flag, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

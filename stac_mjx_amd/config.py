@@ -32,13 +32,42 @@ _MUJOCO_REQUIRED = ("solver", "iterations", "ls_iterations")
 # Engine extensions (not in the reference schema); all optional.  (lm_maxiter: accepted steps per solve of solver = lm, default 20
 # -- 40 until round 3; gather: auto | rank0 | all | none, resolved per run by main.run_stac, the caller's config is never modified;
 # postprocess: host (default) | gpu -- where the cross-fade stitch and qvel of a run happen, read from the caller's config;
-# fill_missing: off (default) | linear | hold -- missing keypoints are filled along time before the fit, read from the caller's config)
-_STAC_EXTENSIONS = ("solver", "lanes_per_chain", "device", "time_indices", "fit_frames_per_clip", "reference_marker_order", "gather", "gather_max_bytes", "lm_maxiter", "postprocess", "fill_missing")
+# fill_missing: off (default) | linear | hold -- missing keypoints are filled along time before the fit, read from the caller's config;
+# reject_outliers: off (default) | hampel, with outlier_window (half-width, 1 .. 16, default 5), outlier_nsigma (default 3.0) and
+# outlier_min_dev (default 0.001, units of kp_data) -- finite but wrong keypoints become missing ones in front of fill_missing)
+_STAC_EXTENSIONS = ("solver", "lanes_per_chain", "device", "time_indices", "fit_frames_per_clip", "reference_marker_order", "gather", "gather_max_bytes", "lm_maxiter", "postprocess", "fill_missing",
+                    "reject_outliers", "outlier_window", "outlier_nsigma", "outlier_min_dev")
 _MODEL_EXTENSIONS = ("KP_NAMES_LABEL3D_PATH",)
 
 
 class ConfigError(ValueError):
     pass
+
+
+OUTLIER_DEFAULTS = {"outlier_window": 5, "outlier_nsigma": 3.0, "outlier_min_dev": 0.001}
+OUTLIER_MAX_WINDOW = 16  # csrc/stac_outlier.hpp: kOutlierMaxHalf
+
+
+def outlier_options(stac) -> tuple:
+    """``stac.reject_outliers`` and its three parameters out of a ``stac`` mapping -> (mode, half_window, n_sigma, min_dev), absent
+    keys at their defaults.  ``ConfigError`` for anything else than off | hampel, a half-width that is not an integer in 1 .. 16,
+    or an ``outlier_nsigma`` / ``outlier_min_dev`` that is not a finite number >= 0."""
+    import math
+
+    mode = stac.get("reject_outliers", "off")
+    mode = "off" if mode is False or mode is None else mode  # (a bare `off` in YAML 1.1 is the boolean)
+    if not isinstance(mode, str) or mode not in ("off", "hampel"):
+        raise ConfigError(f"stac.reject_outliers must be off or hampel, not {mode!r}")
+    h = stac.get("outlier_window", OUTLIER_DEFAULTS["outlier_window"])
+    if isinstance(h, bool) or not isinstance(h, int) or not 1 <= h <= OUTLIER_MAX_WINDOW:
+        raise ConfigError(f"stac.outlier_window (the half-width in frames) must be an integer in 1 .. {OUTLIER_MAX_WINDOW}, not {h!r}")
+    vals = []
+    for key in ("outlier_nsigma", "outlier_min_dev"):
+        v = stac.get(key, OUTLIER_DEFAULTS[key])
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
+            raise ConfigError(f"stac.{key} must be a finite number >= 0, not {v!r}")
+        vals.append(float(v))
+    return mode, h, vals[0], vals[1]
 
 
 class ConfigNode(dict):
@@ -184,6 +213,9 @@ def validate_config(cfg: dict) -> ConfigNode:
         stac["fill_missing"] = fill = "off"
     if not isinstance(fill, str) or fill not in ("off", "linear", "hold"):
         raise ConfigError(f"stac.fill_missing must be off, linear or hold, not {fill!r}")
+    if stac.get("reject_outliers", "off") is False:
+        stac["reject_outliers"] = "off"
+    outlier_options(stac)
     return _wrap({"model": model, "stac": stac})
 
 

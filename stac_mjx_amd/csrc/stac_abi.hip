@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -19,6 +20,7 @@
 #include "stac_jpeg.hpp"
 #include "stac_post.hpp"
 #include "stac_prep.hpp"
+#include "stac_outlier.hpp"
 
 namespace stac {
 hipError_t launch_q_phase(const QArgs &a, const QInst &inst, int wpb, size_t lds_bytes, hipStream_t s);
@@ -41,6 +43,8 @@ hipError_t launch_post_qvel(const float *qpos, float *qvel, int64_t N, int32_t n
                             float max_qvel, hipStream_t s);
 hipError_t launch_prep_fill(const float *kp, int64_t T, int32_t K, int32_t mode, float *out, int32_t *gap, void *workspace,
                             hipStream_t s);
+hipError_t launch_outlier_reject(const float *kp, int64_t T, int32_t K, int32_t h, double thr, double min_dev, float *out, uint8_t *flag,
+                                 hipStream_t s);
 }  // namespace stac
 
 using namespace stac;
@@ -2323,6 +2327,31 @@ extern "C" int32_t stac_prep_fill(const float *kp, int64_t n_frames, int32_t n_k
                                                   " overlap: source, outputs and workspace are distinct buffers");
     const hipError_t e = launch_prep_fill(kp, n_frames, n_kp, mode, out, gap, workspace, (hipStream_t)stream);
     if (e != hipSuccess) return fail(STAC_ERR_HIP, std::string("stac_prep_fill: ") + hipGetErrorString(e));
+    return STAC_OK;
+}
+
+// ---- Rejecting keypoint outliers before the fit (stac_outlier.hip): every argument is checked before the device is touched --------
+extern "C" int32_t stac_prep_reject(const float *kp, int64_t n_frames, int32_t n_kp, int32_t half_window, double thr, double min_dev,
+                                    float *out, uint8_t *flag, void *stream) {
+    if (n_frames < 1 || n_kp < 1 || n_frames > (((int64_t)1 << 59) / n_kp))
+        return fail(STAC_ERR_INVALID, "stac_prep_reject: n_frames >= 1, n_kp >= 1 (and array sizes within int64)");
+    if (half_window < 1 || half_window > kOutlierMaxHalf)
+        return fail(STAC_ERR_INVALID, "stac_prep_reject: half_window " + std::to_string(half_window) + " is outside 1 .. " +
+                                          std::to_string(kOutlierMaxHalf));
+    if (!std::isfinite(thr) || thr < 0.0 || !std::isfinite(min_dev) || min_dev < 0.0)
+        return fail(STAC_ERR_INVALID, "stac_prep_reject: thr and min_dev must be finite and >= 0");
+    if (!kp || !out || !flag) return fail(STAC_ERR_INVALID, "stac_prep_reject: null kp / out / flag");
+    if ((uintptr_t)kp % 4 != 0 || (uintptr_t)out % 4 != 0) return fail(STAC_ERR_INVALID, "stac_prep_reject: kp / out must be 4-byte aligned");
+    const int64_t kp_bytes = n_frames * n_kp * 12, flag_bytes = n_frames * n_kp;
+    const struct { const char *name; uintptr_t lo; int64_t bytes; } buf[3] = {
+        {"kp", (uintptr_t)kp, kp_bytes}, {"out", (uintptr_t)out, kp_bytes}, {"flag", (uintptr_t)flag, flag_bytes}};
+    for (int i = 0; i < 3; ++i)
+        for (int j = i + 1; j < 3; ++j)
+            if (buf[i].lo < buf[j].lo + (uintptr_t)buf[j].bytes && buf[j].lo < buf[i].lo + (uintptr_t)buf[i].bytes)
+                return fail(STAC_ERR_INVALID, std::string("stac_prep_reject: ") + buf[i].name + " and " + buf[j].name +
+                                                  " overlap: neighbours read raw values, so in place is not possible");
+    const hipError_t e = launch_outlier_reject(kp, n_frames, n_kp, half_window, thr, min_dev, out, flag, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(STAC_ERR_HIP, std::string("stac_prep_reject: ") + hipGetErrorString(e));
     return STAC_OK;
 }
 

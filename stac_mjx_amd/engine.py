@@ -56,7 +56,7 @@ ABI_SYMBOLS = (
     "stac_render_scene_create", "stac_render_scene_create_with_meshes", "stac_render_scene_destroy", "stac_render",
     "stac_jpeg_header", "stac_jpeg_workspace_bytes", "stac_jpeg_encode",
     "stac_post_stitch_rows", "stac_post_stitch", "stac_post_qvel",
-    "stac_prep_fill_workspace", "stac_prep_fill",
+    "stac_prep_fill_workspace", "stac_prep_fill", "stac_prep_reject",
 )  # fmt: skip
 
 

@@ -28,6 +28,8 @@ def run_stac(cfg, kp_data, kp_names, base_path=None, *, setup=None, device=None)
     cross-fade of a continuous run, on the device with ``stac.postprocess: gpu`` (DESIGN.md "Post-processing on the GPU").
     ``stac.fill_missing: linear | hold`` fills missing keypoints (NaN / infinite) of the whole series on the GPU before the fit
     and adds ``kp_gap`` to both files (DESIGN.md "Filling missing keypoints"); a keypoint without any valid frame is a ``ValueError``.
+    ``stac.reject_outliers: hampel`` (needs ``fill_missing``) first turns keypoints that are finite but off their track's sliding
+    median into missing ones, on the GPU, and adds ``kp_rejected`` to both files (DESIGN.md "Rejecting keypoint outliers").
     """
     base_path = Path.cwd() if base_path is None else Path(base_path)
     kp_data = np.asarray(kp_data)
@@ -37,6 +39,7 @@ def run_stac(cfg, kp_data, kp_names, base_path=None, *, setup=None, device=None)
             f"kp_data has {kp_data.shape[1]} columns but expected {expected_cols} ({len(kp_names)} keypoints x 3). "
             "Ensure kp_data is shaped (n_frames, n_keypoints * 3) and that kp_names length matches the number of "
             "keypoints in kp_data.")
+    reject_mode, reject_args = _reject_outliers_mode(cfg)  # (bad values and hampel without fill_missing: before any work)
     start = time.time()
     fit_offsets_path = base_path / cfg.stac.fit_offsets_path
     ik_only_path = base_path / cfg.stac.ik_only_path
@@ -62,14 +65,22 @@ def run_stac(cfg, kp_data, kp_names, base_path=None, *, setup=None, device=None)
     # stac.fill_missing (engine extension, read from the caller's config): "off" (default) = kp_data goes to the fit as it came;
     # "linear" / "hold" = the WHOLE series is filled once, here, on the GPU (every rank fills it itself: same bits), so a missing
     # run that crosses n_fit_frames or a clip border is filled from its true neighbours, and both phases see the filled array
-    kp_gap = None
+    # stac.reject_outliers (engine extension, caller's config; needs fill_missing): "hampel" = the whole series goes through the
+    # Hampel identifier once, immediately before the fill (every rank itself: same bits); a rejected keypoint is three NaN, which
+    # the fill closes like any missing one, so kp_gap > 0 there with no further code
+    kp_gap = kp_rejected = None
     fill_mode = _fill_missing_mode(cfg)
+    if reject_mode != "off":
+        kp_data, kp_rejected = stac.reject_outliers(kp_data, **reject_args)
     if fill_mode != "off":
         kp_data, kp_gap = stac.fill_missing(kp_data, fill_mode)
         n_fit = min(int(cfg.stac.n_fit_frames), kp_gap.shape[0])
         if not cfg.stac.skip_fit_offsets and n_fit > 0:  # (the offset phase fits filled positions like observed ones: DESIGN.md §10)
             print(f"fill_missing: {100.0 * np.count_nonzero(kp_gap[:n_fit]) / kp_gap[:n_fit].size:.3f} % of the keypoints of the "
                   f"{n_fit} fit frames are filled values")
+            if kp_rejected is not None:
+                print(f"reject_outliers: {100.0 * np.count_nonzero(kp_rejected[:n_fit]) / kp_rejected[:n_fit].size:.3f} % of the "
+                      f"keypoints of the {n_fit} fit frames were rejected as outliers (and are among the filled ones)")
 
     if not cfg.stac.skip_fit_offsets:
         kps = kp_data[: cfg.stac.n_fit_frames]
@@ -77,6 +88,8 @@ def run_stac(cfg, kp_data, kp_names, base_path=None, *, setup=None, device=None)
         fit_data = stac.fit_offsets(kps)
         if kp_gap is not None:  # (the rows of the fit file are the first rows of the series, in order)
             fit_data.kp_gap = kp_gap[: fit_data.kp_data.shape[0]]
+        if kp_rejected is not None:
+            fit_data.kp_rejected = kp_rejected[: fit_data.kp_data.shape[0]]
         if dist.world()[0] == 0:  # multi-GPU: rank 0 holds the gathered result and writes it
             io.save_data_to_h5(config=cfg, file_path=fit_offsets_path, **fit_data.as_dict())
         fit_offsets_path = io.resolve_output_path(fit_offsets_path)
@@ -121,6 +134,8 @@ def run_stac(cfg, kp_data, kp_names, base_path=None, *, setup=None, device=None)
     if kp_gap is not None:  # rows of the input series, not passed through the cross-fade; a shard file carries the rows of its clips
         lo, hi = dist.shard_range(kp_data.shape[0] // F) if sharded else (0, kp_data.shape[0] // F)
         ik_data.kp_gap = kp_gap[lo * F:hi * F]
+        if kp_rejected is not None:  # (handled exactly like kp_gap)
+            ik_data.kp_rejected = kp_rejected[lo * F:hi * F]
     if sharded:
         # every rank writes ITS clips under a shard name (never a partial result under the full-run name); rank 0 adds
         # the manifest that io.load_sharded_stac_data() reads the run back through
@@ -159,6 +174,19 @@ def _fill_missing_mode(cfg) -> str:
     if mode not in ("off", "linear", "hold"):
         raise ValueError(f"stac.fill_missing must be off, linear or hold, not {mode!r}")
     return mode
+
+
+def _reject_outliers_mode(cfg) -> tuple:
+    """``stac.reject_outliers``: "off" (default) | "hampel" -> (mode, keyword arguments of ``Stac.reject_outliers`` from
+    ``stac.outlier_window`` / ``outlier_nsigma`` / ``outlier_min_dev``).  ``ValueError`` for a bad value of any of the four keys,
+    and for ``hampel`` with ``fill_missing`` off: the solver cannot take the NaN of a rejected keypoint."""
+    from .config import outlier_options
+
+    mode, h, n_sigma, min_dev = outlier_options(cfg.stac)
+    if mode != "off" and _fill_missing_mode(cfg) == "off":
+        raise ValueError("stac.reject_outliers = hampel turns outliers into missing keypoints (NaN), which the solver cannot take: "
+                         "set stac.fill_missing to linear or hold as well")
+    return mode, {"half_window": h, "n_sigma": n_sigma, "min_dev": min_dev}
 
 
 GATHER_AUTO_MAX_BYTES = 1 << 30  # above this much output a multi-GPU run keeps per-rank shard files ("auto")

@@ -1,5 +1,6 @@
 """Filling missing keypoints before the fit on the GPU: ``fill_missing`` over ``stac_prep_fill`` (csrc/stac_prep.hip) and
-``summary`` of the gap lengths it returns.
+``summary`` of the gap lengths it returns; and, in front of it, ``reject_outliers`` over ``stac_prep_reject``
+(csrc/stac_outlier.hip): finite but wrong keypoints become missing ones (DESIGN.md "Rejecting keypoint outliers").
 
 A keypoint is missing in a frame when one of its coordinates is NaN or infinite.  Every track is filled along time on its own
 (``linear``: interpolation between its two valid neighbours in double; ``hold``: the nearer neighbour; leading and trailing runs
@@ -10,6 +11,7 @@ missing run: DESIGN.md "Filling missing keypoints".
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import torch
 
@@ -18,11 +20,15 @@ from .engine import StacHipError, _ptr, load_library
 TILE_FRAMES = 64    # csrc/stac_prep.hpp: kPrepTileFrames (frames of a tile of the staged scan)
 MAX_BLOCKS = 1024   # csrc/stac_prep.hpp: kPrepMaxBlocks (workgroups of a launch: the grid strides over the tiles beyond that)
 MODES = {"linear": 0, "hold": 1}  # include/stac_hip.h: STAC_PREP_LINEAR, STAC_PREP_HOLD
+MAX_HALF_WINDOW = 16  # csrc/stac_outlier.hpp: kOutlierMaxHalf (largest half-width of the outlier window)
+MAD_TO_SIGMA = 1.4826  # the median absolute deviation of a normal distribution is sigma / 1.4826
 
 
 def bind(lib):
-    """Argument types of the two entry points (idempotent)."""
+    """Argument types of the entry points (idempotent)."""
     vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
+    lib.stac_prep_reject.restype = i32
+    lib.stac_prep_reject.argtypes = [vp, i64, i32, i32, C.c_double, C.c_double, vp, vp, vp]
     lib.stac_prep_fill_workspace.restype = i64
     lib.stac_prep_fill_workspace.argtypes = [i64, i32]
     lib.stac_prep_fill.restype = i32
@@ -72,6 +78,46 @@ def fill_missing(kp: torch.Tensor, mode: str = "linear"):
     if rc != 0:
         _fail(lib, "stac_prep_fill", rc)
     return out, gap
+
+
+def outlier_params(half_window, n_sigma, min_dev):
+    """-> (h, thr, min_dev) as ``stac_prep_reject`` takes them: ``thr = n_sigma * 1.4826`` in double.  ValueError for a half-width
+    outside 1 .. 16 or a negative or non-finite ``n_sigma`` / ``min_dev``."""
+    if isinstance(half_window, bool) or not isinstance(half_window, int) or not 1 <= half_window <= MAX_HALF_WINDOW:
+        raise ValueError(f"reject_outliers: half_window must be an integer in 1 .. {MAX_HALF_WINDOW}, not {half_window!r}")
+    vals = []
+    for name, v in (("n_sigma", n_sigma), ("min_dev", min_dev)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
+            raise ValueError(f"reject_outliers: {name} must be a finite number >= 0, not {v!r}")
+        vals.append(float(v))
+    thr = vals[0] * MAD_TO_SIGMA
+    if not math.isfinite(thr):
+        raise ValueError(f"reject_outliers: n_sigma = {n_sigma!r} is too large")
+    return half_window, thr, vals[1]
+
+
+def reject_outliers(kp: torch.Tensor, half_window: int = 5, n_sigma: float = 3.0, min_dev: float = 0.0):
+    """Device tensor [T, 3K] -> (out [T, 3K] float32, flag [T, K] uint8), on the current stream of its device: the Hampel
+    identifier per track and coordinate over the frames t - half_window .. t + half_window; a rejected keypoint leaves as three
+    NaN with flag 1, everything else bit for bit.  The input is made contiguous float32 first and is never written."""
+    h, thr, floor = outlier_params(half_window, n_sigma, min_dev)
+    if not isinstance(kp, torch.Tensor) or not kp.is_cuda:
+        raise ValueError("reject_outliers needs a CUDA tensor")
+    if kp.dim() != 2 or kp.shape[1] % 3 != 0 or kp.shape[1] == 0:
+        raise ValueError(f"reject_outliers: kp must be [frames, 3 * keypoints], got {tuple(kp.shape)}")
+    kp = kp.to(dtype=torch.float32).contiguous()
+    T, K = int(kp.shape[0]), int(kp.shape[1]) // 3
+    out = torch.empty_like(kp)
+    flag = torch.empty((T, K), dtype=torch.uint8, device=kp.device)
+    if T == 0:
+        return out, flag
+    lib = bind(load_library())
+    with torch.cuda.device(kp.device):
+        rc = lib.stac_prep_reject(_ptr(kp), T, K, h, thr, floor, _ptr(out), _ptr(flag),
+                                  C.c_void_p(torch.cuda.current_stream(kp.device).cuda_stream))
+    if rc != 0:
+        _fail(lib, "stac_prep_reject", rc)
+    return out, flag
 
 
 def summary(gap) -> dict:

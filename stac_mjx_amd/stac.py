@@ -100,6 +100,28 @@ class Stac:
                       f"longest run {int(info['longest'][k])}")
         return filled.cpu().numpy(), gap.cpu().numpy()
 
+    # -- reject_outliers (engine extension; DESIGN.md "Rejecting keypoint outliers") ------------------------------------
+    def reject_outliers(self, kp_data, half_window=5, n_sigma=3.0, min_dev=0.001):
+        """The Hampel identifier over the whole series ``kp_data`` [T, 3K] on the GPU (``prep.reject_outliers``) ->
+        ``(out [T, 3K] float32, flag [T, K] uint8)`` as numpy arrays: a keypoint with a coordinate further than
+        ``n_sigma * 1.4826`` median absolute deviations, and than ``min_dev``, from the median of the frames
+        ``t - half_window .. t + half_window`` of its track is three NaN in ``out`` and 1 in ``flag``; everything else is the
+        input bit for bit.  One log line per keypoint that had rejections: the count and the share."""
+        from . import prep
+
+        prep.outlier_params(half_window, n_sigma, min_dev)
+        kp = np.asarray(kp_data, dtype=np.float32)
+        if kp.ndim != 2 or kp.shape[1] != 3 * len(self._kp_names):
+            raise ValueError(f"reject_outliers: kp_data must be [frames, {3 * len(self._kp_names)}], got {kp.shape}")
+        if not kp.flags.writeable:  # (torch does not wrap a read-only array)
+            kp = kp.copy()
+        out, flag = prep.reject_outliers(torch.as_tensor(kp).to(self.engine.device), half_window, n_sigma, min_dev)
+        count = flag.sum(dim=0, dtype=torch.int64).cpu().numpy()
+        for k in np.flatnonzero(count):
+            self._log(f"reject_outliers (hampel, window {half_window}, {n_sigma} sigma): {self._kp_names[k]}: {int(count[k])} of "
+                      f"{kp.shape[0]} frames rejected ({100.0 * int(count[k]) / kp.shape[0]:.3f} %)")
+        return out.cpu().numpy(), flag.cpu().numpy()
+
     # -- fit_offsets (stac.py:253-354) ------------------------------------------------------------------
     def fit_offsets(self, kp_data, time_indices=None) -> StacData:
         """Alternate pose and offset optimisation.

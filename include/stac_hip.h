@@ -330,6 +330,53 @@ int32_t stac_prep_fill(const float *kp, int64_t n_frames, int32_t n_kp, int32_t 
 int32_t stac_prep_reject(const float *kp, int64_t n_frames, int32_t n_kp, int32_t half_window, double thr, double min_dev,
                          float *out, uint8_t *flag, void *stream);
 
+/* ---- Fit report: per-keypoint marker errors and exact quantiles (no stac_model needed; the current device is used) ----
+ * DESIGN.md "Fit report".  The device counterpart of the reference's notebook graph_error.ipynb (per-frame summed squared
+ * marker error, its mean / std and histogram), extended by per-keypoint statistics that count observed keypoints only.
+ *
+ * markers[n_frames, n_kp, 3] and kp[n_frames, 3 * n_kp] (float32; marker_sites and kp_data of a result), gap[n_frames, n_kp]
+ * (int32, kp_gap; may be NULL = all zero).  Per pair (t, k): e = d0*d0 + d1*d1 + d2*d2 of d_c = (double)m_c - (double)y_c,
+ * in double, left to right; sqerr = (float)e, or the quiet NaN 0x7FC00000 when one of the six inputs is not finite.  A
+ * pair is COUNTED iff its six inputs are finite and its gap is 0; sqerr is written for every pair, everything below is
+ * over counted pairs.  frame_n[t] = counted keypoints, frame_sse[t] = their e summed in ascending k from +0.0.  Per
+ * keypoint: count, sum (of e; an order of summation that depends on (n_frames, n_kp) only: two calls give the same bits),
+ * max (of sqerr; NaN without a counted frame), argmax (its smallest frame; -1), hist[k, 1024] (counted sqerr by
+ * bits >> 21) and quant[k, q] = s[(permille[q] * (count - 1)) / 1000] of the counted sqerr s in ascending order (NaN
+ * without a counted frame): exact, by a three-pass radix select over the bit patterns with digits of 11 / 11 / 10 bits.
+ * No square root is taken.  Every element of every output is written; the inputs are only read.
+ * permille: HOST int32[n_quant], read before the call returns, n_quant in 1 .. 8, each in 0 .. 1000.  Every other
+ * pointer is a device pointer.  workspace: 8-byte aligned, at least stac_report_workspace bytes, its contents do not
+ * matter; it may be reused once the call has finished on `stream`.  Arrays 4-byte aligned, those of 64-bit elements
+ * 8-byte; no two buffers may overlap (STAC_ERR_INVALID, before anything is launched).  Two memsets and seven launches on
+ * `stream`; no copy to the host, no synchronisation, no workgroup waits for another, no floating-point atomics. */
+typedef struct stac_report_params {
+    const float *markers;
+    const float *kp;
+    const int32_t *gap;      /* may be NULL */
+    int64_t n_frames;
+    int32_t n_kp;
+    int32_t n_quant;
+    const int32_t *permille; /* HOST */
+    float *sqerr;            /* [n_frames, n_kp] */
+    double *frame_sse;       /* [n_frames] */
+    int32_t *frame_n;        /* [n_frames] */
+    int64_t *count;          /* [n_kp] */
+    double *sum;             /* [n_kp] */
+    float *max;              /* [n_kp] */
+    int64_t *argmax;         /* [n_kp] */
+    int64_t *hist;           /* [n_kp, 1024] */
+    float *quant;            /* [n_kp, n_quant] */
+    void *workspace;
+    int64_t workspace_bytes;
+    void *stream;
+} stac_report_params;
+
+/* HOST.  Bytes of device workspace of stac_report_errors; grows with each of the three.  Negative (STAC_ERR_INVALID) for
+ * n_frames < 1, n_kp < 1 or n_quant outside 1 .. 8. */
+int64_t stac_report_workspace(int64_t n_frames, int32_t n_kp, int32_t n_quant);
+
+int32_t stac_report_errors(const stac_report_params *p);
+
 #ifdef __cplusplus
 }
 #endif

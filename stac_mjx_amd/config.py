@@ -34,9 +34,11 @@ _MUJOCO_REQUIRED = ("solver", "iterations", "ls_iterations")
 # postprocess: host (default) | gpu -- where the cross-fade stitch and qvel of a run happen, read from the caller's config;
 # fill_missing: off (default) | linear | hold -- missing keypoints are filled along time before the fit, read from the caller's config;
 # reject_outliers: off (default) | hampel, with outlier_window (half-width, 1 .. 16, default 5), outlier_nsigma (default 3.0) and
-# outlier_min_dev (default 0.001, units of kp_data) -- finite but wrong keypoints become missing ones in front of fill_missing)
+# outlier_min_dev (default 0.001, units of kp_data) -- finite but wrong keypoints become missing ones in front of fill_missing;
+# report: off (default) | on, with report_quantiles (1 .. 8 permille values, default [500, 900, 990]) and report_worst (frames listed,
+# default 10) -- a <result file>.report.json next to every result file, read from the caller's config)
 _STAC_EXTENSIONS = ("solver", "lanes_per_chain", "device", "time_indices", "fit_frames_per_clip", "reference_marker_order", "gather", "gather_max_bytes", "lm_maxiter", "postprocess", "fill_missing",
-                    "reject_outliers", "outlier_window", "outlier_nsigma", "outlier_min_dev")
+                    "reject_outliers", "outlier_window", "outlier_nsigma", "outlier_min_dev", "report", "report_quantiles", "report_worst")
 _MODEL_EXTENSIONS = ("KP_NAMES_LABEL3D_PATH",)
 
 
@@ -68,6 +70,31 @@ def outlier_options(stac) -> tuple:
             raise ConfigError(f"stac.{key} must be a finite number >= 0, not {v!r}")
         vals.append(float(v))
     return mode, h, vals[0], vals[1]
+
+
+REPORT_DEFAULTS = {"report_quantiles": (500, 900, 990), "report_worst": 10}
+REPORT_MAX_QUANTILES = 8  # csrc/stac_report.hpp: kReportMaxQuant
+
+
+def report_options(stac) -> tuple:
+    """``stac.report`` and its two parameters out of a ``stac`` mapping -> (on, permille values, worst), absent keys at their
+    defaults.  ``ConfigError`` for anything else than off | on (or the bool that a bare YAML off / on arrives as), for
+    ``report_quantiles`` that is not a list of 1 .. 8 integers in 0 .. 1000, or a ``report_worst`` that is not an integer >= 0."""
+    mode = stac.get("report", "off")
+    if isinstance(mode, bool) or mode is None:
+        mode = "on" if mode else "off"
+    if not isinstance(mode, str) or mode not in ("off", "on"):
+        raise ConfigError(f"stac.report must be off or on, not {mode!r}")
+    q = stac.get("report_quantiles", REPORT_DEFAULTS["report_quantiles"])
+    if not isinstance(q, (list, tuple)) or not 1 <= len(q) <= REPORT_MAX_QUANTILES:
+        raise ConfigError(f"stac.report_quantiles must be a list of 1 .. {REPORT_MAX_QUANTILES} permille values, not {q!r}")
+    for v in q:
+        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= 1000:
+            raise ConfigError(f"stac.report_quantiles holds permille values, integers in 0 .. 1000, not {v!r}")
+    w = stac.get("report_worst", REPORT_DEFAULTS["report_worst"])
+    if isinstance(w, bool) or not isinstance(w, int) or w < 0:
+        raise ConfigError(f"stac.report_worst must be an integer >= 0, not {w!r}")
+    return mode == "on", tuple(q), w
 
 
 class ConfigNode(dict):
@@ -216,6 +243,9 @@ def validate_config(cfg: dict) -> ConfigNode:
     if stac.get("reject_outliers", "off") is False:
         stac["reject_outliers"] = "off"
     outlier_options(stac)
+    if isinstance(stac.get("report"), bool):  # a bare `off` / `on` in YAML 1.1 is the boolean
+        stac["report"] = "on" if stac["report"] else "off"
+    report_options(stac)
     return _wrap({"model": model, "stac": stac})
 
 

@@ -57,6 +57,7 @@ ABI_SYMBOLS = (
     "stac_jpeg_header", "stac_jpeg_workspace_bytes", "stac_jpeg_encode",
     "stac_post_stitch_rows", "stac_post_stitch", "stac_post_qvel",
     "stac_prep_fill_workspace", "stac_prep_fill", "stac_prep_reject",
+    "stac_report_workspace", "stac_report_errors",
 )  # fmt: skip
 
 

@@ -30,6 +30,8 @@ def run_stac(cfg, kp_data, kp_names, base_path=None, *, setup=None, device=None)
     and adds ``kp_gap`` to both files (DESIGN.md "Filling missing keypoints"); a keypoint without any valid frame is a ``ValueError``.
     ``stac.reject_outliers: hampel`` (needs ``fill_missing``) first turns keypoints that are finite but off their track's sliding
     median into missing ones, on the GPU, and adds ``kp_rejected`` to both files (DESIGN.md "Rejecting keypoint outliers").
+    ``stac.report: on`` computes the marker errors of each phase's final result on the GPU and writes them as
+    ``<result file>.report.json`` next to the file (DESIGN.md "Fit report"); the result files themselves do not change.
     """
     base_path = Path.cwd() if base_path is None else Path(base_path)
     kp_data = np.asarray(kp_data)
@@ -40,10 +42,19 @@ def run_stac(cfg, kp_data, kp_names, base_path=None, *, setup=None, device=None)
             "Ensure kp_data is shaped (n_frames, n_keypoints * 3) and that kp_names length matches the number of "
             "keypoints in kp_data.")
     reject_mode, reject_args = _reject_outliers_mode(cfg)  # (bad values and hampel without fill_missing: before any work)
+    report_on, report_permille, report_worst = _report_mode(cfg)
     start = time.time()
     fit_offsets_path = base_path / cfg.stac.fit_offsets_path
     ik_only_path = base_path / cfg.stac.ik_only_path
     xml_path = base_path / cfg.model.MJCF_PATH
+    if report_on and not cfg.stac.skip_ik_only and bool(cfg.stac.get("reference_marker_order", False)):
+        # (the config that decides the clip length is the one stored with the fit: the caller's, when this run writes it)
+        fit_cfg = cfg if not cfg.stac.skip_fit_offsets else io.load_stac_data(fit_offsets_path)[0]
+        F_rep = int(fit_cfg.stac.n_frames_per_clip)
+        if F_rep > 1 and kp_data.shape[0] // max(F_rep, 1) > 1:
+            raise ValueError("stac.report = on cannot pair marker_sites with kp_data in the reference's frame-major row order "
+                             "(stac.reference_marker_order: true with more than one clip of more than one frame): the rows of "
+                             "marker_sites are then not the rows of kp_data")
     stac = Stac(xml_path, cfg, kp_names, setup=setup, device=device)
     if not cfg.stac.skip_ik_only and dist.world()[1] > 1 and str(cfg.stac.get("gather", "auto") or "auto") == "none":
         # an EXPLICIT gather = none cannot serve a continuous run (cross-fades reach across shard borders): say so before any
@@ -91,6 +102,8 @@ def run_stac(cfg, kp_data, kp_names, base_path=None, *, setup=None, device=None)
         if kp_rejected is not None:
             fit_data.kp_rejected = kp_rejected[: fit_data.kp_data.shape[0]]
         if dist.world()[0] == 0:  # multi-GPU: rank 0 holds the gathered result and writes it
+            if report_on:
+                _write_report(stac, fit_data, fit_offsets_path, report_permille, report_worst)
             io.save_data_to_h5(config=cfg, file_path=fit_offsets_path, **fit_data.as_dict())
         fit_offsets_path = io.resolve_output_path(fit_offsets_path)
         dist.barrier()
@@ -142,6 +155,8 @@ def run_stac(cfg, kp_data, kp_names, base_path=None, *, setup=None, device=None)
         n_clips = kp_data.shape[0] // F
         lo, hi = dist.shard_range(n_clips)
         shard = io.shard_path(ik_only_path, rank, world_size)
+        if report_on:  # (of this rank's clips; shard reports are not merged)
+            _write_report(stac, ik_data, shard, report_permille, report_worst)
         io.save_data_to_h5(config=cfg, file_path=shard, **ik_data.as_dict())
         dist.barrier()
         manifest = io.manifest_path(ik_only_path)
@@ -152,11 +167,44 @@ def run_stac(cfg, kp_data, kp_names, base_path=None, *, setup=None, device=None)
               f"Finished in {(time.time() - start) / 60:.2f} minutes")
         return fit_offsets_path, manifest
     if rank == 0:
+        if report_on:
+            _write_report(stac, ik_data, ik_only_path, report_permille, report_worst)
         io.save_data_to_h5(config=cfg, file_path=ik_only_path, **ik_data.as_dict())
     ik_only_path = io.resolve_output_path(ik_only_path)
     dist.barrier()
     print(f"Saved ik_only to {ik_only_path}. Finished in {(time.time() - start) / 60:.2f} minutes")
     return fit_offsets_path, ik_only_path
+
+
+def report_path(result_path) -> Path:
+    """``fit.h5`` -> ``fit.h5.report.json`` (of the name the result file really has: ``io.resolve_output_path``)."""
+    p = io.resolve_output_path(result_path)
+    return p.with_name(p.name + ".report.json")
+
+
+def _report_mode(cfg) -> tuple:
+    """``stac.report``: "off" (default) | "on" -> (on, permille values of ``stac.report_quantiles``, ``stac.report_worst``).
+    ``ValueError`` for a bad value of any of the three keys."""
+    from .config import report_options
+
+    return report_options(cfg.stac)
+
+
+def _write_report(stac, data, result_path, permille, worst) -> Path:
+    """The report of a phase's final ``StacData``, computed on the device, as JSON next to the result file that is about to be
+    written, and two lines of it to the log."""
+    import json
+
+    from . import report
+
+    summary = stac.fit_report(data, permille, worst)
+    path = report_path(result_path)
+    path.parent.mkdir(parents=True, exist_ok=True)
+    path.write_text(json.dumps(summary, indent=1) + "\n")
+    for line in report.overall_lines(summary):
+        print(line)
+    print(f"report: wrote {path}", flush=True)
+    return path
 
 
 def _postprocess_mode(cfg) -> str:

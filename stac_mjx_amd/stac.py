@@ -122,6 +122,36 @@ class Stac:
                       f"{kp.shape[0]} frames rejected ({100.0 * int(count[k]) / kp.shape[0]:.3f} %)")
         return out.cpu().numpy(), flag.cpu().numpy()
 
+    # -- fit_report (engine extension; DESIGN.md "Fit report") -----------------------------------------------------------
+    def fit_report(self, data, permille=None, worst=None) -> dict:
+        """The marker error of a result, on the GPU (``report.fit_errors``), as the summary of ``report.summarize``: per keypoint
+        the number of observed frames, the rms, the quantiles and the maximum of the distance between the fitted marker and the
+        keypoint, over all keypoints the same, and the frames of largest summed squared error.  ``data``: a ``StacData`` or the
+        path of a result file (a ``*.manifest.json`` reads a sharded run); its ``kp_gap``, when it has one, keeps filled
+        keypoints out of every statistic.  ``permille`` / ``worst``: None = ``stac.report_quantiles`` / ``stac.report_worst``
+        of the config.  One log line per keypoint."""
+        from . import io, report
+        from .config import report_options
+
+        _, cfg_perm, cfg_worst = report_options(self.cfg.stac)
+        permille = report.check_permille(cfg_perm if permille is None else permille)
+        worst = cfg_worst if worst is None else worst
+        if not isinstance(data, StacData):
+            path = Path(data)
+            data = (io.load_sharded_stac_data(path) if path.name.endswith(".manifest.json") else io.load_stac_data(path))[1]
+        markers = np.asarray(data.marker_sites, dtype=np.float32)
+        kp = np.asarray(data.kp_data, dtype=np.float32)
+        if markers.ndim != 3 or markers.shape[2] != 3 or kp.ndim != 2 or kp.shape != (markers.shape[0], 3 * markers.shape[1]):
+            raise ValueError(f"fit_report: marker_sites {markers.shape} and kp_data {kp.shape} are not [frames, K, 3] and [frames, 3K]")
+        gap = np.asarray(data.kp_gap)
+        dev = self.engine.device
+        to_dev = lambda a: torch.as_tensor(np.array(a)).to(dev)  # noqa: E731  (a copy: torch does not wrap a read-only array)
+        res = report.fit_errors(to_dev(markers), to_dev(kp), to_dev(gap.astype(np.int32)) if gap.size else None, permille)
+        summary = report.summarize(res, list(data.kp_names), worst=worst, permille=permille)
+        for line in report.table_lines(summary):
+            self._log(line)
+        return summary
+
     # -- fit_offsets (stac.py:253-354) ------------------------------------------------------------------
     def fit_offsets(self, kp_data, time_indices=None) -> StacData:
         """Alternate pose and offset optimisation.

@@ -71,7 +71,7 @@ static int fail(int code, const std::string &msg) {
 // set later cannot change the launch shape of a model in use.  -1 = not set.
 struct DebugSwitches {
     int flags = -1, spec = -1, specg = -1, specr = -1, wpe = -1, wpb = -1, handoff = -1, queue = -1, stride_add = -1, rsplit = -1;
-    bool noprune = false, verbose = false, nofast = false, nofree0 = false, noorder = false, nodiet = false, nolean = false, nofk3 = false, nofk3bq = false;
+    bool noprune = false, verbose = false, nofast = false, nofree0 = false, noorder = false, nodiet = false, nolean = false, nofk3 = false, nofk3bq = false, nowsum = false;
     static int geti(const char *name) {
         const char *v = getenv(name);
         return v ? atoi(v) : -1;
@@ -80,10 +80,37 @@ struct DebugSwitches {
         flags = geti("STAC_HIP_FLAGS"); spec = geti("STAC_HIP_SPEC"); wpe = geti("STAC_HIP_WPE"); wpb = geti("STAC_HIP_WPB");
         handoff = geti("STAC_HIP_HANDOFF"); queue = geti("STAC_HIP_QUEUE"); specg = geti("STAC_HIP_SPECG"); specr = geti("STAC_HIP_SPECR"); stride_add = geti("STAC_HIP_STRIDE_ADD"); rsplit = geti("STAC_HIP_RSPLIT");
         noprune = getenv("STAC_HIP_NOPRUNE") != nullptr; nofast = getenv("STAC_HIP_NOFAST") != nullptr; nofree0 = getenv("STAC_HIP_NOFREE0") != nullptr; noorder = getenv("STAC_HIP_NOORDER") != nullptr; nolean = getenv("STAC_HIP_NOLEAN") != nullptr; nodiet = getenv("STAC_HIP_NODIET") != nullptr; verbose = getenv("STAC_HIP_VERBOSE") != nullptr;
-        nofk3 = getenv("STAC_HIP_NOFK3") != nullptr; nofk3bq = getenv("STAC_HIP_NOFK3BQ") != nullptr;
+        nofk3 = getenv("STAC_HIP_NOFK3") != nullptr; nofk3bq = getenv("STAC_HIP_NOFK3BQ") != nullptr; nowsum = getenv("STAC_HIP_NOWSUM") != nullptr;
     }
 };
 
+// The wrench-sum program of a model (WsumRec, stac_plan.hpp): which of its distinct site ranges come out of row sweeps, which are
+// component tasks (with which checkpoint) and which whole ranges.  `ranges` are sorted longest first (build_plan).  parts: bit 0 = plan
+// sweeps, bit 1 = plan checkpoints; with neither the program is PlanHeader::rsplit's split (ntask_fixed) in the program's form.
+struct WsumProgram {
+    int ntask = 0, nwhole = 0, nrows = 0, depth = 0;
+    int row_start[3] = {0, 0, 0};  // rows [row_start[i], row_start[i + 1]) of sorted sites
+    std::vector<WsumRec> recs;     // the tasks, then the whole ranges
+    std::vector<int32_t> rows;     // per (row, lane): {kXf * sorted site (a lane behind the row's end: the row's last), capture bytes:
+                                   // byte s = the range whose sum the lane holds after step s, kWsumNone = nobody's}
+    double cost = 0.0;
+    // the table as the kernel reads it; c_rw: where the range sums stand in a chain's region, dump: six words of it that a full trip
+    // neither reads nor keeps -- where a lane stores a sum that is nobody's
+    std::vector<int32_t> table(int c_rw, int dump) const {
+        std::vector<int32_t> w;
+        for (const WsumRec &r : recs) { w.push_back(r.lo); w.push_back(r.mid); w.push_back(r.hi); w.push_back(r.rids); }
+        for (size_t i = 0; i < rows.size(); i += 2) {
+            uint32_t at[kWsumMaxDepth];
+            for (int s2 = 0; s2 < kWsumMaxDepth; ++s2) {
+                const int rid = (rows[i + 1] >> (8 * s2)) & 0xFF;
+                at[s2] = (uint32_t)(rid == kWsumNone ? dump : c_rw + kXf * rid) & 0xFFFFu;
+            }
+            w.push_back(rows[i]); w.push_back((int32_t)(at[0] | at[1] << 16)); w.push_back((int32_t)(at[2] | at[3] << 16)); w.push_back(rows[i + 1]);
+        }
+        return w;
+    }
+    int32_t counts() const { return ntask | nwhole << 8 | nrows << 16 | depth << 24; }
+};
 struct stac_model {
     int device = 0;   // the HIP device the model lives on: every entry point runs with it current (and restores)
     int cus = 256;    // its compute units (hipDeviceAttributeMultiprocessorCount: 256 on a whole MI355X; fewer on a partition or under a CU mask):
@@ -115,6 +142,8 @@ struct stac_model {
     std::vector<float> h_aj_pos;
     int n_mlev_root = 0;        // micro-levels of the root-pass program currently in the blob (0 = none)
     int n_run_root = 0;         // of which the leading ones have work (n_mlev_root is padded to an even count)
+    WsumProgram wsum;           // the wrench-sum program of the lean 16-lane throughput kernels
+    int off_wsum = 0;           // ... and where its table stands in the blob (0: the model has none)
     PlanHeader h3{};            // h with the chain layout of a lean launch (split kinematics, PlanHeader::fk3); valid when h.fk3
     int fk3r = 0;  // the pruned FK3 program currently in the blob: its counts packed like PlanHeader::fk3_n (0: none)
     std::vector<float> h_bpos;  // body_pos of the active bodies, by slot
@@ -571,6 +600,116 @@ static bool build_fk3_program(const stac_model *m, const PlanHeader &h3, const c
 // ------------------------------------------------------------------------------------------------
 // plan construction
 // ------------------------------------------------------------------------------------------------
+static WsumProgram build_wsum_program(const std::vector<RangeRec> &ranges, int K, int parts, int ntask_fixed) {
+    const int nr = (int)ranges.size();
+    auto len = [&](int r) { return ranges[r].hi - ranges[r].lo; };
+    // Cost of a choice, in instructions of the wavefront, with a dependent LDS round trip counted as twelve (a heuristic, from the
+    // instruction counts and phase times of profiles/r10/wrench_sums.md).  A round of lanes is as long as its longest loop, and runs the
+    // remainder block if any of its lanes has a remainder.  Component tasks: 47 + 25 per trip of four sites + 27 for the remainder; a
+    // checkpoint adds the store and a second pair of loops.  Whole ranges: 42 + 62 per trip + 72.  Sweeps, per row: the record, the
+    // entry and A_0 (11), six additions per further step, five instructions per step for the stores, two round trips.
+    auto round_cost = [&](const std::vector<int> &lens, bool task, bool ckpt) {
+        int trips = 0;
+        bool rem = false;
+        for (const int n : lens) { trips = std::max(trips, n / 4); rem = rem || (n % 4) != 0; }
+        return task ? 47.0 + 25.0 * trips + (rem ? 27.0 : 0.0) + (ckpt ? 10.0 : 0.0) : 42.0 + 62.0 * trips + (rem ? 72.0 : 0.0);
+    };
+    WsumProgram best;
+    bool have = false;
+    const int max_depth = (parts & 1) && nr < kWsumNone ? kWsumMaxDepth : 0;
+    for (int depth = 0; depth <= max_depth; ++depth) {
+        // rows: as few as hold the sites; with two, the cut may sit wherever both keep to 16 sites
+        const int cut_lo = depth == 0 || K <= 16 ? 0 : K - 16, cut_hi = depth == 0 || K <= 16 ? 0 : 16;
+        for (int cut = cut_lo; cut <= cut_hi; ++cut) {
+            WsumProgram pr;
+            pr.depth = depth;
+            if (depth > 0) {
+                pr.nrows = cut > 0 ? 2 : 1;
+                pr.row_start[1] = cut > 0 ? cut : K;
+                pr.row_start[2] = K;
+            }
+            std::vector<char> swept(nr, 0);
+            if (depth > 0) {
+                pr.rows.assign((size_t)pr.nrows * 32, 0);
+                for (int row = 0; row < pr.nrows; ++row)
+                    for (int l = 0; l < 16; ++l) {
+                        pr.rows[2 * (row * 16 + l)] = kXf * std::min(pr.row_start[row] + l, pr.row_start[row + 1] - 1);
+                        pr.rows[2 * (row * 16 + l) + 1] = (int32_t)0xFFFFFFFFu;  // (kWsumNone in every byte)
+                    }
+                for (int r = 0; r < nr; ++r) {
+                    if (len(r) < 1 || len(r) > depth) continue;
+                    const int row = (pr.nrows == 2 && ranges[r].lo >= cut) ? 1 : 0;
+                    if (ranges[r].hi > pr.row_start[row + 1]) continue;  // crosses the cut: not a sweep's
+                    swept[r] = 1;
+                    int32_t &cap = pr.rows[2 * (row * 16 + ranges[r].hi - 1 - pr.row_start[row]) + 1];
+                    const int sh = 8 * (len(r) - 1);
+                    cap = (int32_t)(((uint32_t)cap & ~(0xFFu << sh)) | ((uint32_t)r << sh));
+                }
+                pr.cost += pr.nrows * (11.0 + 6.0 * (depth - 1) + 5.0 * depth + 24.0);
+                bool any_swept = false;
+                for (int r = 0; r < nr; ++r) any_swept = any_swept || swept[r];
+                if (!any_swept) continue;  // (depth 0 is this program without the rows)
+            }
+            // what is left, longest first; a range takes the longest shorter one with its first site as its checkpoint
+            std::vector<int> rest, ckpt(nr, -1), owner(nr, -1);
+            for (int r = 0; r < nr; ++r)
+                if (!swept[r]) rest.push_back(r);
+            if (parts & 2)
+                for (size_t i = 0; i < rest.size(); ++i) {
+                    const int r = rest[i];
+                    if (owner[r] >= 0) continue;
+                    for (size_t j = i + 1; j < rest.size(); ++j) {
+                        const int c = rest[j];
+                        if (owner[c] < 0 && ckpt[c] < 0 && ranges[c].lo == ranges[r].lo && len(c) >= 1 && len(c) < len(r)) {
+                            ckpt[r] = c; owner[c] = r;
+                            break;
+                        }
+                    }
+                }
+            std::vector<int> units;
+            for (const int r : rest)
+                if (owner[r] < 0) units.push_back(r);
+            const int nu = (int)units.size();
+            const int ns_lo = ntask_fixed >= 0 ? std::min(ntask_fixed, nu) : 0, ns_hi = ntask_fixed >= 0 ? ns_lo : nu;
+            for (int ns = ns_lo; ns <= ns_hi; ++ns) {
+                WsumProgram q = pr;
+                q.ntask = ns;
+                for (int u = 0; u < ns; ++u) {
+                    const int r = units[u], c = ckpt[r];
+                    q.recs.push_back(WsumRec{ranges[r].lo, c >= 0 ? ranges[c].hi : ranges[r].hi, ranges[r].hi, (c >= 0 ? c : r) | r << 16});
+                }
+                std::vector<char> is_task(nr, 0);
+                for (int u = 0; u < ns; ++u) { is_task[units[u]] = 1; if (ckpt[units[u]] >= 0) is_task[ckpt[units[u]]] = 1; }
+                for (const int r : rest)
+                    if (!is_task[r]) { q.recs.push_back(WsumRec{ranges[r].lo, ranges[r].hi, ranges[r].hi, r | r << 16}); ++q.nwhole; }
+                for (int t0 = 0; t0 < 6 * ns; t0 += 16) {
+                    std::vector<int> lens;
+                    bool ck = false;
+                    for (int t1 = t0; t1 < std::min(t0 + 16, 6 * ns); ++t1) {
+                        const WsumRec &w = q.recs[t1 / 6];
+                        lens.push_back(w.mid - w.lo); lens.push_back(w.hi - w.mid);
+                        ck = ck || w.mid != w.hi;
+                    }
+                    // (two loops in series: the trips of both; one remainder block each at the most)
+                    std::vector<int> l1, l2;
+                    for (size_t i = 0; i < lens.size(); i += 2) { l1.push_back(lens[i]); l2.push_back(lens[i + 1]); }
+                    q.cost += round_cost(l1, true, ck) + (ck ? round_cost(l2, true, false) - 47.0 : 0.0);
+                }
+                for (int r0 = 0; r0 < q.nwhole; r0 += 16) {
+                    std::vector<int> lens;
+                    for (int r1 = r0; r1 < std::min(r0 + 16, q.nwhole); ++r1) lens.push_back(q.recs[ns + r1].hi - q.recs[ns + r1].lo);
+                    q.cost += round_cost(lens, false, false);
+                }
+                q.cost += q.ntask + q.nwhole;  // (among equals: the cut that fewer short ranges cross)
+                if (q.ntask > 255 || q.nwhole > 255) continue;
+                if (!have || q.cost < best.cost) { best = q; have = true; }
+            }
+        }
+    }
+    return best;
+}
+
+static bool thr_lean_holds(const PlanHeader &h, int G);
 static int build_plan(stac_model *m, const stac_model_tables *t) {
     const int nb = t->nbody, nj = t->njnt, nq = t->nq, K = t->nsite;
     if (nb < 2 || nq < 1 || K < 1) return fail(STAC_ERR_INVALID, "model needs >= 1 body, qpos and fit site");
@@ -788,6 +927,23 @@ static int build_plan(stac_model *m, const stac_model_tables *t) {
     }
     h.off_lev_adr = put_raw(lev_adr.data(), lev_adr.size());
     h.off_body = put_raw(brec.data(), brec.size() * sizeof(BodyRec) / 4);
+    {   // The wrench-sum program (WsumRec, stac_plan.hpp) of a model that the lean 16-lane throughput kernels can take: the conditions of
+        // the split kinematics below that are known by now, and a 16-lane lean shape that holds the model.  Its table stands in front
+        // of the momentum table, so that only a lean throughput launch stages it (plan_q, lean_header).  STAC_HIP_NOWSUM (read at model
+        // creation): no sweeps and no checkpoints -- PlanHeader::rsplit's split in the program's form, what the kernels ran before.
+        m->off_wsum = 0;
+        m->wsum = WsumProgram{};
+        bool lean16 = kWsum != 0 && naj >= 1 && aj_type[0] == STAC_JNT_FREE && aj_qadr[0] == 0 && ab_jnum[0] >= 1 && ab_jadr[0] == 0 && nqj == 1 &&
+                      !has_ball && !m->dbg.nofk3 && h.nrange < kWsumNone && thr_lean_holds(h, 16);
+        for (int j = 1; j < naj && lean16; ++j) lean16 = aj_type[j] == STAC_JNT_HINGE;
+        for (int s = 1; s < nab && lean16; ++s) lean16 = ab_parent[s] != 0;
+        if (lean16) {
+            const int parts = m->dbg.nowsum ? 0 : kWsum;
+            m->wsum = build_wsum_program(ranges, K, parts, parts == 0 ? h.rsplit : (m->dbg.rsplit >= 0 ? m->dbg.rsplit : -1));
+            const std::vector<int32_t> tab = m->wsum.table(0, 0);  // (the words of the lean layout follow once it is made: below)
+            m->off_wsum = put_raw(tab.data(), tab.size());
+        }
+    }
     {   // momentum table (stac_plan.hpp, kTTab): the kernel's expressions, float32, no contraction (build flags)
         std::vector<float> tt(2 * kTTab);
         float tk = 1.0f;
@@ -945,11 +1101,18 @@ static int build_plan(stac_model *m, const stac_model_tables *t) {
     h.total_words = (int)B.size();
 
     h.chain_stride = h.stride_lds;
+    if (!h.fk3) { m->off_wsum = 0; m->wsum = WsumProgram{}; }  // (no lean kernel after all: nobody stages the table)
     if (h.fk3) {  // the lean layout's copy of everything that was settled after it was made
         PlanHeader &g = m->h3;
         g.fk_rec_words = h.fk_rec_words; g.n_mlev_hdr = h.n_mlev_hdr; g.fk_hdr_words = h.fk_hdr_words; g.off_fkstep = h.off_fkstep;
         g.off_fkroot = h.off_fkroot; g.n_mlev = h.n_mlev; g.fk_uniform = h.fk_uniform; g.total_words = h.total_words;
         g.chain_stride = g.stride3;
+        if (m->off_wsum) {  // the sweeps' store words: the range sums' entries, and for a sum that is nobody's the root fast trip's entry
+                            // (c3_rw0: a full trip does not touch it, and a root fast trip writes it before it reads it)
+            if (g.c_rw + kXf * h.nrange > 0xFFFF || g.c3_rw0 + kXf > 0xFFFF) return fail(STAC_ERR_CAPACITY, "plan: chain region too large for the wrench-sum program");
+            const std::vector<int32_t> tab = m->wsum.table(g.c_rw, g.c3_rw0);
+            std::memcpy(B.data() + m->off_wsum, tab.data(), tab.size() * sizeof(int32_t));
+        }
     }
     return STAC_OK;
 }
@@ -1273,7 +1436,7 @@ struct QLaunch {
     int wpb = 0;     // wavefronts per workgroup (0: no launch)
     size_t lds = 0;  // dynamic LDS per workgroup
     PlanHeader h{};  // what it stages: chain layout and chain_stride, LDS diet -- rebased (rebase_plan_offsets)
-    int mb_words = 0, free0p = 0, flags = 0, root_fast = 0, place_crowded = 0;
+    int mb_words = 0, free0p = 0, flags = 0, root_fast = 0, place_crowded = 0, off_wsum = 0, wsum = 0;
     bool keep_perm = false, keep_place = false;  // the request's chain order / placement work space (QArgs::perm / place)
 };
 // The launches of a call: the main one, and the latency kernel's resume launch of a straggler hand-off (resume.wpb > 0), after
@@ -1304,6 +1467,7 @@ static int plan_q(const stac_model *m, const stac_q_params *p, const QArgs &req,
     auto lean_header = [&](bool thr) {
         PlanHeader hh = m->h3;
         hh.plan_skip = mh.off_joint - (thr ? 2 * kTTab : 0);
+        if (thr && m->off_wsum) hh.plan_skip = m->off_wsum;  // (the wrench-sum program's table stands right in front of the momentum table)
         const int area = 16 * (hh.fk3_cap1 + 2) + 4 * hh.fk3_cap2 + 4 * hh.fk3_cap3 + hh.K + hh.naj;
         hh.total_words = (req.do_root_opt && req.fk3r_n != 0) ? hh.off3_root + area : hh.off3_root;
         return hh;
@@ -1314,6 +1478,9 @@ static int plan_q(const stac_model *m, const stac_q_params *p, const QArgs &req,
         L.h.chain_stride = q_chain_stride(h, inst.G);
         rebase_plan_offsets(L.h);
         L.mb_words = q_mb_words(nkinds, inst.G); L.free0p = free0p; L.flags = flags; L.root_fast = req.root_fast;
+        // (the wrench-sum program: its table is staged by a lean throughput launch alone, in front of everything else -- lean_header)
+        const bool wsum = inst.specp == 1 && inst.G == 16 && m->off_wsum && L.h.plan_skip == m->off_wsum;
+        L.off_wsum = wsum ? m->off_wsum - L.h.plan_skip : 0; L.wsum = wsum ? m->wsum.counts() : 0;
     };
     // (`likely_lean` only serves the shape heuristics before the lanes are known; every launch decides from its own flags and lanes)
     const bool likely_lean = mh.fk3 && !req.single && !req.bounds && !dbg.nolean && !(dbg.flags >= 0 && dbg.flags != 0);
@@ -1381,6 +1548,7 @@ static int plan_q(const stac_model *m, const stac_q_params *p, const QArgs &req,
         const long waves_needed = ((long)nchains * G + 63) / 64;
         PlanHeader h = lean ? lean_header(true) : mh;
         if (!lean) { h.total_words = mh.core_words; h.plan_skip = 0; }
+        if (lean && G == 16 && kWsum != 0 && !m->off_wsum) return fail(STAC_ERR_INVALID, "plan: a lean 16-lane launch of a model without a wrench-sum program");
         QShape sh = pick_shape(h, G, nkinds, cus, waves_needed, lean ? kThrLean : kThr);
         if (!sh.wpb) continue;  // no instantiation holds nq, or it does not fit the LDS with this many chains per wave: widen the group
         int flags = flags_in;
@@ -1489,7 +1657,7 @@ static int plan_q(const stac_model *m, const stac_q_params *p, const QArgs &req,
 // The QArgs of one launch of a plan: the caller's request with what the plan decided
 static QArgs launch_args(const QArgs &req, const QLaunch &L) {
     QArgs q = req;
-    q.h = L.h; q.mb_words = L.mb_words; q.free0p = L.free0p; q.flags = L.flags; q.root_fast = L.root_fast; q.place_crowded = L.place_crowded;
+    q.h = L.h; q.mb_words = L.mb_words; q.free0p = L.free0p; q.flags = L.flags; q.root_fast = L.root_fast; q.place_crowded = L.place_crowded; q.off_wsum = L.off_wsum; q.wsum = L.wsum;
     if (!L.keep_perm) q.perm = nullptr;
     if (!L.keep_place) q.place = nullptr;
     return q;
@@ -1551,6 +1719,9 @@ static int run_q(const stac_model *m, const stac_q_params *p, QArgs a, int nchai
         fprintf(stderr, "[stac profile head] stage=%.0f", (double)h[1] / trips);
         for (int i = 0; i < 5; ++i) { fprintf(stderr, " %s=%.0f", subs[i], (double)h[16 + i] / trips); sub_tot += h[16 + i]; }
         fprintf(stderr, " rest=%.0f loop=%.0f\n", ((double)h[1] - (double)sub_tot) / trips, (double)h[0] / trips);
+        // the sub-stamps inside the range sums (stamps 3 -> 5; the names are those of a build with the wrench-sum program)
+        fprintf(stderr, "[stac profile wsum] range_sums=%.0f sweeps_or_round1=%.0f tasks_or_round2=%.0f whole=%.0f rest=%.0f\n", (double)h[5] / trips,
+                (double)h[21] / trips, (double)h[22] / trips, (double)h[23] / trips, ((double)h[5] - (double)(h[21] + h[22] + h[23])) / trips);
     }
 #endif
     return STAC_OK;
@@ -2433,5 +2604,38 @@ extern "C" int32_t stac_debug_fk3_program(const stac_model_tables *t, const uint
     info[0] = 1; info[1] = pr.n1; info[2] = pr.n2; info[3] = pr.n3; info[4] = pr.nrot; info[5] = h.fk3_cap2;
     info[6] = m.h3.c3_qb; info[7] = m.h3.c3_pb + 3 * (h.fk3_cap3 * 4 + 1);
     if (t2) std::memcpy(t2, pr.words.data() + 16 * (h.fk3_cap1 + 2), sizeof(int32_t) * 4 * (size_t)std::max(0, std::min(h.fk3_cap2, cap_tasks)));
+    return STAC_OK;
+}
+
+// Diagnostics, as stac_debug_fk3_program (tests/test_wrench_sweep_host.py, tests/test_gpu_wrench_sweeps.py): the wrench-sum program of a
+// model (WsumRec, stac_plan.hpp), built on the host alone.  out[0 .. 23] = {1 if the model has a program, component tasks, whole ranges,
+// rows, depth, row_start[0 .. 2], distinct ranges, K, words of the table, words a lean throughput launch without root program stages,
+// its chain stride at 16 lanes, its LDS bytes for one wavefront per workgroup and three solve kinds (q_lds_bytes), the words of its
+// mask table, kXf, c_sw, c_rw of the lean layout, PlanHeader::rsplit, the staged words without the table, c3_rw0 (the sweeps' dump
+// entry), c3_ql, stride3, 0}; then {lo, hi} of every
+// distinct range; then the table.  Nothing beyond out[cap_words) is written; returns STAC_OK, or an error if cap_words is too small.
+extern "C" int32_t stac_debug_wsum_program(const stac_model_tables *t, int32_t *out, int32_t cap_words) {
+    if (!t || !out) return fail(STAC_ERR_INVALID, "null argument");
+    stac_model m;
+    m.dbg.read_env();
+    if (const int rc = build_plan(&m, t)) return rc;
+    const std::vector<float> &B = m.blob_host;
+    const std::vector<int32_t> tab = m.wsum.table(0, 0);
+    const int need = 24 + 2 * m.h.nrange + (int)tab.size();
+    if (cap_words < need) return fail(STAC_ERR_CAPACITY, "stac_debug_wsum_program: the buffer is too small");
+    for (int i = 0; i < need; ++i) out[i] = 0;
+    out[8] = m.h.nrange; out[9] = m.h.K; out[15] = kXf; out[18] = m.h.rsplit;
+    std::memcpy(out + 24, B.data() + m.h.off_range, sizeof(int32_t) * 2 * (size_t)m.h.nrange);
+    if (!m.off_wsum) return STAC_OK;
+    out[0] = 1; out[1] = m.wsum.ntask; out[2] = m.wsum.nwhole; out[3] = m.wsum.nrows; out[4] = m.wsum.depth;
+    for (int i = 0; i < 3; ++i) out[5 + i] = m.wsum.row_start[i];
+    out[10] = (int)tab.size();
+    PlanHeader hh = m.h3;  // (plan_q, lean_header(true), without the root program)
+    hh.plan_skip = m.off_wsum;
+    hh.total_words = hh.off3_root;
+    out[11] = hh.total_words - hh.plan_skip; out[12] = q_chain_stride(hh, 16); out[13] = (int32_t)q_lds_bytes(hh, 16, 3, 1);
+    out[14] = q_mb_words(3, 16); out[16] = hh.c_sw; out[17] = hh.c_rw; out[19] = hh.off3_root - (m.h.off_joint - 2 * kTTab);
+    out[20] = hh.c3_rw0; out[21] = hh.c3_ql; out[22] = hh.stride3;
+    std::memcpy(out + 24 + 2 * m.h.nrange, B.data() + m.off_wsum, sizeof(int32_t) * tab.size());  // (what the launch stages, not a copy of it)
     return STAC_OK;
 }

@@ -91,6 +91,12 @@ __device__ __forceinline__ float row_bcast(float v) {
     const int i = __builtin_bit_cast(int, v);
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(i, i, 0x150 + L, 0xF, 0xF, true));
 }
+// The value held by the lane BEFORE the caller's in its 16-lane row; lane 0 of a row gets +0 (DPP row_shr:1 with bound_ctrl: the compiler
+// folds the move into the addition that takes it, and places the hazard distances)
+__device__ __forceinline__ float row_shr1(float v) {
+    const int i = __builtin_bit_cast(int, v);
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, i, 0x111, 0xF, 0xF, true));
+}
 // Pairwise-tree sum over the elements e = r*G + lane_in_group of a striped vector (zeros beyond nq):
 // lane butterflies for the levels below G, then the registers.  Every lane of the group gets the sum.
 // (Round 6 tried gfx950's v_permlane16_swap / v_permlane32_swap for the two levels that cross a 16-lane row, instead of ds_swizzle /
@@ -167,7 +173,8 @@ enum PinClass { PIN_N = 0, PIN_S = 1, PIN_V = 2, PIN_C = 3 };
 #define STAC_HOT_ARGS_FIELDS(X)                                                                                                \
     X(single, STAC_PIN_CTL) X(P, STAC_PIN_CTL2) X(flags, STAC_PIN_CTL) X(free0p, STAC_PIN_CTL) X(root_fast, STAC_PIN_CTL)       \
     X(n_mlev_root, STAC_PIN_CTL2) X(n_run_root, STAC_PIN_CTL2) X(n_root_joints, STAC_PIN_CTL2) X(maxls, STAC_PIN_CTL)           \
-    X(maxiter, STAC_PIN_CTL2) X(queue_slots, N) X(resume, N) X(root_trunk_lo, N) X(root_trunk_hi, N) X(tol, STAC_PIN_CTL2)
+    X(maxiter, STAC_PIN_CTL2) X(queue_slots, N) X(resume, N) X(root_trunk_lo, N) X(root_trunk_hi, N) X(tol, STAC_PIN_CTL2) \
+    X(off_wsum, N) X(wsum, N)
 // (VPIN: 1 = class V fields are pinned in vector registers; bit 1 set = class C fields are pinned in scalar registers)
 template <int VPIN, PinClass C, class T>
 __device__ __forceinline__ T pin_as(T v) {
@@ -212,6 +219,7 @@ struct HotArgs {  // QArgs fields of every trip (values)
     int32_t single, P, flags, free0p, root_fast, n_mlev_root, n_run_root, n_root_joints, maxls, maxiter, queue_slots, resume;
     uint32_t root_trunk_lo, root_trunk_hi;
     float tol;
+    int32_t off_wsum, wsum;
 };
 template <int VPIN, class KA>
 __device__ __forceinline__ HotArgs pin_args(const KA &a) {
@@ -247,7 +255,7 @@ enum : int { ST_VG_Y = 0, ST_LS = 1, ST_VG_X = 2, ST_DONE = 3, ST_SPEC = 4, ST_W
 // In-kernel phase stamps: diagnostic build only (-DSTAC_PROFILE -> libstac_hip_prof.so); the stamps
 // go to a buffer of their own and feed no output.  Read the SHARES, not the run time.
 #ifdef STAC_PROFILE
-constexpr int kProfSub = 5;
+constexpr int kProfSub = 8;
 // -DSTAC_PROFILE_SEL=1: only root fast (lite) trips are accumulated; =0: only the others; undefined: all trips
 #define PROF_DECL unsigned long long pt0 = __builtin_readcyclecounter(), pacc[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, ptmp[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; unsigned long long ptrip0 = pt0; \
     unsigned long long ps0 = pt0, psub[kProfSub] = {0, 0, 0, 0, 0}, psacc[kProfSub] = {0, 0, 0, 0, 0}
@@ -262,6 +270,9 @@ constexpr int kProfSub = 5;
 // figure stays what it was; what the sub-stamps leave of it is the stretch behind the last of them.
 //   0 = kernarg views, 1 = hand-off block, 2 = root phase, chain queue and the votes up to `lite`, 3 = staging stores,
 //   4 = the free root's pre-pass and its wave_sync()
+// and inside the range sums of a full trip (stamps 3 -> 5, lean 16-lane throughput kernels; round 10): 5 = the row sweeps (without the
+// wrench-sum program: the first round of component tasks), 6 = the component tasks (the second round), 7 = the whole ranges; what they
+// leave of the phase is the closing wave_sync()
 #define PROF_SUB(k)                                              \
     do {                                                         \
         const unsigned long long pq_ = __builtin_readcyclecounter(); \

@@ -1086,9 +1086,8 @@ void q_phase_kernel(const QArgs a_in) {
         // (A) subtree wrench of every DISTINCT site range: the site wrenches in (body id, site id) order, summed left to
         //     right from zero (RangeRec, stac_plan.hpp); written where the body transforms were
         const RangeRec *rrec = reinterpret_cast<const RangeRec *>(P + H.off_range);
-        auto range_sum = [&](const int r, float *CBx) {
+        auto range_sum_of = [&](const RangeRec rr, const int r, float *CBx) {  // (the sites [rr.lo, rr.hi) into the entry of range r)
             const float *swx = CBx + H.c_sw;
-            const RangeRec rr = rrec[r];
             V3 Fs = {0.f, 0.f, 0.f}, T0 = {0.f, 0.f, 0.f};
             int i = rr.lo;
             for (; i + 4 <= rr.hi; i += 4) {  // same left-to-right order; four wrenches in flight per LDS round trip
@@ -1115,6 +1114,7 @@ void q_phase_kernel(const QArgs a_in) {
             st_tpos(CBx + H.c_rw + kXf * r, Fs);
             st_tvec2(CBx + H.c_rw + kXf * r, T0);
         };
+        auto range_sum = [&](const int r, float *CBx) { range_sum_of(rrec[r], r, CBx); };
         // With 32 or 64 lanes on one evaluation (latency mode) the sums are split further: one task = one of the six
         // components {F, T} of one range -- the same left-to-right sums, but a lane's loop is one LDS read and one add per
         // site instead of four reads and six adds, and the six tasks of a range sit on neighbouring lanes (equal trip
@@ -1171,6 +1171,69 @@ void q_phase_kernel(const QArgs a_in) {
                 }
             }
             CBx[H.c_rw + kXf * r + co] = acc;
+        };
+        // The wrench-sum program of the lean 16-lane throughput kernels (WsumRec, stac_plan.hpp; the host: build_wsum_program).
+        constexpr bool kWsumProg = LEAN && SPEC == 0 && G == 16 && kWsum != 0;
+        const float *const wrec = P + a.off_wsum;
+        // a component task: range_task's loops over [lo, mid), the running sum stored for the checkpoint's range, then on over [mid, hi)
+        auto wsum_task = [&](const int t, float *CBx) {
+            const int q = t / 6, k = t - 6 * q;
+            const int4 rec = lds4i(wrec + 4 * q);  // lo, mid, hi, rid_mid | rid_hi << 16
+            const int co = k < 3 ? k : kXq + k - 3;
+            const float *src = CBx + H.c_sw + co;
+            float acc = 0.f;
+            auto segment = [&](int i, const int hi) {
+                for (; i + 4 <= hi; i += 4) {  // four in flight per LDS round trip
+                    const float v0 = src[kXf * i], v1 = src[kXf * (i + 1)], v2 = src[kXf * (i + 2)], v3 = src[kXf * (i + 3)];
+                    acc = acc + v0; acc = acc + v1; acc = acc + v2; acc = acc + v3;
+                }
+                if (i < hi) {  // the last one to three sites in one trip (as range_sum)
+                    const int last = hi - 1;
+                    const float v0 = src[kXf * i], v1 = src[kXf * min(i + 1, last)], v2 = src[kXf * min(i + 2, last)];
+                    acc = acc + v0;
+                    acc = i + 1 <= last ? acc + v1 : acc;
+                    acc = i + 2 <= last ? acc + v2 : acc;
+                }
+            };
+            if constexpr ((kWsum & 2) != 0) {
+                segment(rec.x, rec.y);
+                CBx[H.c_rw + kXf * (rec.w & 0xFFFF) + co] = acc;
+                segment(rec.y, rec.z);
+            } else {
+                segment(rec.x, rec.z);
+            }
+            CBx[H.c_rw + kXf * (int)((unsigned)rec.w >> 16) + co] = acc;
+        };
+        // the row sweeps: per row the lane's wrench (one LDS round trip), then `depth` steps of six chains that never leave the registers;
+        // after step s the lane holds the sum of the s + 1 sites that end with its own, and stores it to the step's store word: the
+        // entry of the range it is, or the dump entry
+        auto wsum_sweeps = [&](float *CBx) {
+            const int nrows = (a.wsum >> 16) & 0xFF, depth = (int)((unsigned)a.wsum >> 24);
+            const float *rows = wrec + 4 * ((a.wsum & 0xFF) + ((a.wsum >> 8) & 0xFF));
+            for (int row = 0; row < nrows; ++row) {
+                const int4 rl = lds4i(rows + 4 * (row * 16 + lg));
+                const float *src = CBx + H.c_sw + rl.x;
+                float w[6], acc[6];
+#pragma unroll
+                for (int c = 0; c < 6; ++c) w[c] = src[c < 3 ? c : kXq + c - 3];
+#pragma unroll
+                for (int c = 0; c < 6; ++c) acc[c] = 0.f + w[c];
+#pragma unroll
+                for (int s = 0; s < kWsumMaxDepth; ++s) {
+                    if (s >= depth) break;
+                    if (s > 0) {
+#pragma unroll
+                        for (int c = 0; c < 6; ++c) acc[c] = row_shr1(acc[c]) + w[c];
+                    }
+                    const int pair = s < 2 ? rl.y : rl.z;
+                    const int at = (s & 1) ? (int)((unsigned)pair >> 16) : (pair & 0xFFFF);
+                    float *dst = CBx + at;
+                    if (kWsumDump || at != H.c3_rw0) {
+#pragma unroll
+                        for (int c = 0; c < 6; ++c) dst[c < 3 ? c : kXq + c - 3] = acc[c];
+                    }
+                }
+            }
         };
         // (B) one joint: its range's wrench, then the joint formulas; crefx = the root position the moments refer to
         // (lean kernels: the joints this is called for -- all but the free root, which has its own path -- are hinges: the host has
@@ -1309,12 +1372,34 @@ void q_phase_kernel(const QArgs a_in) {
             // the range sums go where the body transforms were (the site pass, their last reader, is over; cref is in a
             // register), the gradient where the site wrenches were (dead once the range sums are done)
             if constexpr (G >= 32) { for (int t = lg; t < 6 * H.nrange; t += G) range_task(t, CB); }
+            else if constexpr (kWsumProg) {
+                // by the model's wrench-sum program: short ranges out of row sweeps, the longest ones one component per lane with shared
+                // prefixes, the others one range per lane
+                if constexpr ((kWsum & 1) != 0) wsum_sweeps(CB);
+                PROF_SUB(5);  // row sweeps
+                const int ns = a.wsum & 0xFF, nw = (a.wsum >> 8) & 0xFF;
+                for (int t = lg; t < 6 * ns; t += G) wsum_task(t, CB);
+                PROF_SUB(6);  // component tasks
+                for (int i = lg; i < nw; i += G) {
+                    const int4 rec = lds4i(wrec + 4 * (ns + i));
+                    range_sum_of(RangeRec{rec.x, rec.z}, (int)((unsigned)rec.w >> 16), CB);
+                }
+                PROF_SUB(7);  // whole ranges
+            }
             else if constexpr (LEAN && SPEC == 0 && G == 16) {
                 // the longest ranges one component per lane, the others one range per lane (PlanHeader::rsplit: the rodent's 23-site
                 // range of the root joint is 23 reads and additions on each of six lanes instead of 138 of each on one)
                 const int ns = H.rsplit;
+#ifdef STAC_PROFILE  // (the first round of component tasks under a sub-stamp of its own)
+                if (lg < 6 * ns) range_task(lg, CB);
+                PROF_SUB(5);
+                for (int t = lg + G; t < 6 * ns; t += G) range_task(t, CB);
+                PROF_SUB(6);
+#else
                 for (int t = lg; t < 6 * ns; t += G) range_task(t, CB);
+#endif
                 for (int r = ns + lg; r < H.nrange; r += G) range_sum(r, CB);
+                PROF_SUB(7);
             }
             else { for (int r = lg; r < H.nrange; r += G) range_sum(r, CB); }
             wave_sync();

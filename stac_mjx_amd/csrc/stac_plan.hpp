@@ -206,6 +206,36 @@ struct PlanHeader {
     int32_t rsplit;
 };
 
+// The wrench sums of the lean 16-lane throughput kernels, as a program the host writes per model (QArgs::off_wsum).  Every distinct
+// site range is produced exactly once, by one of three ways -- each the same left-to-right sum from zero:
+//   * a ROW SWEEP.  A row is up to 16 consecutive sorted sites, one per lane of the chain.  Lane k holds the wrench w_k of the row's
+//     site k and runs A_0[k] = 0 + w_k, A_s[k] = A_(s-1)[k-1] + w_k (one DPP addition per component; lane 0 takes +0 from outside the
+//     row): after step s it holds the sum of the s + 1 sites that end with its own.  `depth` steps give every range of up to `depth`
+//     sites inside a row without a read, an address or a lane-dependent trip count.  Per (row, lane) four words: {word of the lane's
+//     wrench entry from c_sw, store word of step 0 | of step 1 << 16, of step 2 | of step 3 << 16, the same as capture bytes}: a
+//     store word is the entry (in the chain's region) of the range whose sum the lane holds after that step, or -- the sum being
+//     nobody's -- of PlanHeader::c3_rw0, which a full trip neither reads nor keeps; capture byte s is that range's RangeRec index,
+//     kWsumNone for nobody's (the host's tests read them; the kernel does not).
+//   * a COMPONENT TASK: one of the six components of a range on a lane (as PlanHeader::rsplit).  A shorter range with the same first
+//     site is a CHECKPOINT of the task: the running sum is stored for it when the loop has passed its last site.
+//   * a WHOLE RANGE on one lane.
+// Table: WsumRec[tasks], WsumRec[whole ranges], then the four words of every (row, lane) [rows][16].  A task without a checkpoint has mid == hi
+// and rid_mid == rid_hi; a whole range likewise.
+struct WsumRec { int32_t lo, mid, hi, rids; };  // rids = rid_mid | rid_hi << 16
+constexpr int kWsumNone = 0xFF, kWsumMaxDepth = 4;
+// The parts, one bit each: 1 = row sweeps, 2 = shared prefixes (checkpoints); 0 = the code before the program (PlanHeader::rsplit).
+// Shipped: 2.  The sweeps are an experiment build: on the bench they cost what the whole-range round they replace cost, and more
+// (profiles/r10/NOTES.md: -1.6 % alone, and they take back what the prefixes gain).
+#ifndef STAC_WSUM
+#define STAC_WSUM 2
+#endif
+constexpr int kWsum = STAC_WSUM;
+// 1: a sum that is nobody's is stored to the dump entry (no lane test); 0: it is not stored
+#ifndef STAC_WSUM_DUMP
+#define STAC_WSUM_DUMP 1
+#endif
+constexpr bool kWsumDump = STAC_WSUM_DUMP != 0;
+
 // Full-model tables for the stand-alone FK / offset-phase kernels (device pointers).
 struct FullModel {
     int32_t nbody, njnt, nq, K;
@@ -280,6 +310,10 @@ struct QArgs {
     uint32_t *counters_out; // [C,F,4] or null
     float *q_carry_out;     // [C,nq] or null
     unsigned long long *prof;  // diagnostic builds (-DSTAC_PROFILE) only: [16] per-phase cycle sums (+ [8] sub-stamps of the loop head: PG kernel)
+    // Wrench-sum program of a lean 16-lane throughput launch (WsumRec, above; build_wsum_program, stac_abi.hip): where its table stands
+    // in the staged plan, and its counts: component tasks | whole ranges << 8 | rows << 16 | depth << 24.  (Last, so that no other
+    // argument moves.)
+    int32_t off_wsum, wsum;
 };
 
 // ---- optional LM solver (stac_lm.hip): per solve-kind tables in one global-memory blob of 32-bit words -----

@@ -13,8 +13,9 @@ from pathlib import Path
 
 CSRC = Path(__file__).resolve().parent / "csrc"
 LIB = CSRC / "libstac_hip.so"
-SOURCES = [CSRC / "stac_kernels.hip", CSRC / "stac_lm.hip", CSRC / "stac_abi.hip", CSRC / "stac_render.hip", CSRC / "stac_jpeg.hip", CSRC / "stac_post.hip", CSRC / "stac_prep.hip", CSRC / "stac_outlier.hip", CSRC / "stac_report.hip"]
-HEADERS = [CSRC / "stac_plan.hpp", CSRC / "stac_device.hpp", CSRC / "stac_shapes.hpp", CSRC / "stac_render.hpp", CSRC / "stac_jpeg.hpp", CSRC / "stac_post.hpp", CSRC / "stac_prep.hpp", CSRC / "stac_outlier.hpp", CSRC / "stac_report.hpp", CSRC.parents[1] / "include" / "stac_hip.h"]
+# every unit and every header of csrc: a new file cannot be missing from the build or from source_digest()
+SOURCES = sorted(CSRC.glob("*.hip"))
+HEADERS = sorted(CSRC.glob("*.hpp")) + [CSRC.parents[1] / "include" / "stac_hip.h"]
 # -amdgpu-opt-vgpr-liverange=false: SIOptimizeVGPRLiveRange is the pass behind round 3's stale-state defect (a latency-kernel
 # shape whose results depended on what the previous launch left in registers / scratch): with it off that shape is correct under
 # every poison pattern, with it on it is wrong on 36 of 36 models (profiles/r04/stale_spill_repro.txt, reproducer:

@@ -977,7 +977,7 @@ __device__ __forceinline__ void fk_chain(const HT &H, const float *P, float *CBc
 }
 
 // ------------------------------------------------------------------------------------------------
-// split kinematics of the lean kernels (PlanHeader::fk3; tables: stac_abi.hip, build_fk3_program)
+// split kinematics of the lean kernels (PlanHeader::fk3; tables: stac_planner.hip, build_fk3_program)
 // ------------------------------------------------------------------------------------------------
 // The step program above runs, per body and joint, pos += rotate(bpos, q); anchor = rotate(jpos, q) + pos; q = q * ql;
 // pos = anchor - rotate(jpos, q) as ONE serial chain of ~60-instruction steps.  With a free root and only hinges below it the
@@ -1022,7 +1022,7 @@ __device__ __forceinline__ float fk3_qmul(const float qc, const float ql, const 
     return r;
 }
 // P1.  Blocks of two steps, every block the same instructions (as P3 below): a position keeps its running quaternion or starts the
-// block from a restart value.  T1: records of 24 words (layout: build_fk3_program, stac_abi.hip); block r works from record r + 1 --
+// block from a restart value.  T1: records of 24 words (layout: build_fk3_program, stac_planner.hip); block r works from record r + 1 --
 // its out words and restart flag, the ql and restart words of block r + 1 --, so a block's joint-local quaternions and its restart
 // value are requested while the block before it runs (the host schedules a restart at least three steps behind the step that wrote
 // the value) and its record a block before that.  Two blocks per trip, the two sets of registers in turn: nothing is copied.

@@ -14,6 +14,7 @@
 //                        first interval and RSTn / EOI behind each; no store at or beyond the output's capacity
 #include <hip/hip_runtime.h>
 
+#include "stac_host.hpp"
 #include "stac_jpeg.hpp"
 
 namespace stac {
@@ -416,7 +417,7 @@ __global__ __launch_bounds__(kPackThreads) void jpeg_pack_kernel(const JpegCall 
 
 }  // namespace
 
-hipError_t launch_jpeg_encode(const JpegCall &C, const JpegHeader &Hd, hipStream_t s) {
+static hipError_t launch_jpeg_encode(const JpegCall &C, const JpegHeader &Hd, hipStream_t s) {
     if (C.T <= 0) return hipSuccess;
     JpegQuantArg Q;
     for (int t = 0; t < 2; ++t)
@@ -433,3 +434,54 @@ hipError_t launch_jpeg_encode(const JpegCall &C, const JpegHeader &Hd, hipStream
 }
 
 }  // namespace stac
+
+// ---- C ABI entry points (include/stac_hip.h) ---------------------------------------------------------------------------------------
+static bool jpeg_shape_ok(int64_t N, int32_t width, int32_t height, int32_t restart_mcus, int min_restart) {
+    return N >= 0 && width >= 1 && height >= 1 && width <= kJpegMaxDim && height <= kJpegMaxDim && restart_mcus >= min_restart &&
+           restart_mcus <= 65535;
+}
+
+extern "C" int64_t stac_jpeg_header(int32_t width, int32_t height, int32_t quality, int32_t restart_mcus, uint8_t *buf,
+                                    int64_t capacity) {
+    if (!jpeg_shape_ok(0, width, height, restart_mcus, 0) || quality < 1 || quality > 100 || capacity < 0)
+        return fail(STAC_ERR_INVALID, "stac_jpeg_header: width / height 1..65535, quality 1..100, restart_mcus 0..65535");
+    JpegHeader h;
+    jpeg_make_header(width, height, quality, restart_mcus, &h);
+    if (buf) {
+        if (capacity < h.len) return fail(STAC_ERR_INVALID, "stac_jpeg_header: buffer smaller than the header");
+        memcpy(buf, h.bytes, (size_t)h.len);
+    }
+    return h.len;
+}
+
+extern "C" int64_t stac_jpeg_workspace_bytes(int64_t N, int32_t width, int32_t height, int32_t restart_mcus) {
+    if (!jpeg_shape_ok(N, width, height, restart_mcus, 1))
+        return fail(STAC_ERR_INVALID, "stac_jpeg_workspace_bytes: N >= 0, width / height 1..65535, restart_mcus 1..65535");
+    JpegCall c{};
+    c.N = N; c.W = width; c.H = height; c.R = restart_mcus;
+    const int64_t per_frame = (int64_t)((width + 15) / 16) * ((height + 15) / 16) * (kJpegMcuBitsMax / 8 + 64);
+    if (N > 0 && per_frame > (INT64_MAX >> 4) / N) return fail(STAC_ERR_CAPACITY, "stac_jpeg_workspace_bytes: N x width x height too large");
+    return jpeg_layout(&c, nullptr);
+}
+
+extern "C" int32_t stac_jpeg_encode(int64_t N, int32_t width, int32_t height, int32_t quality, int32_t restart_mcus,
+                                    const uint8_t *rgb, uint8_t *out, int64_t out_capacity, int64_t *frame_offset,
+                                    void *workspace, int64_t workspace_bytes, void *stream) {
+    if (!jpeg_shape_ok(N, width, height, restart_mcus, 1) || quality < 1 || quality > 100)
+        return fail(STAC_ERR_INVALID, "stac_jpeg_encode: N >= 0, width / height 1..65535, quality 1..100, restart_mcus 1..65535");
+    if (N == 0) return STAC_OK;
+    if (!rgb || !frame_offset || out_capacity < 0 || (out_capacity > 0 && !out) || !workspace || ((uintptr_t)workspace & 7))
+        return fail(STAC_ERR_INVALID, "stac_jpeg_encode: null rgb / out / frame_offset / workspace, or workspace not 8-byte aligned");
+    const int64_t need = stac_jpeg_workspace_bytes(N, width, height, restart_mcus);
+    if (need < 0) return (int32_t)need;
+    if (workspace_bytes < need)
+        return fail(STAC_ERR_INVALID, "stac_jpeg_encode: workspace of " + std::to_string(workspace_bytes) + " bytes, " +
+                                          std::to_string(need) + " needed (stac_jpeg_workspace_bytes)");
+    JpegCall c{};
+    c.N = N; c.W = width; c.H = height; c.R = restart_mcus;
+    jpeg_layout(&c, (uint8_t *)workspace);
+    c.rgb = rgb; c.out = out; c.cap = out_capacity; c.frame_offset = frame_offset;
+    JpegHeader h;
+    jpeg_make_header(width, height, quality, restart_mcus, &h);
+    return launch_result("stac_jpeg_encode", launch_jpeg_encode(c, h, (hipStream_t)stream));
+}

@@ -1,4 +1,4 @@
-// Shared tables and layout of the JPEG encoder (stac_jpeg.hip) and its host entry points (stac_abi.hip).
+// Shared tables and layout of the JPEG encoder (stac_jpeg.hip) and its host entry points (below the kernels).
 //
 // The stream is baseline sequential JPEG as libjpeg writes it (DESIGN.md "JPEG on the GPU"): 8 bit, YCbCr 4:2:0, one
 // interleaved scan, the Annex K quantisation and Huffman tables, restart interval counted in MCUs of 16 x 16 pixels.

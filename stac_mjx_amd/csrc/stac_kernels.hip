@@ -32,6 +32,7 @@
 #include "stac_plan.hpp"
 #include "stac_device.hpp"
 #include "stac_shapes.hpp"
+#include "stac_launch.hpp"
 
 #ifndef STAC_RT
 #define STAC_RT 12  // sites per trip of a latency kernel's range sum (measured 6 / 8 / 12 / 16 / 24: 19.24 / 19.20 / 19.33 / 18.72 / 17.62 k frames/s on 40 x 250)
@@ -1966,7 +1967,7 @@ void q_phase_kernel(const QArgs a_in) {
 // registers: a child that follows its parent directly -- the chains that make up most of every tree (the rodent's tail: 26
 // bodies) -- reads nothing.  A body with a child further down the list parks its transform in one of a few LDS slots (7 words per
 // lane, lane-private columns: no bank conflicts, no synchronisation; the host allots the slots like registers, FkTables in
-// stac_abi.hip: rodent 3, mouse 4: 1.8 KB per slot and wavefront).  The model tables are packed records (16 words per body, 12
+// stac_planner.hip: rodent 3, mouse 4: 1.8 KB per slot and wavefront).  The model tables are packed records (16 words per body, 12
 // per joint) read through the SCALAR cache: every lane of a wavefront is at the same body, so body offsets, joint axes and site
 // offsets arrive in SGPRs and cost no vector memory traffic at all.  The coordinate of the joint two visits AHEAD is requested
 // before the current body's results are stored (VMEM counts loads and stores in one in-order counter on gfx9: a load issued
@@ -2214,7 +2215,7 @@ __global__ void key_scatter_kernel(const uint32_t *keybits, uint32_t *offs, int 
 }
 
 // ------------------------------------------------------------------------------------------------
-// launchers (called from stac_abi.hip)
+// launchers (declared in stac_launch.hpp; called from stac_q.hip and stac_model.hip)
 // ------------------------------------------------------------------------------------------------
 hipError_t launch_chain_order(const float *kp, int C, int F, int K, const float *rest_sites, const uint8_t *kpw, int root_kp_idx,
                               float rx, float ry, float rz, uint32_t *hist, uint32_t *keybits, int32_t *perm, int32_t *place,
@@ -2235,7 +2236,7 @@ hipError_t launch_ctl_init(int32_t *ctl, int v0, int v1, int v2, int v3, int v4,
     return hipGetLastError();
 }
 
-// the instantiation of the most recent q_phase launch of this thread (tests: which kernel did the host choose?  stac_abi.hip,
+// the instantiation of the most recent q_phase launch of this thread (tests: which kernel did the host choose?  stac_q.hip,
 // stac_debug_last_q_kernel)
 thread_local int g_last_q_shape[4] = {0, 0, 0, 0};
 
@@ -2258,7 +2259,7 @@ static hipError_t launch_q(const QArgs &a, int wpb, size_t lds_bytes, hipStream_
     return hipGetLastError();
 }
 
-// Launches exactly the instantiation `i` (stac_shapes.hpp: the host plans it, stac_abi.hip, plan_q); anything else is refused.
+// Launches exactly the instantiation `i` (stac_shapes.hpp: the host plans it, stac_q.hip, plan_q); anything else is refused.
 // wpb = wavefronts per workgroup (they share the plan copy).
 hipError_t launch_q_phase(const QArgs &a, const QInst &i, int wpb, size_t lds_bytes, hipStream_t s) {
 #define STAC_INST(GG, RR, WW, SP) \
@@ -2280,7 +2281,7 @@ hipError_t launch_q_phase(const QArgs &a, const QInst &i, int wpb, size_t lds_by
 }
 
 // LDS of an fk_kernel launch: the parking slots (7 words per lane each) and a staging row per lane; a workgroup may take the 160 KiB
-// of a CU, which is 83 slots.  The host refuses a tree that parks more at once by name (stac_abi.hip, fk_capacity) before it gets here.
+// of a CU, which is 83 slots.  The host refuses a tree that parks more at once by name (stac_model.hip, fk_capacity) before it gets here.
 static size_t fk_lds_bytes(int nslots) { return ((size_t)std::max(nslots, 1) * 7 + kFkStride) * 64 * sizeof(float); }
 constexpr size_t kFkLdsCap = 160 * 1024;
 int fk_max_slots() { return (int)((kFkLdsCap / (64 * sizeof(float)) - kFkStride) / 7); }

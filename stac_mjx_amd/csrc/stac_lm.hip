@@ -18,6 +18,7 @@
 #include "stac_device.hpp"
 #include "stac_plan.hpp"
 #include "stac_shapes.hpp"
+#include "stac_launch.hpp"
 
 namespace stac {
 

@@ -1,4 +1,4 @@
-// Rejecting keypoint outliers along time (rule and shared function: stac_outlier.hpp; entry point: stac_abi.hip).
+// Rejecting keypoint outliers along time (rule and shared function: stac_outlier.hpp; entry point: below the kernel).
 //
 // One launch, no workspace, no workgroup ever waits for another.  A workgroup works on one (tile of 64 frames, chunk of up to 32
 // keypoints) at a time and strides over the work with at most kPrepMaxBlocks workgroups:
@@ -15,6 +15,9 @@
 // whose image holds NaN, reads its raw coordinates again from global memory to pass them on bit for bit.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
+
+#include "stac_host.hpp"
 #include "stac_outlier.hpp"
 
 namespace stac {
@@ -87,7 +90,7 @@ __global__ __launch_bounds__(kOutlierThreads) void outlier_reject_kernel(const f
 
 }  // namespace
 
-hipError_t launch_outlier_reject(const float *kp, int64_t T, int32_t K, int32_t h, double thr, double min_dev, float *out, uint8_t *flag,
+static hipError_t launch_outlier_reject(const float *kp, int64_t T, int32_t K, int32_t h, double thr, double min_dev, float *out, uint8_t *flag,
                                  hipStream_t s) {
     const int64_t tiles = prep_tiles(T, kPrepTileFrames);
     const int32_t chunks = (K + kOutlierChunk - 1) / kOutlierChunk;
@@ -98,3 +101,24 @@ hipError_t launch_outlier_reject(const float *kp, int64_t T, int32_t K, int32_t 
 }
 
 }  // namespace stac
+
+// ---- C ABI entry point (include/stac_hip.h): every argument is checked before the device is touched -------------------------------
+extern "C" int32_t stac_prep_reject(const float *kp, int64_t n_frames, int32_t n_kp, int32_t half_window, double thr, double min_dev,
+                                    float *out, uint8_t *flag, void *stream) {
+    if (n_frames < 1 || n_kp < 1 || n_frames > (((int64_t)1 << 59) / n_kp))
+        return fail(STAC_ERR_INVALID, "stac_prep_reject: n_frames >= 1, n_kp >= 1 (and array sizes within int64)");
+    if (half_window < 1 || half_window > kOutlierMaxHalf)
+        return fail(STAC_ERR_INVALID, "stac_prep_reject: half_window " + std::to_string(half_window) + " is outside 1 .. " +
+                                          std::to_string(kOutlierMaxHalf));
+    if (!std::isfinite(thr) || thr < 0.0 || !std::isfinite(min_dev) || min_dev < 0.0)
+        return fail(STAC_ERR_INVALID, "stac_prep_reject: thr and min_dev must be finite and >= 0");
+    if (!kp || !out || !flag) return fail(STAC_ERR_INVALID, "stac_prep_reject: null kp / out / flag");
+    if ((uintptr_t)kp % 4 != 0 || (uintptr_t)out % 4 != 0) return fail(STAC_ERR_INVALID, "stac_prep_reject: kp / out must be 4-byte aligned");
+    const int64_t kp_bytes = n_frames * n_kp * 12, flag_bytes = n_frames * n_kp;
+    const HostBuf buf[3] = {{"kp", (uintptr_t)kp, kp_bytes}, {"out", (uintptr_t)out, kp_bytes}, {"flag", (uintptr_t)flag, flag_bytes}};
+    const HostBuf *a, *b;
+    if (find_overlap(buf, 3, &a, &b))
+        return fail(STAC_ERR_INVALID, std::string("stac_prep_reject: ") + a->name + " and " + b->name +
+                                          " overlap: neighbours read raw values, so in place is not possible");
+    return launch_result("stac_prep_reject", launch_outlier_reject(kp, n_frames, n_kp, half_window, thr, min_dev, out, flag, (hipStream_t)stream));
+}

@@ -140,7 +140,7 @@ struct PlanHeader {
     int32_t total_words;   // end of what a launch stages in LDS (the per-launch copy may stop at core_words, or inside the root program)
     int32_t plan_skip;     // ... and its beginning (per launch): a kernel that runs the FK program does not need the level tables and
                            // body records in front of the joint records, so the LDS copy starts at off_joint; the launch's header copy then carries
-                           // every off_* of a staged area minus plan_skip (rebase_plan_offsets, stac_abi.hip)
+                           // every off_* of a staged area minus plan_skip (rebase_plan_offsets, stac_planner.hip)
     int32_t core_words;    // blob without the FK program (the program is last)
     // per-chain LDS layout (float offsets inside one chain's region) ------------------------------
     int32_t c_bx;      // [(nst+1)*kXf] transform entries of the stored bodies; entry 0 = world
@@ -187,7 +187,7 @@ struct PlanHeader {
     int32_t off3_site;     // [K] per site: word of its body's position | word of its body's quaternion << 16 (chain region), full program;
                            // then [naj] per joint: word of its anchor | word of its pre-joint quaternion << 16
     int32_t off3_prog;     // full program: T1 [16 (cap1 + 2)] = cap1 / 2 + 3 records of 24 words, a record per block of two steps (layout:
-                           // build_fk3_program, stac_abi.hip), T2 [cap2][4] {v.x, v.y, v.z, q word | out word << 16}, T3 [cap3 * 4]: per block of
+                           // build_fk3_program, stac_planner.hip), T2 [cap2][4] {v.x, v.y, v.z, q word | out word << 16}, T3 [cap3 * 4]: per block of
                            // four steps and position the restart entry (word of the value, or bit 31 | a valid word), then the site and joint words
     int32_t off3_root;     // same layout: the pruned program of the root passes (filled per call)
     int32_t fk3_n;         // full program: steps of P1 (even) | steps of P3 (a multiple of 4) << 8 | tasks of P2 (padded to a multiple of 16 with no-ops) << 16
@@ -245,7 +245,7 @@ struct FullModel {
     const float *jnt_pos, *jnt_axis, *qpos0;
     const int32_t *site_bodyid;
     const float *site_pos;  // points INTO the plan blob (single source of truth for the offsets)
-    // packed tables of fk_kernel (stac_abi.hip, build_fk_tables): per body 16 words {parent slot or -1 = the body before, slot to
+    // packed tables of fk_kernel (stac_planner.hip, build_fk_tables): per body 16 words {parent slot or -1 = the body before, slot to
     // park in or -1, jntadr, jntnum | pos xyz, first site | quat wxyz | end of sites, (body 0 only: qposadr of the first joint
     // visited, of the second), 0}; per joint 12 words {type, qposadr, qpos0[qposadr], qposadr of the joint visited two steps on |
     // pos xyz, 0 | axis xyz, 0}; the site ids sorted by body
@@ -282,7 +282,7 @@ struct QArgs {
     // root_fast coordinates move: the joint-local quaternions of all other joints, computed once, stay valid (the root
     // program parks their anchor / pre-joint entries in the sink), the gradient is the root joint's alone and its subtree
     // wrench sums the weighted (trunk) sites only -- the others contribute exact zeros, and a running sum that starts at
-    // +0 is never -0, so leaving them out changes no bit.  0 = off (conditions: stac_abi.hip, stac_q_phase).  A chain
+    // +0 is never -0, so leaving them out changes no bit.  0 = off (conditions: stac_q.hip, stac_q_phase).  A chain
     // that finishes its root solves waits (ST_WAIT) until the other chains of its wavefront have, so that the root trips
     // of a wavefront are ALL fast ones and its chains start their pose solves in the same trip.
     int32_t root_fast;      // number of leading coordinates the root passes optimise (= root_dims), or 0
@@ -310,7 +310,7 @@ struct QArgs {
     uint32_t *counters_out; // [C,F,4] or null
     float *q_carry_out;     // [C,nq] or null
     unsigned long long *prof;  // diagnostic builds (-DSTAC_PROFILE) only: [16] per-phase cycle sums (+ [8] sub-stamps of the loop head: PG kernel)
-    // Wrench-sum program of a lean 16-lane throughput launch (WsumRec, above; build_wsum_program, stac_abi.hip): where its table stands
+    // Wrench-sum program of a lean 16-lane throughput launch (WsumRec, above; build_wsum_program, stac_planner.hip): where its table stands
     // in the staged plan, and its counts: component tasks | whole ranges << 8 | rows << 16 | depth << 24.  (Last, so that no other
     // argument moves.)
     int32_t off_wsum, wsum;

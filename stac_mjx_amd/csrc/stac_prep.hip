@@ -1,4 +1,4 @@
-// Filling missing keypoints along time (rule and shared functions: stac_prep.hpp; entry points: stac_abi.hip).
+// Filling missing keypoints along time (rule and shared functions: stac_prep.hpp; entry points: below the kernels).
 //
 // A staged scan over tiles of 64 frames, three launches on the caller's stream, no workgroup ever waits for another:
 //   1. prep_summary_kernel: per tile and keypoint the first and last valid frame of the tile          -> first, last [K][tiles]
@@ -13,6 +13,7 @@
 // of the tile in one ballot.  Rows are 4-byte aligned only, hence dword accesses; offsets are 64-bit element offsets.
 #include <hip/hip_runtime.h>
 
+#include "stac_host.hpp"
 #include "stac_prep.hpp"
 
 namespace stac {
@@ -190,7 +191,7 @@ __global__ __launch_bounds__(kPrepThreads) void prep_fill_kernel(const float *__
 
 }  // namespace
 
-hipError_t launch_prep_fill(const float *kp, int64_t T, int32_t K, int32_t mode, float *out, int32_t *gap, void *workspace,
+static hipError_t launch_prep_fill(const float *kp, int64_t T, int32_t K, int32_t mode, float *out, int32_t *gap, void *workspace,
                             hipStream_t s) {
     const int64_t tiles = prep_tiles(T, kPrepTileFrames);
     const int32_t chunks = (K + kPrepChunk - 1) / kPrepChunk;
@@ -209,3 +210,33 @@ hipError_t launch_prep_fill(const float *kp, int64_t T, int32_t K, int32_t mode,
 }
 
 }  // namespace stac
+
+// ---- C ABI entry points (include/stac_hip.h): every argument is checked before the device is touched ------------------------------
+extern "C" int64_t stac_prep_fill_workspace(int64_t n_frames, int32_t n_kp) {
+    const int64_t b = prep_workspace_bytes(n_frames, n_kp);
+    if (b < 0) return fail(STAC_ERR_INVALID, "stac_prep_fill_workspace: n_frames >= 1, n_kp >= 1 (and a workspace size within int64)");
+    return b;
+}
+
+extern "C" int32_t stac_prep_fill(const float *kp, int64_t n_frames, int32_t n_kp, int32_t mode, float *out, int32_t *gap,
+                                  void *workspace, int64_t workspace_bytes, void *stream) {
+    const int64_t need = prep_workspace_bytes(n_frames, n_kp);
+    if (need < 0 || n_frames > (((int64_t)1 << 59) / n_kp))
+        return fail(STAC_ERR_INVALID, "stac_prep_fill: n_frames >= 1, n_kp >= 1 (and array sizes within int64)");
+    if (mode != STAC_PREP_LINEAR && mode != STAC_PREP_HOLD)
+        return fail(STAC_ERR_INVALID, "stac_prep_fill: mode " + std::to_string(mode) + " is neither STAC_PREP_LINEAR nor STAC_PREP_HOLD");
+    if (!kp || !out || !gap || !workspace) return fail(STAC_ERR_INVALID, "stac_prep_fill: null kp / out / gap / workspace");
+    if (workspace_bytes < need)
+        return fail(STAC_ERR_INVALID, "stac_prep_fill: workspace_bytes = " + std::to_string(workspace_bytes) + ", " +
+                                          std::to_string(need) + " are needed (stac_prep_fill_workspace)");
+    if ((uintptr_t)workspace % 8 != 0 || (uintptr_t)kp % 4 != 0 || (uintptr_t)out % 4 != 0 || (uintptr_t)gap % 4 != 0)
+        return fail(STAC_ERR_INVALID, "stac_prep_fill: kp / out / gap must be 4-byte aligned, workspace 8-byte aligned");
+    const int64_t kp_bytes = n_frames * n_kp * 12, gap_bytes = n_frames * n_kp * 4;
+    const HostBuf buf[4] = {{"kp", (uintptr_t)kp, kp_bytes}, {"out", (uintptr_t)out, kp_bytes}, {"gap", (uintptr_t)gap, gap_bytes},
+                            {"workspace", (uintptr_t)workspace, need}};
+    const HostBuf *a, *b;
+    if (find_overlap(buf, 4, &a, &b))
+        return fail(STAC_ERR_INVALID, std::string("stac_prep_fill: ") + a->name + " and " + b->name +
+                                          " overlap: source, outputs and workspace are distinct buffers");
+    return launch_result("stac_prep_fill", launch_prep_fill(kp, n_frames, n_kp, mode, out, gap, workspace, (hipStream_t)stream));
+}

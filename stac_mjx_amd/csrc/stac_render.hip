@@ -16,7 +16,7 @@
 
 #include <math.h>
 
-#include "../../include/stac_hip.h"
+#include "stac_host.hpp"
 #include "stac_render.hpp"
 
 namespace stac {
@@ -606,7 +606,7 @@ __global__ __launch_bounds__(kRenderTile *kRenderTile) void render_kernel(const 
 
 }  // namespace
 
-hipError_t launch_render(const RenderScene *S, const RenderCall &C, bool meshes, hipStream_t s) {
+static hipError_t launch_render(const RenderScene *S, const RenderCall &C, bool meshes, hipStream_t s) {
     if (C.N <= 0) return hipSuccess;
     const dim3 grid((C.W + kRenderTile - 1) / kRenderTile, (C.H + kRenderTile - 1) / kRenderTile, C.N < 65535 ? C.N : 65535);
     if (meshes) hipLaunchKernelGGL(render_kernel<true>, grid, dim3(kRenderTile * kRenderTile), 0, s, S, C);
@@ -615,3 +615,195 @@ hipError_t launch_render(const RenderScene *S, const RenderCall &C, bool meshes,
 }
 
 }  // namespace stac
+
+// ---- C ABI entry points (include/stac_hip.h): the scene object and stac_render -----------------------------------------------------
+struct stac_render_scene {
+    int device = 0;
+    RenderScene S{};               // what d_scene holds (device pointers into d_int / d_float)
+    RenderScene *d_scene = nullptr;
+    int32_t *d_int = nullptr;
+    float *d_float = nullptr;
+    float *d_nodes = nullptr;      // meshes: kRenderNodeWords words per node (see stac_render.hpp)
+    float *d_tris = nullptr;       // [NT,3,3]
+    bool has_mesh = false;         // a type-7 primitive: render with the mesh kernel
+};
+
+// Checks stac_render_meshes against the tables (see include/stac_hip.h).  Returns STAC_OK, or the code of the fail() it made.
+static int check_render_meshes(const stac_render_tables *t, const stac_render_meshes *ms, bool *has_mesh) {
+    const std::string who = "stac_render_scene_create_with_meshes: ";
+    *has_mesh = false;
+    if (ms->nmesh < 0 || (ms->nmesh && (!ms->node_offset || !ms->tri_offset || !ms->node_box || !ms->node_link || !ms->tri_vertex)))
+        return fail(STAC_ERR_INVALID, who + "bad argument");
+    if (ms->nmesh && (ms->node_offset[0] != 0 || ms->tri_offset[0] != 0))
+        return fail(STAC_ERR_INVALID, who + "node_offset[0] and tri_offset[0] must be 0");
+    for (int k = 0; k < ms->nmesh; ++k) {
+        const long nn = (long)ms->node_offset[k + 1] - ms->node_offset[k], nt = (long)ms->tri_offset[k + 1] - ms->tri_offset[k];
+        if (nn < 1 || nt < 0) return fail(STAC_ERR_INVALID, who + "mesh " + std::to_string(k) + " has no node, or offsets that decrease");
+        if (nt > STAC_RENDER_MAX_MESH_TRIS)
+            return fail(STAC_ERR_CAPACITY, who + "mesh " + std::to_string(k) + " has " + std::to_string(nt) +
+                                               " triangles, more than STAC_RENDER_MAX_MESH_TRIS = " + std::to_string(STAC_RENDER_MAX_MESH_TRIS));
+        const int32_t *link = ms->node_link + 3 * (size_t)ms->node_offset[k];
+        for (long n = 0; n < nn; ++n) {
+            const long skip = link[3 * n], first = link[3 * n + 1], count = link[3 * n + 2];
+            if (skip <= n || skip > nn || (count > 0 && skip != n + 1))
+                return fail(STAC_ERR_INVALID, who + "mesh " + std::to_string(k) + " node " + std::to_string(n) + ": skip link " +
+                                                  std::to_string(skip) + " does not point forward inside the mesh's " + std::to_string(nn) +
+                                                  " nodes (a leaf's is the next node)");
+            if (count < 0 || (count > 0 && (first < 0 || first + count > nt)))
+                return fail(STAC_ERR_INVALID, who + "mesh " + std::to_string(k) + " node " + std::to_string(n) + ": leaf range " +
+                                                  std::to_string(first) + " + " + std::to_string(count) + " outside the mesh's " +
+                                                  std::to_string(nt) + " triangles");
+        }
+    }
+    for (int i = 0; i < t->nprim; ++i) {
+        if (t->prim_type[i] != 7) continue;
+        *has_mesh = true;
+        if (!ms->prim_mesh || ms->prim_mesh[i] < 0 || ms->prim_mesh[i] >= ms->nmesh)
+            return fail(STAC_ERR_INVALID, who + "primitive " + std::to_string(i) + " is a mesh (type 7) without a mesh, or with a mesh index out of range");
+    }
+    return STAC_OK;
+}
+
+extern "C" stac_render_scene *stac_render_scene_create(const stac_model *m, const stac_render_tables *t) {
+    return stac_render_scene_create_with_meshes(m, t, nullptr);
+}
+
+extern "C" stac_render_scene *stac_render_scene_create_with_meshes(const stac_model *m, const stac_render_tables *t,
+                                                                   const stac_render_meshes *ms) {
+    if (!m || !t || t->nprim < 0 || t->nkp < 0 || t->nlight < 0 || (t->nprim && (!t->prim_type || !t->prim_body || !t->prim_flags
+        || !t->prim_size || !t->prim_pos || !t->prim_quat || !t->prim_rgba || !t->prim_rgb2 || !t->prim_texrepeat))
+        || (t->nkp && !t->kp_rgba) || (t->nlight && (!t->light_dir || !t->light_diffuse))) {
+        fail(STAC_ERR_INVALID, "stac_render_scene_create: bad argument");
+        return nullptr;
+    }
+    const long total = (long)t->nprim + 3L * t->nkp;
+    if (total > STAC_RENDER_MAX_PRIMS) {
+        fail(STAC_ERR_CAPACITY, "stac_render_scene_create: " + std::to_string(total) + " primitives (P + 3K) exceed STAC_RENDER_MAX_PRIMS = " +
+                                    std::to_string(STAC_RENDER_MAX_PRIMS));
+        return nullptr;
+    }
+    const int P = t->nprim, K = t->nkp, NL = t->nlight;
+    for (int i = 0; i < P; ++i) {
+        const int ty = t->prim_type[i];
+        if (t->prim_body[i] < 0 || t->prim_body[i] >= m->h.nbody || !(ty == 0 || (ty >= 2 && ty <= 6) || (ty == 7 && ms))) {
+            fail(STAC_ERR_INVALID, "stac_render_scene_create: primitive " + std::to_string(i) + " has a bad type or body");
+            return nullptr;
+        }
+    }
+    bool has_mesh = false;
+    if (ms && check_render_meshes(t, ms, &has_mesh) != STAC_OK) return nullptr;
+    // with meshes the int block grows by mesh[P] node_offset[M+1] tri_offset[M+1]; nodes and triangles get blocks of their own
+    const int M = has_mesh ? ms->nmesh : 0;
+    std::vector<float> hnodes;
+    std::vector<int32_t> hnoff, htoff;
+    if (has_mesh) {
+        // developer switch: every mesh as one leaf over all its triangles, to show what the hierarchy saves
+        const char *env = getenv("STAC_RENDER_MESH_SINGLE_LEAF");
+        const bool single = env && env[0] && env[0] != '0';
+        hnoff.push_back(0);
+        for (int k = 0; k < M; ++k) {
+            const size_t n0 = (size_t)ms->node_offset[k], nn = single ? 1 : (size_t)(ms->node_offset[k + 1] - ms->node_offset[k]);
+            for (size_t n = 0; n < nn; ++n) {
+                const float *b = ms->node_box + 6 * (n0 + n);
+                const int32_t *l = ms->node_link + 3 * (n0 + n);
+                const bool leaf = single || l[2] > 0;
+                // device node: lo[3], hi[3], then (first, count) of a leaf or (skip, 0) of an inner node, as bit patterns
+                const int32_t nt = ms->tri_offset[k + 1] - ms->tri_offset[k];
+                const int32_t w6 = single ? (nt > 0 ? 0 : 1) : (leaf ? l[1] : l[0]);  // (an empty mesh: an inner node that ends the walk)
+                const int32_t w7 = single ? nt : (leaf ? l[2] : 0);
+                float f6, f7;
+                memcpy(&f6, &w6, 4);
+                memcpy(&f7, &w7, 4);
+                hnodes.insert(hnodes.end(), b, b + 6);
+                hnodes.push_back(f6);
+                hnodes.push_back(f7);
+            }
+            hnoff.push_back((int32_t)(hnodes.size() / stac::kRenderNodeWords));
+        }
+        htoff.assign(ms->tri_offset, ms->tri_offset + M + 1);
+    }
+    // int block: type[P] body[P] flags[P]; float block: size[3P] pos[3P] quat[4P] rgba[4P] rgb2[3P] tex[2P] kp_rgba[4K]
+    // light_dir[3NL] light_diff[3NL]
+    std::vector<int32_t> hi;
+    hi.insert(hi.end(), t->prim_type, t->prim_type + P);
+    hi.insert(hi.end(), t->prim_body, t->prim_body + P);
+    hi.insert(hi.end(), t->prim_flags, t->prim_flags + P);
+    if (has_mesh) {
+        for (int i = 0; i < P; ++i) hi.push_back(t->prim_type[i] == 7 ? ms->prim_mesh[i] : -1);
+        hi.insert(hi.end(), hnoff.begin(), hnoff.end());
+        hi.insert(hi.end(), htoff.begin(), htoff.end());
+    }
+    std::vector<float> hf;
+    size_t off[8];
+    auto put = [&](int k, const float *p, size_t n) { off[k] = hf.size(); if (n) hf.insert(hf.end(), p, p + n); };
+    put(0, t->prim_size, 3 * (size_t)P); put(1, t->prim_pos, 3 * (size_t)P); put(2, t->prim_quat, 4 * (size_t)P);
+    put(3, t->prim_rgba, 4 * (size_t)P); put(4, t->prim_rgb2, 3 * (size_t)P); put(5, t->prim_texrepeat, 2 * (size_t)P);
+    put(6, t->kp_rgba, 4 * (size_t)K);
+    const size_t off_ld = hf.size();
+    if (NL) hf.insert(hf.end(), t->light_dir, t->light_dir + 3 * (size_t)NL);
+    const size_t off_lc = hf.size();
+    if (NL) hf.insert(hf.end(), t->light_diffuse, t->light_diffuse + 3 * (size_t)NL);
+    DeviceGuard dg(m->device);
+    auto *sc = new stac_render_scene;
+    sc->device = m->device;
+    auto bail = [&](hipError_t e) {
+        fail(STAC_ERR_HIP, std::string("stac_render_scene_create: ") + hipGetErrorString(e));
+        stac_render_scene_destroy(sc);  // (frees what has been allocated so far)
+        return nullptr;
+    };
+    hipError_t e = upload(&sc->d_int, hi.data(), hi.size());
+    if (e != hipSuccess) return bail(e);
+    e = upload(&sc->d_float, hf.data(), hf.size());
+    if (e != hipSuccess) return bail(e);
+    RenderScene &S = sc->S;
+    sc->has_mesh = has_mesh;
+    if (has_mesh) {
+        e = upload(&sc->d_nodes, hnodes.data(), hnodes.size());
+        if (e != hipSuccess) return bail(e);
+        const size_t nt = 9 * (size_t)ms->tri_offset[M];
+        const float none[9] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+        e = upload(&sc->d_tris, nt ? ms->tri_vertex : none, nt ? nt : 9);
+        if (e != hipSuccess) return bail(e);
+        S.nmesh = M;
+        S.prim_mesh = sc->d_int + 3 * P; S.mesh_node_off = sc->d_int + 4 * P; S.mesh_tri_off = sc->d_int + 4 * P + M + 1;
+        S.mesh_nodes = sc->d_nodes; S.mesh_tris = sc->d_tris;
+    }
+    S.P = P; S.K = K; S.nbody = m->h.nbody; S.nlight = NL;
+    S.prim_type = sc->d_int; S.prim_body = sc->d_int + P; S.prim_flags = sc->d_int + 2 * P;
+    S.prim_size = sc->d_float + off[0]; S.prim_pos = sc->d_float + off[1]; S.prim_quat = sc->d_float + off[2];
+    S.prim_rgba = sc->d_float + off[3]; S.prim_rgb2 = sc->d_float + off[4]; S.prim_tex = sc->d_float + off[5];
+    S.kp_rgba = sc->d_float + off[6]; S.light_dir = sc->d_float + off_ld; S.light_diff = sc->d_float + off_lc;
+    for (int q = 0; q < 4; ++q) { S.marker_rgba[q] = t->marker_rgba[q]; S.seg_rgba[q] = t->segment_rgba[q]; }
+    S.marker_r = t->marker_radius; S.seg_r = t->segment_radius;
+    for (int q = 0; q < 3; ++q) { S.head_amb[q] = t->head_ambient[q]; S.head_diff[q] = t->head_diffuse[q]; S.bg[q] = t->background[q]; }
+    S.alpha = t->alpha;
+    e = upload(&sc->d_scene, &sc->S, 1);
+    if (e != hipSuccess) return bail(e);
+    clear_error();
+    return sc;
+}
+
+extern "C" void stac_render_scene_destroy(stac_render_scene *sc) {
+    if (!sc) return;
+    DeviceGuard dg(sc->device);
+    (void)hipFree(sc->d_int);
+    (void)hipFree(sc->d_float);
+    (void)hipFree(sc->d_scene);
+    if (sc->d_nodes) (void)hipFree(sc->d_nodes);
+    if (sc->d_tris) (void)hipFree(sc->d_tris);
+    delete sc;
+}
+
+extern "C" int32_t stac_render(const stac_render_scene *sc, int32_t N, const float *xpos, const float *xquat, const float *kp,
+                               const float *markers, int32_t show_error, const float *cam, float tan_half_fovy, int32_t width,
+                               int32_t height, uint8_t *rgb_out, int32_t *seg_out, float *depth_out, void *stream) {
+    if (!sc || N < 0 || width < 1 || height < 1 || width > 32768 || height > 32768 || !(tan_half_fovy > 0.0f) ||
+        !(tan_half_fovy < INFINITY) || (N > 0 && (!xpos || !xquat || !cam)))
+        return fail(STAC_ERR_INVALID, "stac_render: bad argument");
+    DeviceGuard dg(sc->device);
+    RenderCall C{};
+    C.N = N; C.W = width; C.H = height; C.show_error = show_error ? 1 : 0;
+    C.xpos = xpos; C.xquat = xquat; C.kp = kp; C.markers = markers; C.cam = cam; C.tanh = tan_half_fovy;
+    C.rgb = rgb_out; C.seg = seg_out; C.depth = depth_out;
+    return launch_result("stac_render", launch_render(sc->d_scene, C, sc->has_mesh, (hipStream_t)stream));
+}

@@ -1,4 +1,4 @@
-// Shared layout of the render kernel (stac_render.hip) and its host entry points (stac_abi.hip).
+// Shared layout of the render kernel (stac_render.hip) and its host entry points (below the kernel).
 #pragma once
 
 #include <stdint.h>

@@ -1,4 +1,4 @@
-// Fit report: per-keypoint marker errors and exact quantiles (rule and shared functions: stac_report.hpp; entry points: stac_abi.hip).
+// Fit report: per-keypoint marker errors and exact quantiles (rule and shared functions: stac_report.hpp; entry points: below the kernels).
 //
 // One call, nine operations on the caller's stream, no copy to the host, no workgroup ever waits for another:
 //   0. two memsets: the `hist` output and the histograms of the later passes in the workspace (everything the call adds into)
@@ -23,6 +23,7 @@
 // not depend on their order).  They read the keys, not sqerr: sqerr is frame-major, and it does not say whether gap was 0.
 #include <hip/hip_runtime.h>
 
+#include "stac_host.hpp"
 #include "stac_report.hpp"
 
 namespace stac {
@@ -253,7 +254,7 @@ __global__ __launch_bounds__(kReportThreads) void report_finish12_kernel(const u
 
 }  // namespace
 
-hipError_t launch_report_errors(const float *markers, const float *kp, const int32_t *gap, int64_t N, int32_t K, int32_t Q,
+static hipError_t launch_report_errors(const float *markers, const float *kp, const int32_t *gap, int64_t N, int32_t K, int32_t Q,
                                 const int32_t *permille_host, float *sqerr, double *frame_sse, int32_t *frame_n, int64_t *count, double *sum,
                                 float *max, int64_t *argmax, int64_t *hist, float *quant, void *workspace, hipStream_t s) {
     const ReportLayout L = report_layout(N, K, Q);
@@ -296,3 +297,52 @@ hipError_t launch_report_errors(const float *markers, const float *kp, const int
 }
 
 }  // namespace stac
+
+// ---- C ABI entry points (include/stac_hip.h): every argument is checked before the device is touched ------------------------------
+extern "C" int64_t stac_report_workspace(int64_t n_frames, int32_t n_kp, int32_t n_quant) {
+    const ReportLayout L = report_layout(n_frames, n_kp, n_quant);
+    if (L.bytes < 0)
+        return fail(STAC_ERR_INVALID, "stac_report_workspace: n_frames >= 1, n_kp >= 1, n_quant 1 .. " + std::to_string(kReportMaxQuant) +
+                                          " (and a workspace size within int64)");
+    return L.bytes;
+}
+
+extern "C" int32_t stac_report_errors(const stac_report_params *p) {
+    if (!p) return fail(STAC_ERR_INVALID, "stac_report_errors: null parameter struct");
+    if (p->n_frames < 1 || p->n_kp < 1) return fail(STAC_ERR_INVALID, "stac_report_errors: n_frames >= 1, n_kp >= 1");
+    if (p->n_quant < 1 || p->n_quant > kReportMaxQuant)
+        return fail(STAC_ERR_INVALID, "stac_report_errors: n_quant " + std::to_string(p->n_quant) + " is outside 1 .. " +
+                                          std::to_string(kReportMaxQuant));
+    const ReportLayout L = report_layout(p->n_frames, p->n_kp, p->n_quant);
+    if (L.bytes < 0 || p->n_frames > (((int64_t)1 << 58) / p->n_kp))
+        return fail(STAC_ERR_INVALID, "stac_report_errors: array sizes beyond int64");
+    if (!p->markers || !p->kp || !p->permille || !p->sqerr || !p->frame_sse || !p->frame_n || !p->count || !p->sum || !p->max ||
+        !p->argmax || !p->hist || !p->quant || !p->workspace)
+        return fail(STAC_ERR_INVALID, "stac_report_errors: null markers / kp / permille / output / workspace (only gap may be null)");
+    for (int q = 0; q < p->n_quant; ++q)
+        if (p->permille[q] < 0 || p->permille[q] > 1000)
+            return fail(STAC_ERR_INVALID, "stac_report_errors: permille[" + std::to_string(q) + "] = " + std::to_string(p->permille[q]) +
+                                              " is outside 0 .. 1000");
+    if (p->workspace_bytes < L.bytes)
+        return fail(STAC_ERR_INVALID, "stac_report_errors: workspace_bytes = " + std::to_string(p->workspace_bytes) + ", " +
+                                          std::to_string(L.bytes) + " are needed (stac_report_workspace)");
+    const int64_t NK = p->n_frames * p->n_kp, K = p->n_kp, Q = p->n_quant;
+    const HostBuf buf[13] = {
+        {"markers", (uintptr_t)p->markers, NK * 12, 4}, {"kp", (uintptr_t)p->kp, NK * 12, 4}, {"gap", (uintptr_t)p->gap, p->gap ? NK * 4 : 0, 4},
+        {"sqerr", (uintptr_t)p->sqerr, NK * 4, 4}, {"frame_sse", (uintptr_t)p->frame_sse, p->n_frames * 8, 8},
+        {"frame_n", (uintptr_t)p->frame_n, p->n_frames * 4, 4}, {"count", (uintptr_t)p->count, K * 8, 8}, {"sum", (uintptr_t)p->sum, K * 8, 8},
+        {"max", (uintptr_t)p->max, K * 4, 4}, {"argmax", (uintptr_t)p->argmax, K * 8, 8}, {"hist", (uintptr_t)p->hist, K * kReportBins0 * 8, 8},
+        {"quant", (uintptr_t)p->quant, K * Q * 4, 4}, {"workspace", (uintptr_t)p->workspace, L.bytes, 8}};
+    for (int i = 0; i < 13; ++i)
+        if (buf[i].lo % buf[i].align != 0)
+            return fail(STAC_ERR_INVALID, std::string("stac_report_errors: ") + buf[i].name + " must be " + std::to_string(buf[i].align) +
+                                              "-byte aligned");
+    const HostBuf *a, *b;
+    if (find_overlap(buf, 13, &a, &b))  // (gap == NULL: zero bytes, overlaps nothing)
+        return fail(STAC_ERR_INVALID, std::string("stac_report_errors: ") + a->name + " and " + b->name +
+                                          " overlap: inputs, outputs and workspace are distinct buffers");
+    return launch_result("stac_report_errors",
+                         launch_report_errors(p->markers, p->kp, p->gap, p->n_frames, p->n_kp, p->n_quant, p->permille, p->sqerr, p->frame_sse,
+                                              p->frame_n, p->count, p->sum, p->max, p->argmax, p->hist, p->quant, p->workspace,
+                                              (hipStream_t)p->stream));
+}

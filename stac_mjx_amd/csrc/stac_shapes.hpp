@@ -1,7 +1,7 @@
 // stac_shapes.hpp -- the kernel instantiations that ship, and the one lookup the host plans its launches with.
 //
 // launch_q_phase (stac_kernels.hip) and launch_q_phase_lm (stac_lm.hip) expand these tables into their templates; the host
-// (stac_abi.hip, plan_q / plan_q_lm) asks q_shape which row a launch gets.
+// (stac_q.hip, plan_q / plan_q_lm) asks q_shape which row a launch gets.
 #pragma once
 
 // ---- the instantiations that ship -------------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-"""Host checks of the split-kinematics rotation table (build_fk3_program, stac_abi.hip): P2 runs whole rounds of 16 lanes, so the
+"""Host checks of the split-kinematics rotation table (build_fk3_program, stac_planner.hip): P2 runs whole rounds of 16 lanes, so the
 table is padded to a multiple of 16 tasks, and every padding task -- up to the area's capacity, which the 32-lane kernels' last round
 reads -- is an exact no-op: it rotates the zero vector by a quaternion that exists and stores to the sink.  No GPU."""
 

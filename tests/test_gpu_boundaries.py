@@ -5,7 +5,7 @@ kernels' arithmetic.
 Each case names a model (`_edge_tables`: exactly nq coordinates and K fit sites), the lane width / developer switches of the
 launch, and what must happen: the instantiation `stac_debug_last_q_kernel` reports after the q_phase (G, NQR, WPE, SPECP), or a
 refusal with STAC_ERR_CAPACITY (-3) -- at model creation or at the launch.  The edges (stac_shapes.hpp, the STAC_Q_*SHAPES
-tables: a shape holds nq <= G * NQR; the lean kernels hold K <= lean_site_rounds(G, NQR) * G sites in registers; stac_abi.hip:
+tables: a shape holds nq <= G * NQR; the lean kernels hold K <= lean_site_rounds(G, NQR) * G sites in registers; stac_q.hip:
 K <= 4096, P + 3 <= kMaxKinds, LM n <= 192, latency roles of 8 lanes up to nq = 80 and of 16 up to 128) are listed with the
 cases; test_every_shape_edge_has_cases (CPU) fails when a shape is added to the tables without cases on both sides of its edge.
 """
@@ -106,7 +106,7 @@ _EDGE_CASES = [
     ("gen64w4-nq129", 129, 8, FIXED, 64, THR4, None, (64, 4, 2, 0)),
     ("gen64-nq256", 256, 8, FIXED, 64, THR2, None, (64, 4, 2, 0)),
     ("gen64-nq257", 257, 8, FIXED, 64, THR2, None, REFUSE_LAUNCH),
-    # latency group width: 8 lanes per role up to nq = 80, 16 up to 128 (stac_abi.hip, run_q)
+    # latency group width: 8 lanes per role up to nq = 80, 16 up to 128 (stac_q.hip, plan_q)
     ("lat8-nq80", 80, 8, FIXED, 0, _lat(8), None, (8, 10, 2, 8)),
     ("lat8-nq81", 81, 8, FIXED, 0, _lat(8), None, (16, 8, 2, 4)),
     ("lat8R4-nq80", 80, 8, FIXED, 0, dict(_lat(8), STAC_HIP_SPECR="4"), None, (8, 10, 2, 4)),

@@ -101,7 +101,7 @@ def _comb_tables(S):
 
 
 def _fk_slots(parent):
-    """How many LDS slots the host allots for fk_kernel (stac_abi.hip, build_fk_tables): a body with a child that does not follow
+    """How many LDS slots the host allots for fk_kernel (stac_planner.hip, build_fk_tables): a body with a child that does not follow
     it directly parks its transform until its last child has read it; a slot is free again from that child's step on."""
     nb = len(parent)
     last_child, far = [-1] * nb, [False] * nb

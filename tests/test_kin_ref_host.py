@@ -189,7 +189,7 @@ def test_m_opt_against_the_statement(model, T, reg_coef, m_opt_inputs):
 
 def test_hand_built_trees_park_what_they_claim():
     """The trees of tests/test_gpu_offsets_fk.py reach the edges they are named after: a replica of the slot allocator of
-    stac_abi.hip (build_fk_tables) counts the parked transforms; 83 is the last count under fk_kernel's 160 KiB of LDS."""
+    stac_planner.hip (build_fk_tables) counts the parked transforms; 83 is the last count under fk_kernel's 160 KiB of LDS."""
     assert {k: _fk_slots(f().body_parentid.tolist()) for k, (f, _) in FK_TREES.items()} == {k: s for k, (_, s) in FK_TREES.items()}
     assert _fk_slots(_comb_tables(85).body_parentid.tolist()) == FK_MAX_SLOTS + 1
     assert (7 * FK_MAX_SLOTS + 57) * 256 == 163328 <= 160 * 1024 < (7 * (FK_MAX_SLOTS + 1) + 57) * 256

@@ -1,4 +1,4 @@
-"""Host checks of the wrench-sum program of the lean 16-lane throughput kernels (build_wsum_program, stac_abi.hip): row sweeps for the
+"""Host checks of the wrench-sum program of the lean 16-lane throughput kernels (build_wsum_program, stac_planner.hip): row sweeps for the
 short site ranges, component tasks with a checkpoint for ranges with a common first site, whole ranges for the rest.  The program is
 emulated in numpy float32 and compared bit for bit with the oracle's sum of every range -- left to right from zero -- on wrench entries
 seeded with +0.0, -0.0, denormals, infinities and NaN.  No GPU."""

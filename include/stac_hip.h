@@ -285,6 +285,30 @@ int32_t stac_post_stitch(const float *src, int64_t C, int32_t F, int32_t overlap
 int32_t stac_post_qvel(const float *qpos, int64_t N, int32_t nq, int32_t F, double dt, int32_t freejoint, double max_qvel,
                        float *qvel, void *stream);
 
+/* Smoothing fitted poses along time (DESIGN.md "Smoothing fitted poses").  The reference has no counterpart: users of a
+ * fitted trajectory low-pass qpos by hand in front of utils.compute_velocity_from_kinematics (stac_mjx/utils.py:302-347),
+ * whose forward difference divides the frame-to-frame jitter of independent per-frame fits by dt.
+ *
+ * qpos[N, nq] -> out[N, nq], N whole clips of clip_len >= W = 2 * half_window + 1 rows; every element of out written once.
+ * taps: HOST float[W * W], row p = the weights of an output at window position p (read before the call returns).  Frame t
+ * of a clip uses the window that starts at s = clamp(t - half_window, 0, clip_len - W) of that clip and row p = t - s;
+ * nothing is read from another clip.  quat_cols: HOST int32[n_quat], the first columns of the quaternion blocks (w, x, y,
+ * z; columns 3 of a free joint, the four of a ball joint), read before the call returns; every other column is a scalar.
+ * Scalar column: acc = taps[p][0] * x[s], then acc = acc + taps[p][j] * x[s + j] for j = 1 .. W-1, in float32 with one
+ * rounding per operation, then clamped to [lb, ub] of the column with comparisons that keep a NaN (lb, ub: device
+ * float[nq], both or neither; NULL = no clamp).  Quaternion block, c = the block of frame t itself: per j, y = x[s + j],
+ * d = ((c0*y0 + c1*y1) + c2*y2) + c3*y3, sg = d < 0 ? -1 : +1, and per component acc_k (+)= taps[p][j] * (sg * y_k) in the
+ * order of a scalar column; n = sqrt(((a0*a0 + a1*a1) + a2*a2) + a3*a3); the output is acc_k / n where n > 0, else the
+ * bits of c; no clamp.  The output lies in the hemisphere of the frame's own quaternion.
+ * half_window in 1 .. 16; n_quat in 0 .. 64 (kSmoothMaxQuat; the free joint's one block is all the models of
+ * tests/golden/ have), blocks inside the row and disjoint; rows of nq floats must leave room for one window in 64 KiB of
+ * LDS (nq <= 437 at half_window 16, <= 3 275 at 1); arrays 4-byte aligned; out must overlap none of qpos, lb, ub -- in
+ * place is not possible (all of it STAC_ERR_INVALID, before anything is launched or written).  N == 0: nothing is done.
+ * A stream-ordered allocation of W * W floats, one or two launches that fill it and one kernel on `stream`; no
+ * synchronisation, no workgroup waits for another. */
+int32_t stac_post_smooth(const float *qpos, int64_t N, int32_t nq, int32_t clip_len, int32_t half_window, const float *taps,
+                         const int32_t *quat_cols, int32_t n_quat, const float *lb, const float *ub, float *out, void *stream);
+
 /* ---- Filling missing keypoints before the fit (no stac_model needed; the current device is used) --------------------
  * DESIGN.md "Filling missing keypoints".  Replaces the gap filling that every user of the reference writes by hand in
  * front of stac_mjx.main.run_stac (stac_mjx/main.py:33-139 takes kp_data as it comes and has no answer to a NaN: the

@@ -36,9 +36,14 @@ _MUJOCO_REQUIRED = ("solver", "iterations", "ls_iterations")
 # reject_outliers: off (default) | hampel, with outlier_window (half-width, 1 .. 16, default 5), outlier_nsigma (default 3.0) and
 # outlier_min_dev (default 0.001, units of kp_data) -- finite but wrong keypoints become missing ones in front of fill_missing;
 # report: off (default) | on, with report_quantiles (1 .. 8 permille values, default [500, 900, 990]) and report_worst (frames listed,
-# default 10) -- a <result file>.report.json next to every result file, read from the caller's config)
+# default 10) -- a <result file>.report.json next to every result file, read from the caller's config;
+# smooth: off (default) | savgol | gaussian, with smooth_window (half-width H, 1 .. 16, default 3: windows of 2 H + 1 frames),
+# smooth_order (savgol: the polynomial order, 0 <= order < 2 H + 1, default 2) and smooth_sigma (gaussian: frames, > 0, default H / 2)
+# -- the qpos of an ik_only run is low-pass filtered per clip on the GPU between the stitch and qvel, the file gains qpos_raw and its
+# xpos / xquat / marker_sites are those of the smoothed pose; needs postprocess = gpu, read from the caller's config)
 _STAC_EXTENSIONS = ("solver", "lanes_per_chain", "device", "time_indices", "fit_frames_per_clip", "reference_marker_order", "gather", "gather_max_bytes", "lm_maxiter", "postprocess", "fill_missing",
-                    "reject_outliers", "outlier_window", "outlier_nsigma", "outlier_min_dev", "report", "report_quantiles", "report_worst")
+                    "reject_outliers", "outlier_window", "outlier_nsigma", "outlier_min_dev", "report", "report_quantiles", "report_worst",
+                    "smooth", "smooth_window", "smooth_order", "smooth_sigma")
 _MODEL_EXTENSIONS = ("KP_NAMES_LABEL3D_PATH",)
 
 
@@ -95,6 +100,40 @@ def report_options(stac) -> tuple:
     if isinstance(w, bool) or not isinstance(w, int) or w < 0:
         raise ConfigError(f"stac.report_worst must be an integer >= 0, not {w!r}")
     return mode == "on", tuple(q), w
+
+
+SMOOTH_DEFAULTS = {"smooth_window": 3, "smooth_order": 2}
+SMOOTH_MAX_WINDOW = 16  # csrc/stac_smooth.hpp: kSmoothMaxHalf
+
+
+def smooth_options(stac) -> dict:
+    """``stac.smooth`` and its parameters out of a ``stac`` mapping -> ``{"kind", "half_window", "order", "sigma"}``, absent keys
+    at their defaults (``order`` is None for gaussian, ``sigma`` for savgol; both for off).  ``ConfigError`` for anything else
+    than off | savgol | gaussian (a bare YAML ``off`` arrives as False), a half-width that is not an integer in 1 .. 16, an order
+    outside 0 .. 2 H, a sigma that is not a finite number > 0, and for smoothing without ``postprocess: gpu`` (there is no host
+    path) or with ``reference_marker_order: true`` (the rows of marker_sites must be the rows of qpos)."""
+    import math
+
+    kind = stac.get("smooth", "off")
+    kind = "off" if kind is False or kind is None else kind
+    if not isinstance(kind, str) or kind not in ("off", "savgol", "gaussian"):
+        raise ConfigError(f"stac.smooth must be off, savgol or gaussian, not {kind!r}")
+    h = stac.get("smooth_window", SMOOTH_DEFAULTS["smooth_window"])
+    if isinstance(h, bool) or not isinstance(h, int) or not 1 <= h <= SMOOTH_MAX_WINDOW:
+        raise ConfigError(f"stac.smooth_window (the half-width in frames) must be an integer in 1 .. {SMOOTH_MAX_WINDOW}, not {h!r}")
+    order = stac.get("smooth_order", SMOOTH_DEFAULTS["smooth_order"])
+    if isinstance(order, bool) or not isinstance(order, int) or order < 0 or (kind == "savgol" and order > 2 * h):
+        raise ConfigError(f"stac.smooth_order must be an integer with 0 <= order < {2 * h + 1} (the window), not {order!r}")
+    sigma = stac.get("smooth_sigma", h / 2.0)
+    if isinstance(sigma, bool) or not isinstance(sigma, (int, float)) or not math.isfinite(sigma) or not sigma > 0:
+        raise ConfigError(f"stac.smooth_sigma (in frames) must be a finite number > 0, not {sigma!r}")
+    if kind != "off":
+        if stac.get("postprocess", "host") != "gpu":
+            raise ConfigError(f"stac.smooth = {kind} runs on the device only (there is no host path for smoothing): set stac.postprocess to gpu as well")
+        if bool(stac.get("reference_marker_order", False)):
+            raise ConfigError(f"stac.smooth = {kind} recomputes marker_sites from the smoothed qpos row by row, which the reference's "
+                              "frame-major row order of marker_sites (stac.reference_marker_order: true) cannot hold")
+    return {"kind": kind, "half_window": h, "order": order if kind == "savgol" else None, "sigma": float(sigma) if kind == "gaussian" else None}
 
 
 class ConfigNode(dict):
@@ -246,6 +285,9 @@ def validate_config(cfg: dict) -> ConfigNode:
     if isinstance(stac.get("report"), bool):  # a bare `off` / `on` in YAML 1.1 is the boolean
         stac["report"] = "on" if stac["report"] else "off"
     report_options(stac)
+    if stac.get("smooth", "off") is False:
+        stac["smooth"] = "off"
+    smooth_options(stac)
     return _wrap({"model": model, "stac": stac})
 
 

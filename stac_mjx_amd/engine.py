@@ -55,7 +55,7 @@ ABI_SYMBOLS = (
     "stac_m_phase_workspace_floats", "stac_m_phase_partial", "stac_m_phase_finish",
     "stac_render_scene_create", "stac_render_scene_create_with_meshes", "stac_render_scene_destroy", "stac_render",
     "stac_jpeg_header", "stac_jpeg_workspace_bytes", "stac_jpeg_encode",
-    "stac_post_stitch_rows", "stac_post_stitch", "stac_post_qvel",
+    "stac_post_stitch_rows", "stac_post_stitch", "stac_post_qvel", "stac_post_smooth",
     "stac_prep_fill_workspace", "stac_prep_fill", "stac_prep_reject",
     "stac_report_workspace", "stac_report_errors",
 )  # fmt: skip

@@ -32,6 +32,10 @@ def run_stac(cfg, kp_data, kp_names, base_path=None, *, setup=None, device=None)
     median into missing ones, on the GPU, and adds ``kp_rejected`` to both files (DESIGN.md "Rejecting keypoint outliers").
     ``stac.report: on`` computes the marker errors of each phase's final result on the GPU and writes them as
     ``<result file>.report.json`` next to the file (DESIGN.md "Fit report"); the result files themselves do not change.
+    ``stac.smooth: savgol | gaussian`` (needs ``postprocess: gpu``) low-pass filters the ``qpos`` of the ik_only run along time on
+    the GPU, per clip, after the stitch and before ``qvel``: the file's ``qpos`` / ``xpos`` / ``xquat`` / ``marker_sites`` / ``qvel``
+    are those of the smoothed pose and ``qpos_raw`` keeps the fitted one (DESIGN.md "Smoothing fitted poses"); clips shorter than
+    the window of ``2 * smooth_window + 1`` frames are a ``ValueError``.
     """
     base_path = Path.cwd() if base_path is None else Path(base_path)
     kp_data = np.asarray(kp_data)
@@ -43,6 +47,7 @@ def run_stac(cfg, kp_data, kp_names, base_path=None, *, setup=None, device=None)
             "keypoints in kp_data.")
     reject_mode, reject_args = _reject_outliers_mode(cfg)  # (bad values and hampel without fill_missing: before any work)
     report_on, report_permille, report_worst = _report_mode(cfg)
+    smooth = _smooth_mode(cfg)  # (bad values, smoothing without postprocess = gpu or with reference_marker_order: before any work)
     start = time.time()
     fit_offsets_path = base_path / cfg.stac.fit_offsets_path
     ik_only_path = base_path / cfg.stac.ik_only_path
@@ -55,6 +60,11 @@ def run_stac(cfg, kp_data, kp_names, base_path=None, *, setup=None, device=None)
             raise ValueError("stac.report = on cannot pair marker_sites with kp_data in the reference's frame-major row order "
                              "(stac.reference_marker_order: true with more than one clip of more than one frame): the rows of "
                              "marker_sites are then not the rows of kp_data")
+    if smooth is not None and not cfg.stac.skip_ik_only:
+        # stac.smooth: a clip must hold a whole window -- known as soon as the config that decides the clip length is, the one stored
+        # with the fit (the caller's, when this run writes it)
+        fit_cfg = cfg if not cfg.stac.skip_fit_offsets else io.load_stac_data(fit_offsets_path)[0]
+        _check_smooth_clip(smooth, _smooth_clip_len(fit_cfg, kp_data.shape[0]))
     stac = Stac(xml_path, cfg, kp_names, setup=setup, device=device)
     if not cfg.stac.skip_ik_only and dist.world()[1] > 1 and str(cfg.stac.get("gather", "auto") or "auto") == "none":
         # an EXPLICIT gather = none cannot serve a continuous run (cross-fades reach across shard borders): say so before any
@@ -133,6 +143,9 @@ def run_stac(cfg, kp_data, kp_names, base_path=None, *, setup=None, device=None)
         raise ValueError("stac.gather = none writes per-rank shards, but stac.continuous cross-fades neighbouring "
                          "clips across shard borders: use gather = rank0 (or all, or auto) for continuous runs")
     post = {"continuous": bool(cfg.stac.continuous), "n_frames_per_clip": F, "infer_qvels": bool(cfg.stac.infer_qvels)} if post_gpu else None
+    if smooth is not None:  # (postprocess = gpu: _smooth_mode)
+        _check_smooth_clip(smooth, _smooth_clip_len(cfg, kp_data.shape[0]))
+        post["smooth"] = smooth
     ik_data = stac.ik_only(kp_data, fit_data.offsets, gather=mode, **({"post": post} if post_gpu else {}))
     if rank != 0 and not sharded and mode != "all":
         dist.barrier()  # this rank holds its own shard only: rank 0 post-processes and writes the gathered result
@@ -205,6 +218,33 @@ def _write_report(stac, data, result_path, permille, worst) -> Path:
         print(line)
     print(f"report: wrote {path}", flush=True)
     return path
+
+
+def _smooth_mode(cfg):
+    """``stac.smooth``: "off" (default) | "savgol" | "gaussian" -> None, or the options of ``config.smooth_options`` as the
+    ``post["smooth"]`` of ``Stac.ik_only`` takes them.  ``ValueError`` for a bad value of any of the four keys, and for smoothing
+    without ``postprocess: gpu`` or with ``reference_marker_order: true``."""
+    from .config import smooth_options
+
+    opt = smooth_options(cfg.stac)
+    return None if opt["kind"] == "off" else opt
+
+
+def _smooth_clip_len(fit_cfg, n_frames: int) -> int:
+    """Rows that ``stac.smooth`` treats as one clip: ``n_frames_per_clip`` of the config stored with the fit, or, for a continuous
+    run, everything (the stitched rows of ``n_frames // n_frames_per_clip`` windows)."""
+    F = int(fit_cfg.stac.n_frames_per_clip)
+    if not fit_cfg.stac.continuous:
+        return F
+    n_clips, ov = n_frames // max(F, 1), utils.CONTINUOUS_BATCH_OVERLAP
+    return 0 if n_clips == 0 else F + ov + max(n_clips - 2, 0) * F + max(F - ov, 0)
+
+
+def _check_smooth_clip(smooth, clip_len: int):
+    W = 2 * smooth["half_window"] + 1
+    if clip_len < W:
+        raise ValueError(f"stac.smooth = {smooth['kind']} with smooth_window = {smooth['half_window']} needs clips of at least {W} "
+                         f"frames (the window), but a clip of this run has {clip_len}")
 
 
 def _postprocess_mode(cfg) -> str:

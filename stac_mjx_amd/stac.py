@@ -152,6 +152,46 @@ class Stac:
             self._log(line)
         return summary
 
+    # -- smooth_result (engine extension; DESIGN.md "Smoothing fitted poses") ----------------------------------------------
+    def smooth_result(self, data, kind, half_window=3, order=None, sigma=None) -> StacData:
+        """Smooths a stored ``ik_only`` result again without refitting, on the GPU (``post.smooth``): the counterpart of
+        ``fit_report(path)``.  ``data``: the path of a result file (a ``*.manifest.json`` reads a sharded run), whose stored config
+        decides the clips -- a continuous run is one clip, else clips of its ``n_frames_per_clip`` rows -- or a ``StacData``, with
+        this object's config.  It starts from ``qpos_raw`` when the result has one, else from ``qpos``, and returns a ``StacData``
+        whose ``qpos_raw`` is that start, whose ``qpos`` is its smoothed version (``kind`` / ``half_window`` / ``order`` /
+        ``sigma`` as ``stac.smooth`` and its keys), whose ``xpos`` / ``xquat`` / ``marker_sites`` are the kinematics of that
+        under the stored ``offsets`` and whose ``qvel`` is inferred again when the result had one; every other field passes.
+        The engine's offsets are left as they were."""
+        from . import io
+        from . import post as gpost
+
+        taps = gpost.smooth_taps(kind, half_window, order=order, sigma=sigma)
+        cfg = self.cfg
+        if not isinstance(data, StacData):
+            path = Path(data)
+            cfg, data = io.load_sharded_stac_data(path) if path.name.endswith(".manifest.json") else io.load_stac_data(path)
+        raw = np.asarray(data.qpos_raw if np.asarray(data.qpos_raw).size else data.qpos, dtype=np.float32)
+        nq, K = self.setup.tables.nq, self.setup.tables.nsite
+        if raw.ndim != 2 or raw.shape[1] != nq:
+            raise ValueError(f"smooth_result: qpos must be [frames, {nq}], got {raw.shape}")
+        F = int(cfg.stac.n_frames_per_clip)
+        clip_len = raw.shape[0] if bool(cfg.stac.continuous) else F
+        if clip_len < taps.shape[0]:
+            raise ValueError(f"smooth_result: clips of {clip_len} frames are shorter than the window of {taps.shape[0]} frames")
+        eng = self.engine
+        keep = eng.get_site_pos()
+        eng.set_site_pos(torch.as_tensor(np.array(data.offsets, dtype=np.float32)).reshape(K, 3))
+        try:
+            out = self._smooth_gpu(torch.as_tensor(np.array(raw)).to(eng.device), clip_len, taps)
+            if np.asarray(data.qvel).size:
+                out["qvel"] = gpost.infer_qvel(out["qpos"], F, self._timestep, self._freejoint)
+            host = {k: v.cpu().numpy() for k, v in out.items()}
+        finally:
+            eng.set_site_pos(keep)
+        from dataclasses import replace
+
+        return replace(data, qpos_raw=raw, **host)
+
     # -- fit_offsets (stac.py:253-354) ------------------------------------------------------------------
     def fit_offsets(self, kp_data, time_indices=None) -> StacData:
         """Alternate pose and offset optimisation.
@@ -226,7 +266,9 @@ class Stac:
         ``post`` (``stac.postprocess: gpu``, engine extension): ``{"continuous", "n_frames_per_clip", "infer_qvels"}`` as the fit
         file's config decided them.  The cross-fade stitch of ``utils.handle_edge_effects`` and the ``qvel`` of
         ``utils.compute_velocity_from_kinematics`` then run on the device (``post.py``), wherever the full tensors are, only
-        the stitched arrays cross to the host and the returned ``StacData`` carries ``qvel``.  None: nothing of that."""
+        the stitched arrays cross to the host and the returned ``StacData`` carries ``qvel``.  None: nothing of that.
+        An optional ``post["smooth"]`` (``stac.smooth``: ``{"kind", "half_window", "order", "sigma"}``) smooths ``qpos`` per clip
+        between the two; the ``StacData`` then carries ``qpos_raw`` and the kinematics of the smoothed pose."""
         eng = self.engine
         if post is not None:
             post = self._check_post(post, gather)
@@ -270,7 +312,37 @@ class Stac:
         if out["continuous"] and dist.world()[1] > 1 and self._gather_mode(gather) == "none":
             raise ValueError("stac.gather = none keeps per-rank shards, but a continuous run cross-fades neighbouring clips "
                              "across shard borders: gather (rank0 or all) for continuous runs")
+        if post.get("smooth"):
+            from . import post as gpost
+
+            sm = dict(post["smooth"])
+            if bool(self.cfg.stac.get("reference_marker_order", False)):
+                raise ValueError("stac.smooth recomputes marker_sites from the smoothed qpos row by row, which the reference's "
+                                 "frame-major row order of marker_sites (stac.reference_marker_order: true) cannot hold")
+            # (every bad kind / half_window / order / sigma is a ValueError of smooth_taps)
+            out["smooth"] = {"kind": sm["kind"], "half_window": int(sm["half_window"]),
+                             "taps": gpost.smooth_taps(sm["kind"], sm["half_window"], order=sm.get("order"), sigma=sm.get("sigma"))}
+            if not out["continuous"] and out["n_frames_per_clip"] < 2 * out["smooth"]["half_window"] + 1:
+                raise ValueError(f"stac.smooth: clips of {out['n_frames_per_clip']} frames are shorter than the window of "
+                                 f"{2 * out['smooth']['half_window'] + 1} frames")
         return out
+
+    def _quat_cols(self):
+        """First columns of the quaternion blocks of a qpos row: the free joint's (its address + 3) and every ball joint's."""
+        from .mjcf import JNT_BALL, JNT_FREE
+
+        t = self.setup.tables
+        jt, adr = np.asarray(t.jnt_type), np.asarray(t.jnt_qposadr)
+        return [int(a) + 3 for a in adr[jt == JNT_FREE]] + [int(a) for a in adr[jt == JNT_BALL]]
+
+    def _smooth_gpu(self, qpos, clip_len, taps):
+        """``post.smooth`` of a flat device ``qpos`` with this model's quaternion columns and the engine's bounds, and the
+        kinematics of the result under the offsets the engine holds -> {qpos, xpos, xquat, marker_sites} (device)."""
+        from . import post as gpost
+
+        q = gpost.smooth(qpos, clip_len, taps, self._quat_cols(), lb=self.engine.lb, ub=self.engine.ub)
+        fk = self.engine.fk(q, want=("xpos", "xquat", "site_xpos"))
+        return {"qpos": q, "xpos": fk["xpos"], "xquat": fk["xquat"], "marker_sites": fk["site_xpos"]}
 
     def _postprocess_gpu(self, res, kp_clips, post):
         """Stitch (continuous) and qvel (infer_qvels) of the flattened outputs on the device -> {name: device tensor}."""
@@ -286,6 +358,11 @@ class Stac:
                 if a.shape[0] % (F + ov) != 0:
                     raise ValueError(f"cannot reshape {a.shape[0]} rows of {name} into windows of {F + ov} frames")
                 out[name] = gpost.stitch(a.reshape((-1, F + ov) + tuple(a.shape[1:])), F, ov)
+        if post.get("smooth") and out["qpos"].shape[0]:
+            # stac.smooth: the fitted pose stays as qpos_raw; qpos, and the kinematics that go with it, are the smoothed one's.  A
+            # continuous run is one clip (the stitched rows), else clips are the F rows they were solved as: no window crosses a border
+            out["qpos_raw"] = out["qpos"]
+            out.update(self._smooth_gpu(out["qpos"], out["qpos"].shape[0] if post["continuous"] else F, post["smooth"]["taps"]))
         if post["infer_qvels"] and out["qpos"].shape[0]:
             out["qvel"] = gpost.infer_qvel(out["qpos"], F, self._timestep, self._freejoint)
         return out

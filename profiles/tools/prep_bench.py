@@ -103,7 +103,7 @@ def main():
 
     if not torch.cuda.is_available():
         raise SystemExit("prep_bench needs a GPU: nothing is measured without one")
-    lib = prep.bind(load_library())
+    lib = load_library()
     T, K = args.frames, args.kp
     rng = np.random.default_rng(5)
     base = (np.cumsum(rng.standard_normal((T, 3 * K)).astype(np.float32) * np.float32(1e-3), axis=0, dtype=np.float32)

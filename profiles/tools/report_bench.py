@@ -105,7 +105,7 @@ def main():
 
     if not torch.cuda.is_available():
         raise SystemExit("report_bench needs a GPU: nothing is measured without one")
-    lib = report.bind(load_library())
+    lib = load_library()
     N, K, permille = args.frames, args.kp, report.DEFAULT_PERMILLE
     Q = len(permille)
     rng = np.random.default_rng(9)

@@ -51,6 +51,31 @@ class ConfigError(ValueError):
     pass
 
 
+def _switch(stac, key):
+    """``stac[key]`` of a key whose first value is ``off`` (absent: off).  YAML 1.1 reads a bare ``off`` / ``on`` as a boolean: False is
+    off, and True is on for ``report``, the one key that has an ``on``.  A key without a value (None) is off, except ``fill_missing``."""
+    v = stac.get(key, "off")
+    if v is False or (v is None and key != "fill_missing"):
+        return "off"
+    return "on" if v is True and key == "report" else v
+
+
+def postprocess_options(stac) -> str:
+    """``stac.postprocess`` out of a ``stac`` mapping -> "host" (default) | "gpu"; ``ConfigError`` for anything else."""
+    mode = stac.get("postprocess", "host")
+    if mode not in ("host", "gpu"):
+        raise ConfigError(f"stac.postprocess must be host or gpu, not {mode!r}")
+    return mode
+
+
+def fill_missing_options(stac) -> str:
+    """``stac.fill_missing`` out of a ``stac`` mapping -> "off" (default) | "linear" | "hold"; ``ConfigError`` for anything else."""
+    mode = _switch(stac, "fill_missing")
+    if not isinstance(mode, str) or mode not in ("off", "linear", "hold"):
+        raise ConfigError(f"stac.fill_missing must be off, linear or hold, not {mode!r}")
+    return mode
+
+
 OUTLIER_DEFAULTS = {"outlier_window": 5, "outlier_nsigma": 3.0, "outlier_min_dev": 0.001}
 OUTLIER_MAX_WINDOW = 16  # csrc/stac_outlier.hpp: kOutlierMaxHalf
 
@@ -61,8 +86,7 @@ def outlier_options(stac) -> tuple:
     or an ``outlier_nsigma`` / ``outlier_min_dev`` that is not a finite number >= 0."""
     import math
 
-    mode = stac.get("reject_outliers", "off")
-    mode = "off" if mode is False or mode is None else mode  # (a bare `off` in YAML 1.1 is the boolean)
+    mode = _switch(stac, "reject_outliers")
     if not isinstance(mode, str) or mode not in ("off", "hampel"):
         raise ConfigError(f"stac.reject_outliers must be off or hampel, not {mode!r}")
     h = stac.get("outlier_window", OUTLIER_DEFAULTS["outlier_window"])
@@ -85,9 +109,7 @@ def report_options(stac) -> tuple:
     """``stac.report`` and its two parameters out of a ``stac`` mapping -> (on, permille values, worst), absent keys at their
     defaults.  ``ConfigError`` for anything else than off | on (or the bool that a bare YAML off / on arrives as), for
     ``report_quantiles`` that is not a list of 1 .. 8 integers in 0 .. 1000, or a ``report_worst`` that is not an integer >= 0."""
-    mode = stac.get("report", "off")
-    if isinstance(mode, bool) or mode is None:
-        mode = "on" if mode else "off"
+    mode = _switch(stac, "report")
     if not isinstance(mode, str) or mode not in ("off", "on"):
         raise ConfigError(f"stac.report must be off or on, not {mode!r}")
     q = stac.get("report_quantiles", REPORT_DEFAULTS["report_quantiles"])
@@ -114,8 +136,7 @@ def smooth_options(stac) -> dict:
     path) or with ``reference_marker_order: true`` (the rows of marker_sites must be the rows of qpos)."""
     import math
 
-    kind = stac.get("smooth", "off")
-    kind = "off" if kind is False or kind is None else kind
+    kind = _switch(stac, "smooth")
     if not isinstance(kind, str) or kind not in ("off", "savgol", "gaussian"):
         raise ConfigError(f"stac.smooth must be off, savgol or gaussian, not {kind!r}")
     h = stac.get("smooth_window", SMOOTH_DEFAULTS["smooth_window"])
@@ -131,9 +152,20 @@ def smooth_options(stac) -> dict:
         if stac.get("postprocess", "host") != "gpu":
             raise ConfigError(f"stac.smooth = {kind} runs on the device only (there is no host path for smoothing): set stac.postprocess to gpu as well")
         if bool(stac.get("reference_marker_order", False)):
-            raise ConfigError(f"stac.smooth = {kind} recomputes marker_sites from the smoothed qpos row by row, which the reference's "
-                              "frame-major row order of marker_sites (stac.reference_marker_order: true) cannot hold")
+            raise ConfigError(smooth_marker_order_refusal(kind))
     return {"kind": kind, "half_window": h, "order": order if kind == "savgol" else None, "sigma": float(sigma) if kind == "gaussian" else None}
+
+
+# Refusals that both run_stac (before any work) and Stac.ik_only (for its direct callers) raise: one text each
+GATHER_NONE_CONTINUOUS = ("stac.gather = none writes per-rank shards, but stac.continuous cross-fades neighbouring "
+                          "clips across shard borders: use gather = rank0 (or all, or auto) for continuous runs")
+POSTPROCESS_GPU_MARKER_ORDER = ("stac.postprocess = gpu cannot cross-fade marker_sites in the reference's frame-major row order "
+                                "(stac.reference_marker_order: true): only postprocess = host reproduces fading across it")
+
+
+def smooth_marker_order_refusal(kind) -> str:
+    return (f"stac.smooth = {kind} recomputes marker_sites from the smoothed qpos row by row, which the reference's "
+            "frame-major row order of marker_sites (stac.reference_marker_order: true) cannot hold")
 
 
 class ConfigNode(dict):
@@ -272,22 +304,12 @@ def validate_config(cfg: dict) -> ConfigNode:
     for k in ("skip_fit_offsets", "skip_ik_only", "infer_qvels", "continuous"):
         if not isinstance(stac[k], bool):
             raise ConfigError(f"stac.{k} must be a bool")
-    if stac.get("postprocess", "host") not in ("host", "gpu"):
-        raise ConfigError(f"stac.postprocess must be host or gpu, not {stac['postprocess']!r}")
-    fill = stac.get("fill_missing", "off")
-    if fill is False:  # a bare `off` in YAML 1.1 is the boolean
-        stac["fill_missing"] = fill = "off"
-    if not isinstance(fill, str) or fill not in ("off", "linear", "hold"):
-        raise ConfigError(f"stac.fill_missing must be off, linear or hold, not {fill!r}")
-    if stac.get("reject_outliers", "off") is False:
-        stac["reject_outliers"] = "off"
-    outlier_options(stac)
-    if isinstance(stac.get("report"), bool):  # a bare `off` / `on` in YAML 1.1 is the boolean
-        stac["report"] = "on" if stac["report"] else "off"
-    report_options(stac)
-    if stac.get("smooth", "off") is False:
-        stac["smooth"] = "off"
-    smooth_options(stac)
+    postprocess_options(stac)
+    for key, options in (("fill_missing", fill_missing_options), ("reject_outliers", outlier_options), ("report", report_options),
+                         ("smooth", smooth_options)):
+        if isinstance(stac.get(key), bool):  # the file that is written with a result says off / on, not the boolean
+            stac[key] = _switch(stac, key)
+        options(stac)
     return _wrap({"model": model, "stac": stac})
 
 

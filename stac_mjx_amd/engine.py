@@ -1,4 +1,4 @@
-"""ctypes binding of ``libstac_hip.so`` (the C ABI of ``include/stac_hip.h``).
+"""``load_library`` and ``Engine``, one compiled model on one GPU, over the ctypes statement of ``libstac_hip.so`` in ``abi.py``.
 
 Device memory, streams and (in ``dist.py``) the process group come from PyTorch-ROCm; every
 compute call goes through the C ABI into hand-written HIP kernels.  There is no CPU or eager
@@ -14,55 +14,19 @@ from pathlib import Path
 import numpy as np
 import torch
 
+from .abi import (ABI_SYMBOLS, StacHipError, StacModelTables, StacQParams, _f32p, _i32p, _ptr, _u8p, check, declare,  # noqa: F401
+                  hip_error, last_error, stream_ptr)
 from .build import LIB, STAMP, source_digest
 
 ABI_VERSION = 3  # include/stac_hip.h: STAC_HIP_ABI_VERSION
-
-_i32p = C.POINTER(C.c_int32)
-_f32p = C.POINTER(C.c_float)
-_u8p = C.POINTER(C.c_uint8)
-
-
-class StacModelTables(C.Structure):
-    _fields_ = [
-        ("nbody", C.c_int32), ("njnt", C.c_int32), ("nq", C.c_int32), ("nsite", C.c_int32),
-        ("body_parentid", _i32p), ("body_pos", _f32p), ("body_quat", _f32p),
-        ("body_jntadr", _i32p), ("body_jntnum", _i32p),
-        ("jnt_type", _i32p), ("jnt_qposadr", _i32p), ("jnt_bodyid", _i32p),
-        ("jnt_pos", _f32p), ("jnt_axis", _f32p), ("qpos0", _f32p),
-        ("site_bodyid", _i32p), ("site_pos", _f32p), ("lb", _f32p), ("ub", _f32p),
-    ]  # fmt: skip
-
-
-class StacQParams(C.Structure):
-    _fields_ = [("tol", C.c_float), ("maxiter", C.c_int32), ("maxls", C.c_int32), ("lanes_per_chain", C.c_int32),
-                ("solver", C.c_int32), ("lm_lambda0", C.c_float)]
-
-
 SOLVERS = {"pg": 0, "lm": 1}  # STAC_SOLVER_PG (the reference's algorithm, parity mode) / STAC_SOLVER_LM
-
-
-class StacHipError(RuntimeError):
-    pass
-
 
 _LIB = None
 
-# every symbol include/stac_hip.h declares
-ABI_SYMBOLS = (
-    "stac_last_error", "stac_last_error_code", "stac_abi_version", "stac_device_count", "stac_model_create", "stac_model_destroy",
-    "stac_model_info", "stac_set_site_pos", "stac_get_site_pos", "stac_fk", "stac_q_solve", "stac_q_phase",
-    "stac_m_phase_workspace_floats", "stac_m_phase_partial", "stac_m_phase_finish",
-    "stac_render_scene_create", "stac_render_scene_create_with_meshes", "stac_render_scene_destroy", "stac_render",
-    "stac_jpeg_header", "stac_jpeg_workspace_bytes", "stac_jpeg_encode",
-    "stac_post_stitch_rows", "stac_post_stitch", "stac_post_qvel", "stac_post_smooth",
-    "stac_prep_fill_workspace", "stac_prep_fill", "stac_prep_reject",
-    "stac_report_workspace", "stac_report_errors",
-)  # fmt: skip
-
 
 def load_library(path: Path | None = None):
-    """Load ``libstac_hip.so``; raises if it has not been built (``__graft_entry__.build()``)."""
+    """Load ``libstac_hip.so`` with every prototype of ``abi.PROTOTYPES`` declared; raises if it has not been built
+    (``__graft_entry__.build()``)."""
     global _LIB
     if _LIB is not None and path is None:
         return _LIB
@@ -75,35 +39,15 @@ def load_library(path: Path | None = None):
         raise StacHipError(f"{p} was built from other sources than the ones in this tree (stamp {STAMP.name} differs): "
                            "rebuild with `python -m stac_mjx_amd.build`")
     lib = C.CDLL(str(p))
-    lib.stac_abi_version.restype = C.c_int32
+    lib.stac_abi_version.restype = C.c_int32  # (ahead of the table: a library of another version may lack some of its functions)
     got = int(lib.stac_abi_version())
     if got != ABI_VERSION:
         raise StacHipError(f"{p} exports ABI version {got}, this binding needs {ABI_VERSION}: rebuild with "
                            "`python -m stac_mjx_amd.build`")
-    lib.stac_last_error.restype = C.c_char_p
-    lib.stac_last_error_code.restype = C.c_int32
-    lib.stac_model_create.restype = C.c_void_p
-    lib.stac_model_create.argtypes = [C.POINTER(StacModelTables)]
-    lib.stac_model_destroy.argtypes = [C.c_void_p]
-    lib.stac_m_phase_workspace_floats.restype = C.c_int64
-    lib.stac_m_phase_workspace_floats.argtypes = [C.c_void_p, C.c_int32]
-    vp = C.c_void_p
-    lib.stac_model_info.argtypes = [vp, _i32p]
-    lib.stac_set_site_pos.argtypes = [vp, vp, vp]
-    lib.stac_get_site_pos.argtypes = [vp, vp, vp]
-    lib.stac_fk.argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp, vp]
-    lib.stac_q_solve.argtypes = [vp, C.POINTER(StacQParams), vp, vp, _u8p, _u8p, _f32p, _f32p, C.c_int32, vp, vp, vp, vp]
-    lib.stac_q_phase.argtypes = [vp, C.POINTER(StacQParams), vp, vp, _u8p, _u8p, C.c_int32, C.c_int32, C.c_int32,
-                                 C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.stac_m_phase_partial.argtypes = [vp, vp, vp, C.c_int32, vp, vp, vp]
-    lib.stac_m_phase_finish.argtypes = [vp, vp, vp, vp, C.c_float, vp, vp, vp]
+    declare(lib)
     if path is None:
         _LIB = lib
     return lib
-
-
-def _ptr(t: torch.Tensor | None):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def _host_u8(a, n):
@@ -153,21 +97,20 @@ class Engine:
             setattr(t, name, arr.ctypes.data_as(ctype))
         self._h = self.lib.stac_model_create(C.byref(t))
         if not self._h:
-            raise StacHipError(f"stac_model_create failed: libstac_hip error {self.lib.stac_last_error_code()}: {self._err()}")
+            raise hip_error(self.lib, "stac_model_create failed", self.lib.stac_last_error_code())
         info = (C.c_int32 * 8)()
         self._check(self.lib.stac_model_info(self._h, info))
         self.info = dict(zip(("nbody", "njnt", "nq", "K", "n_active_bodies", "n_active_joints", "n_levels", "max_level_width"), info))
 
     # -- plumbing ---------------------------------------------------------------------------
     def _err(self) -> str:
-        return self.lib.stac_last_error().decode("utf-8", "replace")
+        return last_error(self.lib)
 
     def _check(self, rc: int):
-        if rc != 0:
-            raise StacHipError(f"libstac_hip error {rc}: {self._err()}")
+        check(self.lib, None, rc)
 
     def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return stream_ptr(self.device)
 
     def _dev(self, a, dtype=torch.float32):
         if isinstance(a, torch.Tensor):

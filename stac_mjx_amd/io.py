@@ -469,3 +469,9 @@ def load_sharded_stac_data(manifest):
                          offsets=first.offsets, kp_data=cat("kp_data"), names_qpos=first.names_qpos,
                          names_xpos=first.names_xpos, kp_names=first.kp_names, qvel=cat("qvel"), kp_gap=cat("kp_gap"),
                          kp_rejected=cat("kp_rejected"), qpos_raw=cat("qpos_raw"))
+
+
+def load_stac_result(path):
+    """``(config, StacData)`` of a result: a result file, or the ``*.manifest.json`` of a sharded run."""
+    path = Path(path)
+    return load_sharded_stac_data(path) if path.name.endswith(".manifest.json") else load_stac_data(path)

@@ -10,27 +10,13 @@ import ctypes as C
 
 import torch
 
-from .engine import StacHipError, _ptr, load_library
+from .abi import _ptr, check, stream_ptr
+from .abi import declare as bind  # noqa: F401  (the name callers of the raw library know: the whole table, idempotent)
+from .engine import load_library
 from .video import JPEG_QUALITY
 
 HEADER_MAX = 640  # csrc/stac_jpeg.hpp: kJpegHeaderMax
 FIRST_GUESS = 0.25  # the output buffer of a first attempt, as a fraction of the raw frames (rendered frames need about 0.01)
-
-
-def bind(lib):
-    """Argument types of the JPEG entry points (idempotent)."""
-    vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
-    lib.stac_jpeg_header.restype = i64
-    lib.stac_jpeg_header.argtypes = [i32, i32, i32, i32, vp, i64]
-    lib.stac_jpeg_workspace_bytes.restype = i64
-    lib.stac_jpeg_workspace_bytes.argtypes = [i64, i32, i32, i32]
-    lib.stac_jpeg_encode.restype = i32
-    lib.stac_jpeg_encode.argtypes = [i64, i32, i32, i32, i32, vp, vp, i64, vp, vp, i64, vp]
-    return lib
-
-
-def _fail(lib, what, rc):
-    raise StacHipError(f"{what}: libstac_hip error {rc}: {lib.stac_last_error().decode('utf-8', 'replace')}")
 
 
 def default_restart_mcus(width: int) -> int:
@@ -40,34 +26,27 @@ def default_restart_mcus(width: int) -> int:
 
 def jpeg_header(width: int, height: int, quality: int = JPEG_QUALITY, restart_mcus: int = 0) -> bytes:
     """SOI .. SOS of the file that the encoder writes for these settings (host only; ``restart_mcus=0``: no DRI segment)."""
-    lib = bind(load_library())
+    lib = load_library()
     buf = (C.c_uint8 * HEADER_MAX)()
-    n = int(lib.stac_jpeg_header(int(width), int(height), int(quality), int(restart_mcus), buf, HEADER_MAX))
-    if n < 0:
-        _fail(lib, "stac_jpeg_header", n)
+    n = check(lib, "stac_jpeg_header", lib.stac_jpeg_header(int(width), int(height), int(quality), int(restart_mcus), buf, HEADER_MAX))
     return bytes(buf[:n])
 
 
 def workspace_bytes(n: int, width: int, height: int, restart_mcus: int) -> int:
-    lib = bind(load_library())
-    need = int(lib.stac_jpeg_workspace_bytes(int(n), int(width), int(height), int(restart_mcus)))
-    if need < 0:
-        _fail(lib, "stac_jpeg_workspace_bytes", need)
-    return need
+    lib = load_library()
+    return int(check(lib, "stac_jpeg_workspace_bytes", lib.stac_jpeg_workspace_bytes(int(n), int(width), int(height), int(restart_mcus))))
 
 
 def encode_raw(rgb: torch.Tensor, out: torch.Tensor, frame_offset: torch.Tensor, workspace: torch.Tensor, quality: int,
                restart_mcus: int, out_capacity: int | None = None):
     """One ``stac_jpeg_encode`` on the current stream of ``rgb``'s device; every tensor is the caller's."""
-    lib = bind(load_library())
+    lib = load_library()
     N, H, W, _ = rgb.shape
     cap = out.numel() if out_capacity is None else int(out_capacity)
     with torch.cuda.device(rgb.device):
         rc = lib.stac_jpeg_encode(N, W, H, int(quality), int(restart_mcus), _ptr(rgb), _ptr(out), cap, _ptr(frame_offset),
-                                  _ptr(workspace), workspace.numel() * workspace.element_size(),
-                                  C.c_void_p(torch.cuda.current_stream(rgb.device).cuda_stream))
-    if rc != 0:
-        _fail(lib, "stac_jpeg_encode", rc)
+                                  _ptr(workspace), workspace.numel() * workspace.element_size(), stream_ptr(rgb.device))
+    check(lib, "stac_jpeg_encode", rc)
 
 
 class JpegEncoder:

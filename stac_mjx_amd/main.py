@@ -8,7 +8,8 @@ from pathlib import Path
 import numpy as np
 
 from . import dist, io, utils
-from .config import compose_config
+from .config import (GATHER_NONE_CONTINUOUS, POSTPROCESS_GPU_MARKER_ORDER, compose_config, fill_missing_options, outlier_options,
+                     postprocess_options, report_options, smooth_options)
 from .stac import Stac
 
 
@@ -45,85 +46,45 @@ def run_stac(cfg, kp_data, kp_names, base_path=None, *, setup=None, device=None)
             f"kp_data has {kp_data.shape[1]} columns but expected {expected_cols} ({len(kp_names)} keypoints x 3). "
             "Ensure kp_data is shaped (n_frames, n_keypoints * 3) and that kp_names length matches the number of "
             "keypoints in kp_data.")
-    reject_mode, reject_args = _reject_outliers_mode(cfg)  # (bad values and hampel without fill_missing: before any work)
-    report_on, report_permille, report_worst = _report_mode(cfg)
-    smooth = _smooth_mode(cfg)  # (bad values, smoothing without postprocess = gpu or with reference_marker_order: before any work)
     start = time.time()
     fit_offsets_path = base_path / cfg.stac.fit_offsets_path
     ik_only_path = base_path / cfg.stac.ik_only_path
-    xml_path = base_path / cfg.model.MJCF_PATH
-    if report_on and not cfg.stac.skip_ik_only and bool(cfg.stac.get("reference_marker_order", False)):
-        # (the config that decides the clip length is the one stored with the fit: the caller's, when this run writes it)
-        fit_cfg = cfg if not cfg.stac.skip_fit_offsets else io.load_stac_data(fit_offsets_path)[0]
-        F_rep = int(fit_cfg.stac.n_frames_per_clip)
-        if F_rep > 1 and kp_data.shape[0] // max(F_rep, 1) > 1:
-            raise ValueError("stac.report = on cannot pair marker_sites with kp_data in the reference's frame-major row order "
-                             "(stac.reference_marker_order: true with more than one clip of more than one frame): the rows of "
-                             "marker_sites are then not the rows of kp_data")
-    if smooth is not None and not cfg.stac.skip_ik_only:
-        # stac.smooth: a clip must hold a whole window -- known as soon as the config that decides the clip length is, the one stored
-        # with the fit (the caller's, when this run writes it)
-        fit_cfg = cfg if not cfg.stac.skip_fit_offsets else io.load_stac_data(fit_offsets_path)[0]
-        _check_smooth_clip(smooth, _smooth_clip_len(fit_cfg, kp_data.shape[0]))
-    stac = Stac(xml_path, cfg, kp_names, setup=setup, device=device)
-    if not cfg.stac.skip_ik_only and dist.world()[1] > 1 and str(cfg.stac.get("gather", "auto") or "auto") == "none":
-        # an EXPLICIT gather = none cannot serve a continuous run (cross-fades reach across shard borders): say so before any
-        # work is done -- the config that decides is the one stored with the fit (the caller's, when this run writes it)
-        fit_cfg = cfg if not cfg.stac.skip_fit_offsets else io.load_stac_data(fit_offsets_path)[0]
-        if fit_cfg.stac.continuous:
-            raise ValueError("stac.gather = none writes per-rank shards, but stac.continuous cross-fades neighbouring "
-                             "clips across shard borders: use gather = rank0 (or all, or auto) for continuous runs")
-
-    # stac.postprocess (engine extension, read from the caller's config like gather): "host" (default) = the numpy functions
-    # of utils.py below; "gpu" = ik_only stitches and infers qvel on the device (post.py) and the two host steps are skipped
-    post_gpu = _postprocess_mode(cfg) == "gpu"
-    if post_gpu and not cfg.stac.skip_ik_only and bool(cfg.stac.get("reference_marker_order", False)):
-        fit_cfg = cfg if not cfg.stac.skip_fit_offsets else io.load_stac_data(fit_offsets_path)[0]
-        if fit_cfg.stac.continuous:
-            raise ValueError("stac.postprocess = gpu cannot cross-fade marker_sites in the reference's frame-major row order "
-                             "(stac.reference_marker_order: true): only postprocess = host reproduces fading across it")
-
-    # stac.fill_missing (engine extension, read from the caller's config): "off" (default) = kp_data goes to the fit as it came;
-    # "linear" / "hold" = the WHOLE series is filled once, here, on the GPU (every rank fills it itself: same bits), so a missing
-    # run that crosses n_fit_frames or a clip border is filled from its true neighbours, and both phases see the filled array
-    # stac.reject_outliers (engine extension, caller's config; needs fill_missing): "hampel" = the whole series goes through the
-    # Hampel identifier once, immediately before the fill (every rank itself: same bits); a rejected keypoint is three NaN, which
-    # the fill closes like any missing one, so kp_gap > 0 there with no further code
-    kp_gap = kp_rejected = None
-    fill_mode = _fill_missing_mode(cfg)
-    if reject_mode != "off":
-        kp_data, kp_rejected = stac.reject_outliers(kp_data, **reject_args)
-    if fill_mode != "off":
-        kp_data, kp_gap = stac.fill_missing(kp_data, fill_mode)
-        n_fit = min(int(cfg.stac.n_fit_frames), kp_gap.shape[0])
-        if not cfg.stac.skip_fit_offsets and n_fit > 0:  # (the offset phase fits filled positions like observed ones: DESIGN.md §10)
-            print(f"fill_missing: {100.0 * np.count_nonzero(kp_gap[:n_fit]) / kp_gap[:n_fit].size:.3f} % of the keypoints of the "
-                  f"{n_fit} fit frames are filled values")
-            if kp_rejected is not None:
-                print(f"reject_outliers: {100.0 * np.count_nonzero(kp_rejected[:n_fit]) / kp_rejected[:n_fit].size:.3f} % of the "
-                      f"keypoints of the {n_fit} fit frames were rejected as outliers (and are among the filled ones)")
-
+    pre = _Preflight(cfg, kp_data.shape[0], fit_offsets_path)
+    pre.check_config()
+    stac = Stac(base_path / cfg.model.MJCF_PATH, cfg, kp_names, setup=setup, device=device)
+    pre.check_run(dist.world()[1])
+    series = _prepare_series(stac, cfg, kp_data, pre)
     if not cfg.stac.skip_fit_offsets:
-        kps = kp_data[: cfg.stac.n_fit_frames]
-        print(f"Running fit. Mocap data shape: {kps.shape}")
-        fit_data = stac.fit_offsets(kps)
-        if kp_gap is not None:  # (the rows of the fit file are the first rows of the series, in order)
-            fit_data.kp_gap = kp_gap[: fit_data.kp_data.shape[0]]
-        if kp_rejected is not None:
-            fit_data.kp_rejected = kp_rejected[: fit_data.kp_data.shape[0]]
-        if dist.world()[0] == 0:  # multi-GPU: rank 0 holds the gathered result and writes it
-            if report_on:
-                _write_report(stac, fit_data, fit_offsets_path, report_permille, report_worst)
-            io.save_data_to_h5(config=cfg, file_path=fit_offsets_path, **fit_data.as_dict())
-        fit_offsets_path = io.resolve_output_path(fit_offsets_path)
-        dist.barrier()
-        print(f"saved fit to {fit_offsets_path}", flush=True)
+        fit_offsets_path = _run_fit(stac, cfg, series, fit_offsets_path, pre.report)
     else:
         print("Skipping fit_offsets. To change this behavior, set cfg.stac.skip_fit_offsets to False.")
-
     if cfg.stac.skip_ik_only:
         print("Skipping IK-only phase. To change this behavior, set cfg.stac.skip_ik_only to False.")
         return fit_offsets_path, None
+    return _run_ik(stac, series, fit_offsets_path, ik_only_path, pre, start)
+
+
+def _run_fit(stac, cfg, series, fit_offsets_path, report) -> Path:
+    """``fit_offsets`` on the first ``n_fit_frames`` of the series and the fit file -> the name the file really has."""
+    kp_data, kp_gap, kp_rejected = series
+    kps = kp_data[: cfg.stac.n_fit_frames]
+    print(f"Running fit. Mocap data shape: {kps.shape}")
+    fit_data = stac.fit_offsets(kps)
+    if kp_gap is not None:  # (the rows of the fit file are the first rows of the series, in order)
+        fit_data.kp_gap = kp_gap[: fit_data.kp_data.shape[0]]
+    if kp_rejected is not None:
+        fit_data.kp_rejected = kp_rejected[: fit_data.kp_data.shape[0]]
+    # multi-GPU: rank 0 holds the gathered result and writes it
+    fit_offsets_path = _write_result(stac, cfg, fit_data, fit_offsets_path, report, dist.world()[0] == 0)
+    print(f"saved fit to {fit_offsets_path}", flush=True)
+    return fit_offsets_path
+
+
+def _run_ik(stac, series, fit_offsets_path, ik_only_path, pre, start):
+    """``ik_only`` on the whole series with the offsets of the fit file, the host post-processing and the result file(s) -> what
+    ``run_stac`` returns."""
+    kp_data, kp_gap, kp_rejected = series
+    cfg = pre.cfg  # the caller's, until the fit file is read back
     if kp_data.shape[0] % cfg.stac.n_frames_per_clip != 0:
         raise ValueError(
             f"n_frames_per_clip ({cfg.stac.n_frames_per_clip}) must divide evenly with the total number of mocap "
@@ -135,18 +96,18 @@ def run_stac(cfg, kp_data, kp_names, base_path=None, *, setup=None, device=None)
     cfg, fit_data = io.load_stac_data(fit_offsets_path)
     rank, world_size = dist.world()
     F = int(cfg.stac.n_frames_per_clip)
+    n_clips = kp_data.shape[0] // F
     # where the results go: resolved here (an "auto" becomes rank0 / none by output size; a continuous run always gathers) and
     # handed to ik_only as an argument -- the caller's config object is not touched
     mode = _ik_output_mode(stac.cfg, kp_data.shape[0], stac, continuous=bool(cfg.stac.continuous)) if world_size > 1 else "rank0"
     sharded = world_size > 1 and mode == "none"
     if sharded and cfg.stac.continuous:  # (explicit gather = none with a fit file whose config turned out continuous)
-        raise ValueError("stac.gather = none writes per-rank shards, but stac.continuous cross-fades neighbouring "
-                         "clips across shard borders: use gather = rank0 (or all, or auto) for continuous runs")
-    post = {"continuous": bool(cfg.stac.continuous), "n_frames_per_clip": F, "infer_qvels": bool(cfg.stac.infer_qvels)} if post_gpu else None
-    if smooth is not None:  # (postprocess = gpu: _smooth_mode)
-        _check_smooth_clip(smooth, _smooth_clip_len(cfg, kp_data.shape[0]))
-        post["smooth"] = smooth
-    ik_data = stac.ik_only(kp_data, fit_data.offsets, gather=mode, **({"post": post} if post_gpu else {}))
+        raise ValueError(GATHER_NONE_CONTINUOUS)
+    post = {"continuous": bool(cfg.stac.continuous), "n_frames_per_clip": F, "infer_qvels": bool(cfg.stac.infer_qvels)} if pre.post_gpu else None
+    if pre.smooth is not None:  # (postprocess = gpu: _smooth_mode)
+        _check_smooth_clip(pre.smooth, _smooth_clip_len(cfg, kp_data.shape[0]))
+        post["smooth"] = pre.smooth
+    ik_data = stac.ik_only(kp_data, fit_data.offsets, gather=mode, **({"post": post} if pre.post_gpu else {}))
     if rank != 0 and not sharded and mode != "all":
         dist.barrier()  # this rank holds its own shard only: rank 0 post-processes and writes the gathered result
         return fit_offsets_path, io.resolve_output_path(ik_only_path)
@@ -157,36 +118,105 @@ def run_stac(cfg, kp_data, kp_names, base_path=None, *, setup=None, device=None)
         batched = ik_data.qpos.reshape((-1, F, ik_data.qpos.shape[-1]))
         qvels = [utils.compute_velocity_from_kinematics(c, dt=stac._timestep, freejoint=stac._freejoint) for c in batched]
         ik_data.qvel = np.stack(qvels).reshape(-1, qvels[0].shape[-1])
+    lo, hi = dist.shard_range(n_clips) if sharded else (0, n_clips)
     if kp_gap is not None:  # rows of the input series, not passed through the cross-fade; a shard file carries the rows of its clips
-        lo, hi = dist.shard_range(kp_data.shape[0] // F) if sharded else (0, kp_data.shape[0] // F)
         ik_data.kp_gap = kp_gap[lo * F:hi * F]
         if kp_rejected is not None:  # (handled exactly like kp_gap)
             ik_data.kp_rejected = kp_rejected[lo * F:hi * F]
     if sharded:
-        # every rank writes ITS clips under a shard name (never a partial result under the full-run name); rank 0 adds
-        # the manifest that io.load_sharded_stac_data() reads the run back through
-        n_clips = kp_data.shape[0] // F
-        lo, hi = dist.shard_range(n_clips)
-        shard = io.shard_path(ik_only_path, rank, world_size)
-        if report_on:  # (of this rank's clips; shard reports are not merged)
-            _write_report(stac, ik_data, shard, report_permille, report_worst)
-        io.save_data_to_h5(config=cfg, file_path=shard, **ik_data.as_dict())
-        dist.barrier()
+        # every rank writes ITS clips under a shard name (never a partial result under the full-run name; its report is of these
+        # clips, shard reports are not merged); rank 0 adds the manifest that io.load_stac_result() reads the run back through
+        shard = _write_result(stac, cfg, ik_data, io.shard_path(ik_only_path, rank, world_size), pre.report, True)
         manifest = io.manifest_path(ik_only_path)
         if rank == 0:
             io.write_manifest(manifest, ik_only_path, world_size, n_clips, F)
         dist.barrier()
-        print(f"Saved ik_only shard {io.resolve_output_path(shard)} (clips {lo}:{hi}); manifest {manifest}. "
+        print(f"Saved ik_only shard {shard} (clips {lo}:{hi}); manifest {manifest}. "
               f"Finished in {(time.time() - start) / 60:.2f} minutes")
         return fit_offsets_path, manifest
-    if rank == 0:
-        if report_on:
-            _write_report(stac, ik_data, ik_only_path, report_permille, report_worst)
-        io.save_data_to_h5(config=cfg, file_path=ik_only_path, **ik_data.as_dict())
-    ik_only_path = io.resolve_output_path(ik_only_path)
-    dist.barrier()
+    ik_only_path = _write_result(stac, cfg, ik_data, ik_only_path, pre.report, rank == 0)
     print(f"Saved ik_only to {ik_only_path}. Finished in {(time.time() - start) / 60:.2f} minutes")
     return fit_offsets_path, ik_only_path
+
+
+class _Preflight:
+    """What ``run_stac`` reads from the caller's config and refuses before any work is done.  Several refusals depend on the config
+    stored with the fit (it decides the clip length and ``continuous`` of the ik_only run): ``fit_cfg`` is the caller's when this run
+    writes the fit, else it is read from the fit file, once, and only if a refusal asks for it."""
+
+    def __init__(self, cfg, n_frames: int, fit_offsets_path):
+        self.cfg, self.n_frames, self.fit_offsets_path = cfg, int(n_frames), fit_offsets_path
+        self._fit_cfg = None
+
+    @property
+    def fit_cfg(self):
+        if self._fit_cfg is None:
+            self._fit_cfg = self.cfg if not self.cfg.stac.skip_fit_offsets else io.load_stac_data(self.fit_offsets_path)[0]
+        return self._fit_cfg
+
+    def check_config(self):
+        """What needs no model (bad values, hampel without fill_missing, smoothing without postprocess = gpu or with
+        reference_marker_order, ...): refused before a ``Stac`` is built."""
+        stac = self.cfg.stac
+        self.reject_mode, self.reject_args = _reject_outliers_mode(self.cfg)
+        self.report = _report_mode(self.cfg)
+        self.smooth = _smooth_mode(self.cfg)
+        self.marker_order = not stac.skip_ik_only and bool(stac.get("reference_marker_order", False))
+        if self.report[0] and self.marker_order:
+            F = int(self.fit_cfg.stac.n_frames_per_clip)
+            if F > 1 and self.n_frames // max(F, 1) > 1:
+                raise ValueError("stac.report = on cannot pair marker_sites with kp_data in the reference's frame-major row order "
+                                 "(stac.reference_marker_order: true with more than one clip of more than one frame): the rows of "
+                                 "marker_sites are then not the rows of kp_data")
+        if self.smooth is not None and not stac.skip_ik_only:  # stac.smooth: a clip must hold a whole window
+            _check_smooth_clip(self.smooth, _smooth_clip_len(self.fit_cfg, self.n_frames))
+
+    def check_run(self, world_size: int):
+        """What today follows the construction of the ``Stac``, in that order."""
+        stac = self.cfg.stac
+        if not stac.skip_ik_only and world_size > 1 and str(stac.get("gather", "auto") or "auto") == "none":
+            # an EXPLICIT gather = none cannot serve a continuous run (cross-fades reach across shard borders)
+            if self.fit_cfg.stac.continuous:
+                raise ValueError(GATHER_NONE_CONTINUOUS)
+        # stac.postprocess (engine extension, read from the caller's config like gather): "host" (default) = the numpy functions
+        # of utils.py; "gpu" = ik_only stitches and infers qvel on the device (post.py) and the two host steps are skipped
+        self.post_gpu = _postprocess_mode(self.cfg) == "gpu"
+        if self.post_gpu and self.marker_order and self.fit_cfg.stac.continuous:
+            raise ValueError(POSTPROCESS_GPU_MARKER_ORDER)
+        self.fill_mode = _fill_missing_mode(self.cfg)
+
+
+def _prepare_series(stac, cfg, kp_data, pre):
+    """``stac.reject_outliers`` then ``stac.fill_missing`` over the WHOLE series, once, on the GPU (every rank itself: same bits)
+    -> (kp_data, kp_gap or None, kp_rejected or None).  A missing run that crosses n_fit_frames or a clip border is so filled from
+    its true neighbours, and both phases see the filled array.  A rejected keypoint is three NaN, which the fill closes like any
+    missing one, so kp_gap > 0 there with no further code."""
+    kp_gap = kp_rejected = None
+    if pre.reject_mode != "off":
+        kp_data, kp_rejected = stac.reject_outliers(kp_data, **pre.reject_args)
+    if pre.fill_mode != "off":
+        kp_data, kp_gap = stac.fill_missing(kp_data, pre.fill_mode)
+        n_fit = min(int(cfg.stac.n_fit_frames), kp_gap.shape[0])
+        if not cfg.stac.skip_fit_offsets and n_fit > 0:  # (the offset phase fits filled positions like observed ones: DESIGN.md §10)
+            print(f"fill_missing: {100.0 * np.count_nonzero(kp_gap[:n_fit]) / kp_gap[:n_fit].size:.3f} % of the keypoints of the "
+                  f"{n_fit} fit frames are filled values")
+            if kp_rejected is not None:
+                print(f"reject_outliers: {100.0 * np.count_nonzero(kp_rejected[:n_fit]) / kp_rejected[:n_fit].size:.3f} % of the "
+                      f"keypoints of the {n_fit} fit frames were rejected as outliers (and are among the filled ones)")
+    return kp_data, kp_gap, kp_rejected
+
+
+def _write_result(stac, cfg, data, path, report, writes: bool) -> Path:
+    """The tail of a phase: the rank that ``writes`` adds the report (``stac.report: on``) and saves ``data``; every rank gets the
+    name the file really has, once it is there."""
+    on, permille, worst = report
+    if writes:
+        if on:
+            _write_report(stac, data, path, permille, worst)
+        io.save_data_to_h5(config=cfg, file_path=path, **data.as_dict())
+    path = io.resolve_output_path(path)
+    dist.barrier()
+    return path
 
 
 def report_path(result_path) -> Path:
@@ -198,8 +228,6 @@ def report_path(result_path) -> Path:
 def _report_mode(cfg) -> tuple:
     """``stac.report``: "off" (default) | "on" -> (on, permille values of ``stac.report_quantiles``, ``stac.report_worst``).
     ``ValueError`` for a bad value of any of the three keys."""
-    from .config import report_options
-
     return report_options(cfg.stac)
 
 
@@ -224,8 +252,6 @@ def _smooth_mode(cfg):
     """``stac.smooth``: "off" (default) | "savgol" | "gaussian" -> None, or the options of ``config.smooth_options`` as the
     ``post["smooth"]`` of ``Stac.ik_only`` takes them.  ``ValueError`` for a bad value of any of the four keys, and for smoothing
     without ``postprocess: gpu`` or with ``reference_marker_order: true``."""
-    from .config import smooth_options
-
     opt = smooth_options(cfg.stac)
     return None if opt["kind"] == "off" else opt
 
@@ -249,27 +275,18 @@ def _check_smooth_clip(smooth, clip_len: int):
 
 def _postprocess_mode(cfg) -> str:
     """``stac.postprocess``: "host" (default) | "gpu"."""
-    mode = str(cfg.stac.get("postprocess", "host") or "host")
-    if mode not in ("host", "gpu"):
-        raise ValueError(f"stac.postprocess must be host or gpu, not {mode!r}")
-    return mode
+    return postprocess_options(cfg.stac)
 
 
 def _fill_missing_mode(cfg) -> str:
     """``stac.fill_missing``: "off" (default) | "linear" | "hold"."""
-    mode = cfg.stac.get("fill_missing", "off")
-    mode = "off" if mode in (None, False) else mode
-    if mode not in ("off", "linear", "hold"):
-        raise ValueError(f"stac.fill_missing must be off, linear or hold, not {mode!r}")
-    return mode
+    return fill_missing_options(cfg.stac)
 
 
 def _reject_outliers_mode(cfg) -> tuple:
     """``stac.reject_outliers``: "off" (default) | "hampel" -> (mode, keyword arguments of ``Stac.reject_outliers`` from
     ``stac.outlier_window`` / ``outlier_nsigma`` / ``outlier_min_dev``).  ``ValueError`` for a bad value of any of the four keys,
     and for ``hampel`` with ``fill_missing`` off: the solver cannot take the NaN of a rejected keypoint."""
-    from .config import outlier_options
-
     mode, h, n_sigma, min_dev = outlier_options(cfg.stac)
     if mode != "off" and _fill_missing_mode(cfg) == "off":
         raise ValueError("stac.reject_outliers = hampel turns outliers into missing keypoints (NaN), which the solver cannot take: "

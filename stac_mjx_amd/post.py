@@ -14,7 +14,9 @@ import ctypes as C
 import numpy as np
 import torch
 
-from .engine import StacHipError, _ptr, load_library
+from .abi import _f32p, _i32p, _ptr, check, device_tensor, stream_ptr
+from .abi import declare as bind  # noqa: F401  (the name callers of the raw library know: the whole table, idempotent)
+from .engine import load_library
 from .utils import CONTINUOUS_BATCH_OVERLAP
 
 MAX_OVERLAP = 32  # csrc/stac_post.hpp: kPostMaxOverlap
@@ -22,24 +24,6 @@ SMOOTH_MAX_HALF = 16  # csrc/stac_smooth.hpp: kSmoothMaxHalf
 SMOOTH_MAX_QUAT = 64  # kSmoothMaxQuat
 SMOOTH_LDS_FLOATS = 16384  # kSmoothLdsFloats
 SMOOTH_MAX_TILE = 128  # kSmoothMaxTile
-
-
-def bind(lib):
-    """Argument types of the post-processing entry points (idempotent)."""
-    vp, i32, i64, f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_double
-    lib.stac_post_stitch_rows.restype = i64
-    lib.stac_post_stitch_rows.argtypes = [i64, i32, i32]
-    lib.stac_post_stitch.restype = i32
-    lib.stac_post_stitch.argtypes = [vp, i64, i32, i32, i32, C.POINTER(f64), vp, i64, vp]
-    lib.stac_post_qvel.restype = i32
-    lib.stac_post_qvel.argtypes = [vp, i64, i32, i32, f64, i32, f64, vp, vp]
-    lib.stac_post_smooth.restype = i32
-    lib.stac_post_smooth.argtypes = [vp, i64, i32, i32, i32, C.POINTER(C.c_float), C.POINTER(i32), i32, vp, vp, vp, vp]
-    return lib
-
-
-def _fail(lib, what, rc):
-    raise StacHipError(f"{what}: libstac_hip error {rc}: {lib.stac_last_error().decode('utf-8', 'replace')}")
 
 
 def crossfade_mask(overlap: int = CONTINUOUS_BATCH_OVERLAP, center: float = 0.5, steepness: float = 10.0) -> np.ndarray:
@@ -50,17 +34,12 @@ def crossfade_mask(overlap: int = CONTINUOUS_BATCH_OVERLAP, center: float = 0.5,
 
 def stitch_rows(n_clips: int, n_frames_per_clip: int, overlap: int = CONTINUOUS_BATCH_OVERLAP) -> int:
     """Rows of the stitched array of ``n_clips`` windows (host only)."""
-    lib = bind(load_library())
-    R = int(lib.stac_post_stitch_rows(int(n_clips), int(n_frames_per_clip), int(overlap)))
-    if R < 0:
-        _fail(lib, "stac_post_stitch_rows", R)
-    return R
+    lib = load_library()
+    return int(check(lib, "stac_post_stitch_rows", lib.stac_post_stitch_rows(int(n_clips), int(n_frames_per_clip), int(overlap))))
 
 
 def _device_f32(x, what):
-    if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        raise ValueError(f"{what} needs a CUDA tensor (the host path is in stac_mjx_amd.utils)")
-    return x.to(dtype=torch.float32).contiguous()
+    return device_tensor(x, f"{what} needs a CUDA tensor (the host path is in stac_mjx_amd.utils)")
 
 
 def stitch(x: torch.Tensor, n_frames_per_clip: int, overlap: int = CONTINUOUS_BATCH_OVERLAP) -> torch.Tensor:
@@ -70,7 +49,7 @@ def stitch(x: torch.Tensor, n_frames_per_clip: int, overlap: int = CONTINUOUS_BA
     F, ov = int(n_frames_per_clip), int(overlap)
     if x.dim() < 2 or x.shape[1] != F + ov:
         raise ValueError(f"stitch: expected [clips, {F + ov}, ...] for n_frames_per_clip = {F} and overlap = {ov}, got {tuple(x.shape)}")
-    lib = bind(load_library())
+    lib = load_library()
     n_clips, trailing = x.shape[0], tuple(x.shape[2:])
     D = int(np.prod(trailing, dtype=np.int64))
     R = stitch_rows(n_clips, F, ov)
@@ -79,10 +58,8 @@ def stitch(x: torch.Tensor, n_frames_per_clip: int, overlap: int = CONTINUOUS_BA
         return out
     m = np.ascontiguousarray(crossfade_mask(ov), dtype=np.float64)
     with torch.cuda.device(x.device):
-        rc = lib.stac_post_stitch(_ptr(x), n_clips, F, ov, D, m.ctypes.data_as(C.POINTER(C.c_double)), _ptr(out), R,
-                                  C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
-    if rc != 0:
-        _fail(lib, "stac_post_stitch", rc)
+        rc = lib.stac_post_stitch(_ptr(x), n_clips, F, ov, D, m.ctypes.data_as(C.POINTER(C.c_double)), _ptr(out), R, stream_ptr(x.device))
+    check(lib, "stac_post_stitch", rc)
     return out
 
 
@@ -99,15 +76,13 @@ def infer_qvel(qpos: torch.Tensor, n_frames_per_clip: int, dt: float, freejoint:
         raise ValueError(f"cannot reshape {N} rows of qpos into clips of {F} frames")
     if freejoint and nq < 7:
         raise ValueError(f"infer_qvel: a free joint needs nq >= 7, got {nq}")
-    lib = bind(load_library())
+    lib = load_library()
     out = torch.empty((N, nq - (1 if freejoint else 0)), dtype=torch.float32, device=qpos.device)
     if N == 0:
         return out
     with torch.cuda.device(qpos.device):
-        rc = lib.stac_post_qvel(_ptr(qpos), N, nq, F, float(dt), 1 if freejoint else 0, float(max_qvel), _ptr(out),
-                                C.c_void_p(torch.cuda.current_stream(qpos.device).cuda_stream))
-    if rc != 0:
-        _fail(lib, "stac_post_qvel", rc)
+        rc = lib.stac_post_qvel(_ptr(qpos), N, nq, F, float(dt), 1 if freejoint else 0, float(max_qvel), _ptr(out), stream_ptr(qpos.device))
+    check(lib, "stac_post_qvel", rc)
     return out
 
 
@@ -205,14 +180,12 @@ def smooth(qpos: torch.Tensor, clip_len: int, taps, quat_cols, lb=None, ub=None)
         if b.numel() != nq:
             raise ValueError(f"smooth: {name} must have {nq} entries, got {b.numel()}")
         bounds.append(b)
-    lib = bind(load_library())
+    lib = load_library()
     out = torch.empty_like(qpos)
     if N == 0:
         return out
     with torch.cuda.device(qpos.device):
-        rc = lib.stac_post_smooth(_ptr(qpos), N, nq, L, W // 2, taps.ctypes.data_as(C.POINTER(C.c_float)),
-                                  cols.ctypes.data_as(C.POINTER(C.c_int32)), int(cols.size), _ptr(bounds[0]), _ptr(bounds[1]), _ptr(out),
-                                  C.c_void_p(torch.cuda.current_stream(qpos.device).cuda_stream))
-    if rc != 0:
-        _fail(lib, "stac_post_smooth", rc)
+        rc = lib.stac_post_smooth(_ptr(qpos), N, nq, L, W // 2, taps.ctypes.data_as(_f32p), cols.ctypes.data_as(_i32p), int(cols.size),
+                                  _ptr(bounds[0]), _ptr(bounds[1]), _ptr(out), stream_ptr(qpos.device))
+    check(lib, "stac_post_smooth", rc)
     return out

@@ -10,34 +10,19 @@ missing run: DESIGN.md "Filling missing keypoints".
 
 from __future__ import annotations
 
-import ctypes as C
 import math
 
 import torch
 
-from .engine import StacHipError, _ptr, load_library
+from .abi import _ptr, check, device_tensor, stream_ptr
+from .abi import declare as bind  # noqa: F401  (the name callers of the raw library know: the whole table, idempotent)
+from .engine import load_library
 
 TILE_FRAMES = 64    # csrc/stac_prep.hpp: kPrepTileFrames (frames of a tile of the staged scan)
 MAX_BLOCKS = 1024   # csrc/stac_prep.hpp: kPrepMaxBlocks (workgroups of a launch: the grid strides over the tiles beyond that)
 MODES = {"linear": 0, "hold": 1}  # include/stac_hip.h: STAC_PREP_LINEAR, STAC_PREP_HOLD
 MAX_HALF_WINDOW = 16  # csrc/stac_outlier.hpp: kOutlierMaxHalf (largest half-width of the outlier window)
 MAD_TO_SIGMA = 1.4826  # the median absolute deviation of a normal distribution is sigma / 1.4826
-
-
-def bind(lib):
-    """Argument types of the entry points (idempotent)."""
-    vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
-    lib.stac_prep_reject.restype = i32
-    lib.stac_prep_reject.argtypes = [vp, i64, i32, i32, C.c_double, C.c_double, vp, vp, vp]
-    lib.stac_prep_fill_workspace.restype = i64
-    lib.stac_prep_fill_workspace.argtypes = [i64, i32]
-    lib.stac_prep_fill.restype = i32
-    lib.stac_prep_fill.argtypes = [vp, i64, i32, i32, vp, vp, vp, i64, vp]
-    return lib
-
-
-def _fail(lib, what, rc):
-    raise StacHipError(f"{what}: libstac_hip error {rc}: {lib.stac_last_error().decode('utf-8', 'replace')}")
 
 
 def mode_code(mode) -> int:
@@ -48,35 +33,28 @@ def mode_code(mode) -> int:
 
 def workspace_bytes(n_frames: int, n_kp: int) -> int:
     """Bytes of device workspace of one ``stac_prep_fill`` call (host only)."""
-    lib = bind(load_library())
-    b = int(lib.stac_prep_fill_workspace(int(n_frames), int(n_kp)))
-    if b < 0:
-        _fail(lib, "stac_prep_fill_workspace", b)
-    return b
+    lib = load_library()
+    return int(check(lib, "stac_prep_fill_workspace", lib.stac_prep_fill_workspace(int(n_frames), int(n_kp))))
 
 
 def fill_missing(kp: torch.Tensor, mode: str = "linear"):
     """Device tensor [T, 3K] -> (filled [T, 3K] float32, gap [T, K] int32), on the current stream of its device.  The input is
     made contiguous float32 first and is never written."""
     code = mode_code(mode)
-    if not isinstance(kp, torch.Tensor) or not kp.is_cuda:
-        raise ValueError("fill_missing needs a CUDA tensor")
+    kp = device_tensor(kp, "fill_missing needs a CUDA tensor")
     if kp.dim() != 2 or kp.shape[1] % 3 != 0 or kp.shape[1] == 0:
         raise ValueError(f"fill_missing: kp must be [frames, 3 * keypoints], got {tuple(kp.shape)}")
-    kp = kp.to(dtype=torch.float32).contiguous()
     T, K = int(kp.shape[0]), int(kp.shape[1]) // 3
     out = torch.empty_like(kp)
     gap = torch.empty((T, K), dtype=torch.int32, device=kp.device)
     if T == 0:
         return out, gap
-    lib = bind(load_library())
+    lib = load_library()
     nbytes = workspace_bytes(T, K)
     work = torch.empty(nbytes // 8, dtype=torch.int64, device=kp.device)
     with torch.cuda.device(kp.device):
-        rc = lib.stac_prep_fill(_ptr(kp), T, K, code, _ptr(out), _ptr(gap), _ptr(work), nbytes,
-                                C.c_void_p(torch.cuda.current_stream(kp.device).cuda_stream))
-    if rc != 0:
-        _fail(lib, "stac_prep_fill", rc)
+        rc = lib.stac_prep_fill(_ptr(kp), T, K, code, _ptr(out), _ptr(gap), _ptr(work), nbytes, stream_ptr(kp.device))
+    check(lib, "stac_prep_fill", rc)
     return out, gap
 
 
@@ -101,22 +79,18 @@ def reject_outliers(kp: torch.Tensor, half_window: int = 5, n_sigma: float = 3.0
     identifier per track and coordinate over the frames t - half_window .. t + half_window; a rejected keypoint leaves as three
     NaN with flag 1, everything else bit for bit.  The input is made contiguous float32 first and is never written."""
     h, thr, floor = outlier_params(half_window, n_sigma, min_dev)
-    if not isinstance(kp, torch.Tensor) or not kp.is_cuda:
-        raise ValueError("reject_outliers needs a CUDA tensor")
+    kp = device_tensor(kp, "reject_outliers needs a CUDA tensor")
     if kp.dim() != 2 or kp.shape[1] % 3 != 0 or kp.shape[1] == 0:
         raise ValueError(f"reject_outliers: kp must be [frames, 3 * keypoints], got {tuple(kp.shape)}")
-    kp = kp.to(dtype=torch.float32).contiguous()
     T, K = int(kp.shape[0]), int(kp.shape[1]) // 3
     out = torch.empty_like(kp)
     flag = torch.empty((T, K), dtype=torch.uint8, device=kp.device)
     if T == 0:
         return out, flag
-    lib = bind(load_library())
+    lib = load_library()
     with torch.cuda.device(kp.device):
-        rc = lib.stac_prep_reject(_ptr(kp), T, K, h, thr, floor, _ptr(out), _ptr(flag),
-                                  C.c_void_p(torch.cuda.current_stream(kp.device).cuda_stream))
-    if rc != 0:
-        _fail(lib, "stac_prep_reject", rc)
+        rc = lib.stac_prep_reject(_ptr(kp), T, K, h, thr, floor, _ptr(out), _ptr(flag), stream_ptr(kp.device))
+    check(lib, "stac_prep_reject", rc)
     return out, flag
 
 

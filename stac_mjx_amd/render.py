@@ -15,7 +15,8 @@ import math
 import numpy as np
 import torch
 
-from .engine import Engine, StacHipError, _f32p, _i32p, _ptr
+from .abi import StacRenderMeshes, StacRenderTables, _f32p, _i32p, _ptr, hip_error
+from .engine import Engine
 from .mjcf import RenderScene
 
 MAX_PRIMS = 512  # include/stac_hip.h: STAC_RENDER_MAX_PRIMS
@@ -28,36 +29,6 @@ SEGMENT_RGBA = (1.0, 0.0, 0.0, 1.0)
 GEOM_GROUPS = (0, 2)  # stac.py:619-625: geomgroup 1 off, 2 on (0 on by default)
 SITE_GROUPS = (0, 1, 2)  # sitegroup 0-2 on, 3 off
 FREE_CAMERA_DISTANCE = 2.0  # free camera: distance = FREE_CAMERA_DISTANCE * spread / tan(fovy / 2)
-
-
-class StacRenderTables(C.Structure):
-    _fields_ = [
-        ("nprim", C.c_int32), ("prim_type", _i32p), ("prim_body", _i32p), ("prim_flags", _i32p),
-        ("prim_size", _f32p), ("prim_pos", _f32p), ("prim_quat", _f32p), ("prim_rgba", _f32p), ("prim_rgb2", _f32p),
-        ("prim_texrepeat", _f32p), ("nkp", C.c_int32), ("kp_rgba", _f32p),
-        ("marker_rgba", C.c_float * 4), ("segment_rgba", C.c_float * 4), ("marker_radius", C.c_float),
-        ("segment_radius", C.c_float), ("nlight", C.c_int32), ("light_dir", _f32p), ("light_diffuse", _f32p),
-        ("head_ambient", C.c_float * 3), ("head_diffuse", C.c_float * 3), ("alpha", C.c_float), ("background", C.c_float * 3),
-    ]  # fmt: skip
-
-
-class StacRenderMeshes(C.Structure):
-    _fields_ = [
-        ("nmesh", C.c_int32), ("node_offset", _i32p), ("tri_offset", _i32p), ("node_box", _f32p), ("node_link", _i32p),
-        ("tri_vertex", _f32p), ("prim_mesh", _i32p),
-    ]  # fmt: skip
-
-
-def bind(lib):
-    """Argument types of the render entry points (idempotent)."""
-    vp = C.c_void_p
-    lib.stac_render_scene_create.restype = vp
-    lib.stac_render_scene_create.argtypes = [vp, C.POINTER(StacRenderTables)]
-    lib.stac_render_scene_create_with_meshes.restype = vp
-    lib.stac_render_scene_create_with_meshes.argtypes = [vp, C.POINTER(StacRenderTables), C.POINTER(StacRenderMeshes)]
-    lib.stac_render_scene_destroy.argtypes = [vp]
-    lib.stac_render.argtypes = [vp, C.c_int32, vp, vp, vp, vp, C.c_int32, vp, C.c_float, C.c_int32, C.c_int32, vp, vp, vp, vp]
-    lib.stac_render.restype = C.c_int32
 
 
 def render_tables(scene: RenderScene, kp_rgba, marker_size: float, geom_groups=None) -> dict:
@@ -139,7 +110,6 @@ class RenderSceneHandle:
 
     def __init__(self, engine: Engine, tables: dict):
         self.engine, self.lib = engine, engine.lib
-        bind(self.lib)
         self.tables = tables
         self.P, self.K = len(tables["prim_type"]), len(tables["kp_rgba"])
         if tables.get("meshes") is not None:  # triangles and hierarchies go to device memory once, here
@@ -149,7 +119,7 @@ class RenderSceneHandle:
             self._h = self.lib.stac_render_scene_create(C.c_void_p(engine._h), C.byref(_ctables(tables)))
         if not self._h:
             self.code = int(self.lib.stac_last_error_code())
-            raise StacHipError(f"stac_render_scene_create failed: libstac_hip error {self.code}: {engine._err()}")
+            raise hip_error(self.lib, "stac_render_scene_create failed", self.code)
 
     def render(self, xpos, xquat, kp, markers, show_error, cam, tan_half_fovy, width, height, rgb=None, seg=None, depth=None):
         """Raw ``stac_render`` on device tensors (outputs preallocated by the caller, each may be None)."""

@@ -16,7 +16,10 @@ import math
 import numpy as np
 import torch
 
-from .engine import StacHipError, load_library
+from .abi import StacReportParams as Params  # include/stac_hip.h: stac_report_params
+from .abi import check, device_tensor
+from .abi import declare as bind  # noqa: F401  (the name callers of the raw library know: the whole table, idempotent)
+from .engine import load_library
 
 TILE_FRAMES = 64    # csrc/stac_report.hpp: kReportTileFrames (frames of a tile of the first pass)
 MAX_BLOCKS = 1024   # csrc/stac_report.hpp: kReportMaxBlocks (workgroups of a launch: the grid strides over the work beyond that)
@@ -25,29 +28,6 @@ MAX_QUANT = 8       # csrc/stac_report.hpp: kReportMaxQuant
 HIST_BINS = 1024    # csrc/stac_report.hpp: kReportBins0 (bins of `hist`: bits >> 21)
 DEFAULT_PERMILLE = (500, 900, 990)
 NAN_BITS = 0x7FC00000
-
-
-class Params(C.Structure):
-    """include/stac_hip.h: stac_report_params"""
-
-    _fields_ = [("markers", C.c_void_p), ("kp", C.c_void_p), ("gap", C.c_void_p), ("n_frames", C.c_int64), ("n_kp", C.c_int32),
-                ("n_quant", C.c_int32), ("permille", C.POINTER(C.c_int32)), ("sqerr", C.c_void_p), ("frame_sse", C.c_void_p),
-                ("frame_n", C.c_void_p), ("count", C.c_void_p), ("sum", C.c_void_p), ("max", C.c_void_p), ("argmax", C.c_void_p),
-                ("hist", C.c_void_p), ("quant", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
-                ("stream", C.c_void_p)]
-
-
-def bind(lib):
-    """Argument types of the entry points (idempotent)."""
-    lib.stac_report_workspace.restype = C.c_int64
-    lib.stac_report_workspace.argtypes = [C.c_int64, C.c_int32, C.c_int32]
-    lib.stac_report_errors.restype = C.c_int32
-    lib.stac_report_errors.argtypes = [C.POINTER(Params)]
-    return lib
-
-
-def _fail(lib, what, rc):
-    raise StacHipError(f"{what}: libstac_hip error {rc}: {lib.stac_last_error().decode('utf-8', 'replace')}")
 
 
 def workspace_formula(n_frames: int, n_kp: int, n_quant: int) -> int:
@@ -59,11 +39,8 @@ def workspace_formula(n_frames: int, n_kp: int, n_quant: int) -> int:
 
 def workspace_bytes(n_frames: int, n_kp: int, n_quant: int) -> int:
     """Bytes of device workspace of one ``stac_report_errors`` call (host only)."""
-    lib = bind(load_library())
-    b = int(lib.stac_report_workspace(int(n_frames), int(n_kp), int(n_quant)))
-    if b < 0:
-        _fail(lib, "stac_report_workspace", b)
-    return b
+    lib = load_library()
+    return int(check(lib, "stac_report_workspace", lib.stac_report_workspace(int(n_frames), int(n_kp), int(n_quant))))
 
 
 def check_permille(permille) -> tuple:
@@ -87,9 +64,9 @@ def fit_errors(markers: torch.Tensor, kp: torch.Tensor, gap: torch.Tensor | None
     are never written."""
     perm = check_permille(permille)
     Q = len(perm)
-    for name, t in (("markers", markers), ("kp", kp)) + ((("gap", gap),) if gap is not None else ()):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise ValueError(f"fit_errors needs CUDA tensors ({name} is not one)")
+    markers = device_tensor(markers, "fit_errors needs CUDA tensors (markers is not one)")
+    kp = device_tensor(kp, "fit_errors needs CUDA tensors (kp is not one)")
+    gap = device_tensor(gap, "fit_errors needs CUDA tensors (gap is not one)", torch.int32) if gap is not None else None
     if markers.dim() != 3 or markers.shape[2] != 3 or markers.shape[1] == 0:
         raise ValueError(f"fit_errors: markers must be [frames, keypoints, 3], got {tuple(markers.shape)}")
     N, K = int(markers.shape[0]), int(markers.shape[1])
@@ -100,9 +77,6 @@ def fit_errors(markers: torch.Tensor, kp: torch.Tensor, gap: torch.Tensor | None
     dev = markers.device
     if kp.device != dev or (gap is not None and gap.device != dev):
         raise ValueError("fit_errors: markers, kp and gap must be on one device")
-    markers = markers.to(dtype=torch.float32).contiguous()
-    kp = kp.to(dtype=torch.float32).contiguous()
-    gap = gap.to(dtype=torch.int32).contiguous() if gap is not None else None
     new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)  # noqa: E731
     out = {"sqerr": new((N, K), torch.float32), "frame_sse": new((N,), torch.float64), "frame_n": new((N,), torch.int32),
            "count": new((K,), torch.int64), "sum": new((K,), torch.float64), "max": new((K,), torch.float32),
@@ -115,7 +89,7 @@ def fit_errors(markers: torch.Tensor, kp: torch.Tensor, gap: torch.Tensor | None
         out["max"].fill_(float("nan"))
         out["quant"].fill_(float("nan"))
         return out
-    lib = bind(load_library())
+    lib = load_library()
     nbytes = workspace_bytes(N, K, Q)
     work = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
     host_perm = (C.c_int32 * Q)(*perm)
@@ -124,8 +98,7 @@ def fit_errors(markers: torch.Tensor, kp: torch.Tensor, gap: torch.Tensor | None
                    n_quant=Q, permille=host_perm, workspace=work.data_ptr(), workspace_bytes=nbytes,
                    stream=torch.cuda.current_stream(dev).cuda_stream, **{k: v.data_ptr() for k, v in out.items()})
         rc = lib.stac_report_errors(C.byref(p))
-    if rc != 0:
-        _fail(lib, "stac_report_errors", rc)
+    check(lib, "stac_report_errors", rc)
     return out
 
 

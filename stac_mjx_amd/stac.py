@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import dist, prng, utils
+from .config import GATHER_NONE_CONTINUOUS, POSTPROCESS_GPU_MARKER_ORDER, report_options, smooth_marker_order_refusal
 from .engine import Engine
 from .fit_model import FitSetup, build_fit_setup
 from .io import StacData
@@ -74,6 +75,15 @@ class Stac:
             root_dims=s.root_dims, do_root_opt=do_root_opt, q_init=q_init, want_bodies=want_outputs,
             want_markers=want_outputs)
 
+    def _series_to_device(self, kp_data, what):
+        """The whole series ``kp_data`` [T, 3K] as a float32 tensor on the engine's device."""
+        kp = np.asarray(kp_data, dtype=np.float32)
+        if kp.ndim != 2 or kp.shape[1] != 3 * len(self._kp_names):
+            raise ValueError(f"{what}: kp_data must be [frames, {3 * len(self._kp_names)}], got {kp.shape}")
+        if not kp.flags.writeable:  # (torch does not wrap a read-only array)
+            kp = kp.copy()
+        return torch.as_tensor(kp).to(self.engine.device)
+
     # -- fill_missing (engine extension; DESIGN.md "Filling missing keypoints") ----------------------------------------
     def fill_missing(self, kp_data, mode=None):
         """Fills the missing keypoints (a NaN or infinite coordinate) of the whole series ``kp_data`` [T, 3K] along time on the
@@ -85,12 +95,8 @@ class Stac:
 
         mode = str(self.cfg.stac.get("fill_missing", "off") or "off") if mode is None else mode
         prep.mode_code(mode)
-        kp = np.asarray(kp_data, dtype=np.float32)
-        if kp.ndim != 2 or kp.shape[1] != 3 * len(self._kp_names):
-            raise ValueError(f"fill_missing: kp_data must be [frames, {3 * len(self._kp_names)}], got {kp.shape}")
-        if not kp.flags.writeable:  # (torch does not wrap a read-only array)
-            kp = kp.copy()
-        filled, gap = prep.fill_missing(torch.as_tensor(kp).to(self.engine.device), mode)
+        kp = self._series_to_device(kp_data, "fill_missing")
+        filled, gap = prep.fill_missing(kp, mode)
         info = prep.summary(gap)
         if info["empty"]:
             raise ValueError("fill_missing: no valid frame at all for keypoint(s) "
@@ -110,12 +116,8 @@ class Stac:
         from . import prep
 
         prep.outlier_params(half_window, n_sigma, min_dev)
-        kp = np.asarray(kp_data, dtype=np.float32)
-        if kp.ndim != 2 or kp.shape[1] != 3 * len(self._kp_names):
-            raise ValueError(f"reject_outliers: kp_data must be [frames, {3 * len(self._kp_names)}], got {kp.shape}")
-        if not kp.flags.writeable:  # (torch does not wrap a read-only array)
-            kp = kp.copy()
-        out, flag = prep.reject_outliers(torch.as_tensor(kp).to(self.engine.device), half_window, n_sigma, min_dev)
+        kp = self._series_to_device(kp_data, "reject_outliers")
+        out, flag = prep.reject_outliers(kp, half_window, n_sigma, min_dev)
         count = flag.sum(dim=0, dtype=torch.int64).cpu().numpy()
         for k in np.flatnonzero(count):
             self._log(f"reject_outliers (hampel, window {half_window}, {n_sigma} sigma): {self._kp_names[k]}: {int(count[k])} of "
@@ -131,14 +133,12 @@ class Stac:
         keypoints out of every statistic.  ``permille`` / ``worst``: None = ``stac.report_quantiles`` / ``stac.report_worst``
         of the config.  One log line per keypoint."""
         from . import io, report
-        from .config import report_options
 
         _, cfg_perm, cfg_worst = report_options(self.cfg.stac)
         permille = report.check_permille(cfg_perm if permille is None else permille)
         worst = cfg_worst if worst is None else worst
         if not isinstance(data, StacData):
-            path = Path(data)
-            data = (io.load_sharded_stac_data(path) if path.name.endswith(".manifest.json") else io.load_stac_data(path))[1]
+            data = io.load_stac_result(data)[1]
         markers = np.asarray(data.marker_sites, dtype=np.float32)
         kp = np.asarray(data.kp_data, dtype=np.float32)
         if markers.ndim != 3 or markers.shape[2] != 3 or kp.ndim != 2 or kp.shape != (markers.shape[0], 3 * markers.shape[1]):
@@ -168,8 +168,7 @@ class Stac:
         taps = gpost.smooth_taps(kind, half_window, order=order, sigma=sigma)
         cfg = self.cfg
         if not isinstance(data, StacData):
-            path = Path(data)
-            cfg, data = io.load_sharded_stac_data(path) if path.name.endswith(".manifest.json") else io.load_stac_data(path)
+            cfg, data = io.load_stac_result(data)
         raw = np.asarray(data.qpos_raw if np.asarray(data.qpos_raw).size else data.qpos, dtype=np.float32)
         nq, K = self.setup.tables.nq, self.setup.tables.nsite
         if raw.ndim != 2 or raw.shape[1] != nq:
@@ -307,18 +306,15 @@ class Stac:
         if out["n_frames_per_clip"] < 1:
             raise ValueError(f"post: n_frames_per_clip = {out['n_frames_per_clip']}")
         if out["continuous"] and bool(self.cfg.stac.get("reference_marker_order", False)):
-            raise ValueError("stac.postprocess = gpu cannot cross-fade marker_sites in the reference's frame-major row order "
-                             "(stac.reference_marker_order: true): only the host path reproduces fading across it")
+            raise ValueError(POSTPROCESS_GPU_MARKER_ORDER)
         if out["continuous"] and dist.world()[1] > 1 and self._gather_mode(gather) == "none":
-            raise ValueError("stac.gather = none keeps per-rank shards, but a continuous run cross-fades neighbouring clips "
-                             "across shard borders: gather (rank0 or all) for continuous runs")
+            raise ValueError(GATHER_NONE_CONTINUOUS)
         if post.get("smooth"):
             from . import post as gpost
 
             sm = dict(post["smooth"])
             if bool(self.cfg.stac.get("reference_marker_order", False)):
-                raise ValueError("stac.smooth recomputes marker_sites from the smoothed qpos row by row, which the reference's "
-                                 "frame-major row order of marker_sites (stac.reference_marker_order: true) cannot hold")
+                raise ValueError(smooth_marker_order_refusal(sm["kind"]))
             # (every bad kind / half_window / order / sigma is a ValueError of smooth_taps)
             out["smooth"] = {"kind": sm["kind"], "half_window": int(sm["half_window"]),
                              "taps": gpost.smooth_taps(sm["kind"], sm["half_window"], order=sm.get("order"), sigma=sm.get("sigma"))}
@@ -414,23 +410,18 @@ class Stac:
         nq, nb, K = self.setup.tables.nq, self.setup.tables.nbody, self.setup.tables.nsite
         if post is not None:  # stac.postprocess = gpu: the arrays are stitched and flat already (_postprocess_gpu)
             host = {k: v.cpu().numpy() for k, v in post.items()}
-            if batched and bool(self.cfg.stac.get("reference_marker_order", False)):  # (never a continuous run: _check_post)
-                ms = res["marker_sites"]
-                host["marker_sites"] = (ms.transpose(0, 1) if ms.dim() == 4 else ms).reshape(-1, K, 3).cpu().numpy()
-            return StacData(offsets=np.asarray(torch.as_tensor(self._offsets).cpu()).reshape(K, 3), names_qpos=self._part_names,
-                            names_xpos=self._body_names, kp_names=self._kp_names, **host)
-        qpos = res["qpos"].reshape(-1, nq).cpu().numpy()
-        xpos = res["xpos"].reshape(-1, nb, 3).cpu().numpy()
-        xquat = res["xquat"].reshape(-1, nb, 4).cpu().numpy()
-        ms = res["marker_sites"]
-        if batched and ms.dim() == 4 and bool(self.cfg.stac.get("reference_marker_order", False)):
-            ms = ms.transpose(0, 1)  # (C, F, K, 3) -> (F, C, K, 3), flattened in C order like stac.py:486
-        markers = ms.reshape(-1, K, 3).cpu().numpy()
-        offsets = np.asarray(torch.as_tensor(self._offsets).cpu()).reshape(K, 3)
-        kp_flat = np.asarray(kp_data).reshape(-1, np.asarray(kp_data).shape[-1])
-        return StacData(qpos=qpos, xpos=xpos, xquat=xquat, marker_sites=markers, offsets=offsets,
-                        names_qpos=self._part_names, names_xpos=self._body_names, kp_data=kp_flat,
-                        kp_names=self._kp_names)
+        else:
+            host = {"qpos": res["qpos"].reshape(-1, nq).cpu().numpy(), "xpos": res["xpos"].reshape(-1, nb, 3).cpu().numpy(),
+                    "xquat": res["xquat"].reshape(-1, nb, 4).cpu().numpy(),
+                    "kp_data": np.asarray(kp_data).reshape(-1, np.asarray(kp_data).shape[-1])}
+        marker_order = batched and bool(self.cfg.stac.get("reference_marker_order", False))
+        if post is None or marker_order:  # (with post never a continuous run: _check_post)
+            ms = res["marker_sites"]
+            if marker_order and ms.dim() == 4:
+                ms = ms.transpose(0, 1)  # (C, F, K, 3) -> (F, C, K, 3), flattened in C order like stac.py:486
+            host["marker_sites"] = ms.reshape(-1, K, 3).cpu().numpy()
+        return StacData(offsets=np.asarray(torch.as_tensor(self._offsets).cpu()).reshape(K, 3), names_qpos=self._part_names,
+                        names_xpos=self._body_names, kp_names=self._kp_names, **host)
 
     # -- render (stac.py:505-658) -------------------------------------------------------------------------------
     def _get_renderer(self, geom_groups=None):

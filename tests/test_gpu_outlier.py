@@ -16,10 +16,9 @@ PATTERN, FLAG_PATTERN, GUARD = -12345.0, 0xEE, 64
 
 
 def _lib():
-    from stac_mjx_amd import prep
     from stac_mjx_amd.engine import load_library
 
-    return prep.bind(load_library())
+    return load_library()
 
 
 def _tile():

@@ -15,10 +15,9 @@ PATTERN = -12345.0
 
 
 def _lib():
-    from stac_mjx_amd import post
     from stac_mjx_amd.engine import load_library
 
-    return post.bind(load_library())
+    return load_library()
 
 
 def _raw_stitch(lib, src, Cn, F, D, dst, rows, stream=None):

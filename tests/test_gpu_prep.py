@@ -15,10 +15,9 @@ PATTERN, GAP_PATTERN, GUARD = -12345.0, -7, 64
 
 
 def _lib():
-    from stac_mjx_amd import prep
     from stac_mjx_amd.engine import load_library
 
-    return prep.bind(load_library())
+    return load_library()
 
 
 def _raw(lib, kp, T, K, mode, out, gap, work, nbytes, stream=None):

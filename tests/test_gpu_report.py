@@ -21,10 +21,9 @@ WORK_PATTERN = 0x7FF8_DEAD_BEEF_0123
 
 
 def _lib():
-    from stac_mjx_amd import report
     from stac_mjx_amd.engine import load_library
 
-    return report.bind(load_library())
+    return load_library()
 
 
 def _tile():

@@ -18,10 +18,9 @@ STAC_ERR_INVALID = -1
 
 
 def _lib():
-    from stac_mjx_amd import post
     from stac_mjx_amd.engine import load_library
 
-    return post.bind(load_library())
+    return load_library()
 
 
 def _raw_smooth(lib, src, L, taps, cols, lb, ub, dst, stream=None):

@@ -13,19 +13,105 @@ from conftest import ROOT
 
 
 # ---- C ABI -----------------------------------------------------------------------------------------------
+_C_CLASSES = ("int32_t", "int64_t", "float", "double", "void")
+
+
+def _c_class(ctype: str) -> str:
+    """A C type of the header as one of: pointer, int32_t, int64_t, float, double, void."""
+    if "*" in ctype:
+        return "pointer"
+    base = ctype.replace("const", " ").split()
+    assert len(base) == 1 and base[0] in _C_CLASSES, ctype
+    return base[0]
+
+
+def _ctypes_class(t) -> str:
+    import ctypes as C
+
+    if t is None:
+        return "void"
+    if t in (C.c_void_p, C.c_char_p) or issubclass(t, C._Pointer):
+        return "pointer"
+    return {C.c_int32: "int32_t", C.c_int64: "int64_t", C.c_float: "float", C.c_double: "double"}[t]
+
+
+def _header_prototypes() -> dict:
+    """Every ``ret stac_name(args);`` of include/stac_hip.h -> name: (class of ret, [class of every argument])."""
+    text = re.sub(r"/\*.*?\*/", " ", (ROOT / "include" / "stac_hip.h").read_text(), flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    text = "\n".join(ln for ln in text.splitlines() if not ln.lstrip().startswith("#"))
+    text = text.replace('extern "C" {', " ")
+    text = re.sub(r"(typedef\s+struct\s+\w+|enum)\s*\{[^}]*\}\s*\w*\s*;", " ", text)  # struct and enum bodies
+    text = re.sub(r"typedef\s+struct\s+\w+\s+\w+\s*;", " ", text)  # opaque handles
+    protos = {}
+    for stmt in text.split(";"):
+        stmt = " ".join(stmt.split())
+        if stmt in ("", "}"):  # (the closing brace of extern "C")
+            continue
+        m = re.fullmatch(r"(.*?)\b(stac_[a-z0-9_]+) ?\((.*)\)", stmt)
+        assert m, f"not a prototype: {stmt!r}"  # nothing of the header is passed over in silence
+        ret, name, args = m.groups()
+        args = [] if args.strip() == "void" else [a.strip() for a in args.split(",")]
+        # an argument is its type followed by its name: what is left without the last identifier is the type
+        protos[name] = (_c_class(ret), [_c_class(re.sub(r"\w+$", "", a)) for a in args])
+    return protos
+
+
 def test_library_exports_every_declared_symbol():
+    """The ONE binding table (abi.PROTOTYPES) against the header: the same names, the same number of arguments, every argument and
+    return value of the same class; and the loaded library carries exactly the table."""
     from stac_mjx_amd.build import build_extension
     from stac_mjx_amd.engine import ABI_SYMBOLS, load_library
+    from stac_mjx_amd import abi
 
     build_extension()
     header = (ROOT / "include" / "stac_hip.h").read_text()
     declared = set(re.findall(r"\b(stac_[a-z0-9_]+)\s*\(", header))
     assert declared == set(ABI_SYMBOLS), declared ^ set(ABI_SYMBOLS)
+    protos = _header_prototypes()
+    assert len(protos) == 31 and set(protos) == declared and ABI_SYMBOLS == tuple(abi.PROTOTYPES)
+    for name, (ret, args) in protos.items():
+        assert name in abi.PROTOTYPES, name
+        restype, argtypes = abi.PROTOTYPES[name]
+        assert len(argtypes) == len(args), name
+        assert [_ctypes_class(t) for t in argtypes] == args, name
+        assert _ctypes_class(restype) == ret, name
+    assert not set(abi.PROTOTYPES) - set(protos)
+    assert [n for n, (r, _) in abi.PROTOTYPES.items() if r is None] == ["stac_model_destroy", "stac_render_scene_destroy"]
     lib = load_library()
     for s in declared:
         assert hasattr(lib, s), s
+        fn = getattr(lib, s)
+        assert fn.restype is abi.PROTOTYPES[s][0] and list(fn.argtypes) == list(abi.PROTOTYPES[s][1]), s
     assert lib.stac_abi_version() == 3
     assert lib.stac_device_count() >= 0
+
+
+def test_ctypes_structures_have_the_compilers_layout(tmp_path):
+    """sizeof, and offsetof / size of every field, of the five structures of the header as the host C compiler lays them out,
+    against the ctypes structures of abi.py.  (A field that the header lacks does not compile.)"""
+    import ctypes as C
+    import shutil
+    import subprocess
+
+    from stac_mjx_amd import abi
+
+    cc = next((c for c in (shutil.which("cc"), shutil.which("gcc"), shutil.which("clang")) if c), None)
+    if cc is None:
+        pytest.skip("no host C compiler")
+    assert sorted(abi.STRUCTS) == ["stac_model_tables", "stac_q_params", "stac_render_meshes", "stac_render_tables", "stac_report_params"]
+    for cname, struct in abi.STRUCTS.items():
+        fields = [f[0] for f in struct._fields_]
+        lines = [f'printf("%zu %zu\\n", offsetof({cname}, {f}), sizeof((({cname} *)0)->{f}));' for f in fields]
+        src = tmp_path / f"{cname}.c"
+        src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "stac_hip.h"\nint main(void) {\n'
+                       f'printf("%zu\\n", sizeof({cname}));\n' + "\n".join(lines) + "\nreturn 0;\n}\n")
+        exe = tmp_path / cname
+        subprocess.run([cc, "-std=c99", f"-I{ROOT / 'include'}", str(src), "-o", str(exe)], check=True, capture_output=True, text=True)
+        out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split("\n")
+        assert int(out[0]) == C.sizeof(struct), cname
+        got = [tuple(int(v) for v in ln.split()) for ln in out[1:] if ln]
+        assert got == [(getattr(struct, f).offset, getattr(struct, f).size) for f in fields], cname
 
 
 def test_engine_fails_loudly_without_gpu(rodent_setup):
@@ -640,6 +726,46 @@ def test_load_library_refuses_a_stale_or_wrong_abi_library(monkeypatch):
     monkeypatch.setattr(engine, "ABI_VERSION", 99)
     with pytest.raises(engine.StacHipError, match="ABI version"):
         engine.load_library()
+
+
+# ---- the pre-flight of run_stac ----------------------------------------------------------------------------------------------
+def test_run_stac_preflight_reads_the_fit_file_once(rodent_cfg, monkeypatch, tmp_path):
+    """Every refusal of run_stac that depends on the config stored with the fit asks the same lazily loaded copy: a
+    ``skip_fit_offsets`` run opens the fit file at most once before its ik_only starts, and a run that writes the fit never does.
+    The configs trip no refusal but need the stored config for each one they can reach (``smooth`` and ``reference_marker_order``
+    exclude each other at config load, hence two)."""
+    from stac_mjx_amd import io
+    from stac_mjx_amd.config import validate_config
+    from stac_mjx_amd.main import _Preflight
+
+    def cfg(**over):
+        stac = dict(fit_offsets_path="fit.h5", ik_only_path="ik.h5", data_path="d.mat", continuous=False, n_fit_frames=4,
+                    skip_fit_offsets=True, skip_ik_only=False, infer_qvels=False, n_frames_per_clip=8,
+                    mujoco=dict(solver="newton", iterations=1, ls_iterations=4), report="on", postprocess="gpu", gather="none")
+        stac.update(over)
+        return validate_config({"model": dict(rodent_cfg), "stac": stac})
+
+    stored = cfg(skip_fit_offsets=False)  # what the fit file holds: one clip of 8 frames, not continuous
+    loads = []
+    monkeypatch.setattr(io, "load_stac_data", lambda path: (loads.append(path), (stored, None))[1])
+    for over in (dict(reference_marker_order=True), dict(smooth="savgol", smooth_window=3)):
+        for skip_fit, most in ((True, 1), (False, 0)):
+            del loads[:]
+            pre = _Preflight(cfg(skip_fit_offsets=skip_fit, **over), 8, tmp_path / "fit.h5")
+            pre.check_config()
+            assert len(loads) == most, (over, skip_fit)  # (each config's first refusal is one of check_config: read by now)
+            pre.check_run(2)  # a world of 2 with gather = none
+            assert len(loads) == most and loads == [tmp_path / "fit.h5"] * most, (over, skip_fit)
+            assert pre.post_gpu and pre.report[0] and pre.fill_mode == "off" and pre.reject_mode == "off"
+            assert (pre.smooth is not None) == ("smooth" in over)
+    # and the stored config is the one that decides: a continuous fit file refuses gather = none, still after one load
+    stored = cfg(skip_fit_offsets=False, continuous=True)
+    del loads[:]
+    pre = _Preflight(cfg(smooth="savgol"), 8, tmp_path / "fit.h5")
+    pre.check_config()
+    with pytest.raises(ValueError, match="gather = none"):
+        pre.check_run(2)
+    assert len(loads) == 1
 
 
 def test_bench_gpus_n_launches_itself_or_says_why_not():

@@ -146,7 +146,7 @@ def test_symbols_and_argument_errors():
     from stac_mjx_amd import jpeg
 
     build_extension()
-    lib = jpeg.bind(load_library())
+    lib = load_library()
     for s in ("stac_jpeg_header", "stac_jpeg_workspace_bytes", "stac_jpeg_encode"):
         assert s in ABI_SYMBOLS and hasattr(lib, s), s
     assert lib.stac_abi_version() == 3

@@ -244,12 +244,11 @@ def test_run_stac_refuses_rejecting_without_filling_before_any_work(tmp_path, ro
 # ---- C ABI and wrapper ------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def lib():
-    from stac_mjx_amd import prep
     from stac_mjx_amd.build import build_extension
     from stac_mjx_amd.engine import load_library
 
     build_extension()
-    return prep.bind(load_library())
+    return load_library()
 
 
 def test_reject_argument_errors_need_no_device(lib):

@@ -19,12 +19,11 @@ STAC_ERR_INVALID = -1
 
 @pytest.fixture(scope="module")
 def lib():
-    from stac_mjx_amd import report
     from stac_mjx_amd.build import build_extension
     from stac_mjx_amd.engine import load_library
 
     build_extension()
-    return report.bind(load_library())
+    return load_library()
 
 
 def _invalid(lib, rc_):

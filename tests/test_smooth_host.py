@@ -354,12 +354,11 @@ def test_cpu_build_equals_restatement(hostlib, name, H):
 # ---- the entry point's argument checks (before the device is touched) -------------------------------------------------------------
 @pytest.fixture(scope="module")
 def lib():
-    from stac_mjx_amd import post
     from stac_mjx_amd.build import build_extension
     from stac_mjx_amd.engine import load_library
 
     build_extension()
-    return post.bind(load_library())
+    return load_library()
 
 
 def _invalid(lib, rc):

@@ -1,6 +1,7 @@
 """The C ABI of ``libstac_hip.so`` (``include/stac_hip.h``) as ctypes sees it: the five structures, ONE table of the 31
 prototypes, ``declare`` that applies the table to a loaded library (``engine.load_library`` does, to whatever it loads), and the
 few helpers every caller of the library shares.  ``tests/test_host.py`` holds the table against the header and the structures against the compiler.
+A second table, ``PAIRWISE_PROTOTYPES``, holds the two functions of ``include/stac_hip_pairwise.h``; ``declare`` applies both.
 """
 
 from __future__ import annotations
@@ -96,6 +97,12 @@ PROTOTYPES = {
     "stac_report_errors": (i32, [P(StacReportParams)]),
 }  # fmt: skip
 ABI_SYMBOLS = tuple(PROTOTYPES)
+# every function include/stac_hip_pairwise.h declares (the second header: it does not count into the ABI version or ABI_SYMBOLS);
+# tests/test_pairwise_host.py holds this table against that header
+PAIRWISE_PROTOTYPES = {
+    "stac_prep_pairwise_workspace": (i64, [i64, i32]),
+    "stac_prep_pairwise": (i32, [vp, i64, i32, f64, f64, i32, vp, vp, vp, vp, vp, vp, i64, vp]),
+}  # fmt: skip
 
 
 class StacHipError(RuntimeError):
@@ -103,8 +110,8 @@ class StacHipError(RuntimeError):
 
 
 def declare(lib):
-    """Declares ``restype`` and ``argtypes`` of every function of the table on ``lib`` (idempotent) -> ``lib``."""
-    for name, (restype, argtypes) in PROTOTYPES.items():
+    """Declares ``restype`` and ``argtypes`` of every function of both tables on ``lib`` (idempotent) -> ``lib``."""
+    for name, (restype, argtypes) in (*PROTOTYPES.items(), *PAIRWISE_PROTOTYPES.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     return lib

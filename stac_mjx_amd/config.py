@@ -35,6 +35,9 @@ _MUJOCO_REQUIRED = ("solver", "iterations", "ls_iterations")
 # fill_missing: off (default) | linear | hold -- missing keypoints are filled along time before the fit, read from the caller's config;
 # reject_outliers: off (default) | hampel, with outlier_window (half-width, 1 .. 16, default 5), outlier_nsigma (default 3.0) and
 # outlier_min_dev (default 0.001, units of kp_data) -- finite but wrong keypoints become missing ones in front of fill_missing;
+# reject_pairwise: off (default) | mad, with pairwise_nsigma (default 6.0), pairwise_min_dev (default 0.002, units of kp_data) and
+# pairwise_votes (default 2) -- keypoints that leave the distributions of their distances to the other keypoints over the whole series
+# become missing ones, in front of reject_outliers and fill_missing;
 # report: off (default) | on, with report_quantiles (1 .. 8 permille values, default [500, 900, 990]) and report_worst (frames listed,
 # default 10) -- a <result file>.report.json next to every result file, read from the caller's config;
 # smooth: off (default) | savgol | gaussian, with smooth_window (half-width H, 1 .. 16, default 3: windows of 2 H + 1 frames),
@@ -43,7 +46,8 @@ _MUJOCO_REQUIRED = ("solver", "iterations", "ls_iterations")
 # xpos / xquat / marker_sites are those of the smoothed pose; needs postprocess = gpu, read from the caller's config)
 _STAC_EXTENSIONS = ("solver", "lanes_per_chain", "device", "time_indices", "fit_frames_per_clip", "reference_marker_order", "gather", "gather_max_bytes", "lm_maxiter", "postprocess", "fill_missing",
                     "reject_outliers", "outlier_window", "outlier_nsigma", "outlier_min_dev", "report", "report_quantiles", "report_worst",
-                    "smooth", "smooth_window", "smooth_order", "smooth_sigma")
+                    "smooth", "smooth_window", "smooth_order", "smooth_sigma",
+                    "reject_pairwise", "pairwise_nsigma", "pairwise_min_dev", "pairwise_votes")
 _MODEL_EXTENSIONS = ("KP_NAMES_LABEL3D_PATH",)
 
 
@@ -99,6 +103,34 @@ def outlier_options(stac) -> tuple:
             raise ConfigError(f"stac.{key} must be a finite number >= 0, not {v!r}")
         vals.append(float(v))
     return mode, h, vals[0], vals[1]
+
+
+PAIRWISE_DEFAULTS = {"pairwise_nsigma": 6.0, "pairwise_min_dev": 0.002, "pairwise_votes": 2}
+# the one text of run_stac's pre-flight and of main._reject_pairwise_mode
+PAIRWISE_NEEDS_FILL = ("stac.reject_pairwise = mad turns the keypoints it rejects into missing ones (NaN), which the solver cannot take: "
+                       "set stac.fill_missing to linear or hold as well")
+
+
+def pairwise_options(stac) -> tuple:
+    """``stac.reject_pairwise`` and its three parameters out of a ``stac`` mapping -> (mode, n_sigma, min_dev, votes), absent keys
+    at their defaults.  ``ConfigError`` for anything else than off | mad (a bare YAML ``off`` arrives as False), a
+    ``pairwise_nsigma`` / ``pairwise_min_dev`` (units of kp_data) that is not a finite number >= 0, or a ``pairwise_votes`` that
+    is not an integer >= 1."""
+    import math
+
+    mode = _switch(stac, "reject_pairwise")
+    if not isinstance(mode, str) or mode not in ("off", "mad"):
+        raise ConfigError(f"stac.reject_pairwise must be off or mad, not {mode!r}")
+    vals = []
+    for key in ("pairwise_nsigma", "pairwise_min_dev"):
+        v = stac.get(key, PAIRWISE_DEFAULTS[key])
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
+            raise ConfigError(f"stac.{key} must be a finite number >= 0, not {v!r}")
+        vals.append(float(v))
+    votes = stac.get("pairwise_votes", PAIRWISE_DEFAULTS["pairwise_votes"])
+    if isinstance(votes, bool) or not isinstance(votes, int) or not 1 <= votes <= 2**31 - 1:
+        raise ConfigError(f"stac.pairwise_votes must be an integer >= 1, not {votes!r}")
+    return mode, vals[0], vals[1], votes
 
 
 REPORT_DEFAULTS = {"report_quantiles": (500, 900, 990), "report_worst": 10}
@@ -306,7 +338,7 @@ def validate_config(cfg: dict) -> ConfigNode:
             raise ConfigError(f"stac.{k} must be a bool")
     postprocess_options(stac)
     for key, options in (("fill_missing", fill_missing_options), ("reject_outliers", outlier_options), ("report", report_options),
-                         ("smooth", smooth_options)):
+                         ("smooth", smooth_options), ("reject_pairwise", pairwise_options)):
         if isinstance(stac.get(key), bool):  # the file that is written with a result says off / on, not the boolean
             stac[key] = _switch(stac, key)
         options(stac)

@@ -47,14 +47,17 @@ class StacData:
     # the smoothed version of; rows as qpos.  Empty without the option, and then not written to the file.  (Pass it by keyword:
     # kp_rejected stays the trailing field.)
     qpos_raw: np.ndarray = field(default_factory=lambda: np.array([]))
+    # engine extension (stac.reject_pairwise): [frames, K] uint8, 1 = the keypoint was rejected by its pairwise distances; with it
+    # kp_rejected is what either detector rejected.  Empty without the option, and then not written to the file.  (By keyword too.)
+    kp_rejected_pairwise: np.ndarray = field(default_factory=lambda: np.array([]))
     # engine extension (stac.reject_outliers): [frames, K] uint8, 1 = the keypoint was rejected as an outlier before the fill (so
     # kp_gap > 0 there); rows as kp_gap.  Empty without the option, and then not written to the file.
     kp_rejected: np.ndarray = field(default_factory=lambda: np.array([]))
 
     def as_dict(self) -> dict:
-        """The fields as ``save_data_to_h5`` takes them (an empty ``kp_gap`` / ``kp_rejected`` / ``qpos_raw`` is left out: the reference's fields alone)."""
+        """The fields as ``save_data_to_h5`` takes them (an empty ``kp_gap`` / ``kp_rejected`` / ``kp_rejected_pairwise`` / ``qpos_raw`` is left out: the reference's fields alone)."""
         d = asdict(self)
-        for name in ("kp_gap", "kp_rejected", "qpos_raw"):
+        for name in ("kp_gap", "kp_rejected", "kp_rejected_pairwise", "qpos_raw"):
             if not np.asarray(d[name]).size:
                 del d[name]
         return d
@@ -356,12 +359,12 @@ def _npz_write_parallel(path, members: dict, pool, level: int = _H5_GZIP_LEVEL) 
 
 
 def save_data_to_h5(config, kp_names, names_qpos, names_xpos, kp_data, marker_sites, offsets, qpos,
-                    xpos, xquat, qvel, file_path, kp_gap=None, kp_rejected=None, qpos_raw=None) -> Path:  # fmt: skip
+                    xpos, xquat, qvel, file_path, kp_gap=None, kp_rejected=None, qpos_raw=None, kp_rejected_pairwise=None) -> Path:  # fmt: skip
     """Write the reference's output contract (io.py:194-237).  Returns the path actually written.  Same datasets, dtypes
     and gzip filter as the reference; the deflate work of the large arrays runs on every host core (see above).  A non-empty
     ``kp_gap`` (engine extension, ``stac.fill_missing``) adds one dataset of that name, a non-empty ``kp_rejected``
-    (``stac.reject_outliers``) another, a non-empty ``qpos_raw`` (``stac.smooth``) a third; without them the file holds the
-    reference's."""
+    (``stac.reject_outliers``) another, a non-empty ``qpos_raw`` (``stac.smooth``) a third, a non-empty ``kp_rejected_pairwise``
+    (``stac.reject_pairwise``) a fourth; without them the file holds the reference's."""
     file_path = Path(file_path)
     cfg_yaml = config.to_yaml() if isinstance(config, ConfigNode) else yaml.safe_dump(config, sort_keys=False)
     arrays = dict(kp_data=kp_data, marker_sites=marker_sites, offsets=offsets, qpos=qpos,
@@ -372,6 +375,8 @@ def save_data_to_h5(config, kp_names, names_qpos, names_xpos, kp_data, marker_si
         arrays["kp_rejected"] = np.asarray(kp_rejected, dtype=np.uint8)
     if qpos_raw is not None and np.asarray(qpos_raw).size:
         arrays["qpos_raw"] = np.asarray(qpos_raw)
+    if kp_rejected_pairwise is not None and np.asarray(kp_rejected_pairwise).size:
+        arrays["kp_rejected_pairwise"] = np.asarray(kp_rejected_pairwise, dtype=np.uint8)
     if h5py is not None and file_path.suffix in (".h5", ".hdf5"):
         with h5py.File(file_path, "w") as f, _pool() as pool:
             f.create_dataset("config", data=np.bytes_(cfg_yaml))
@@ -418,7 +423,8 @@ def load_stac_data(file_path):
         kp_data=d["kp_data"], marker_sites=d["marker_sites"], offsets=d["offsets"], qpos=d["qpos"],
         qvel=d["qvel"], xpos=d["xpos"], xquat=d["xquat"], kp_gap=d["kp_gap"] if "kp_gap" in d else np.array([]),
         kp_rejected=d["kp_rejected"] if "kp_rejected" in d else np.array([]),
-        qpos_raw=d["qpos_raw"] if "qpos_raw" in d else np.array([]))  # fmt: skip
+        qpos_raw=d["qpos_raw"] if "qpos_raw" in d else np.array([]),
+        kp_rejected_pairwise=d["kp_rejected_pairwise"] if "kp_rejected_pairwise" in d else np.array([]))  # fmt: skip
 
 
 # ---- per-rank shard files of a multi-GPU ik_only run (engine extension; main.run_stac with stac.gather = none / auto) ----
@@ -468,7 +474,8 @@ def load_sharded_stac_data(manifest):
     return cfg, StacData(qpos=cat("qpos"), xpos=cat("xpos"), xquat=cat("xquat"), marker_sites=cat("marker_sites"),
                          offsets=first.offsets, kp_data=cat("kp_data"), names_qpos=first.names_qpos,
                          names_xpos=first.names_xpos, kp_names=first.kp_names, qvel=cat("qvel"), kp_gap=cat("kp_gap"),
-                         kp_rejected=cat("kp_rejected"), qpos_raw=cat("qpos_raw"))
+                         kp_rejected=cat("kp_rejected"), qpos_raw=cat("qpos_raw"),
+                         kp_rejected_pairwise=cat("kp_rejected_pairwise"))
 
 
 def load_stac_result(path):

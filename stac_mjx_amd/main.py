@@ -8,8 +8,8 @@ from pathlib import Path
 import numpy as np
 
 from . import dist, io, utils
-from .config import (GATHER_NONE_CONTINUOUS, POSTPROCESS_GPU_MARKER_ORDER, compose_config, fill_missing_options, outlier_options,
-                     postprocess_options, report_options, smooth_options)
+from .config import (GATHER_NONE_CONTINUOUS, PAIRWISE_NEEDS_FILL, POSTPROCESS_GPU_MARKER_ORDER, compose_config, fill_missing_options,
+                     outlier_options, pairwise_options, postprocess_options, report_options, smooth_options)
 from .stac import Stac
 
 
@@ -31,6 +31,10 @@ def run_stac(cfg, kp_data, kp_names, base_path=None, *, setup=None, device=None)
     and adds ``kp_gap`` to both files (DESIGN.md "Filling missing keypoints"); a keypoint without any valid frame is a ``ValueError``.
     ``stac.reject_outliers: hampel`` (needs ``fill_missing``) first turns keypoints that are finite but off their track's sliding
     median into missing ones, on the GPU, and adds ``kp_rejected`` to both files (DESIGN.md "Rejecting keypoint outliers").
+    ``stac.reject_pairwise: mad`` (needs ``fill_missing``) does the same, ahead of it and on the raw series, to keypoints that leave
+    the distributions of their distances to the other keypoints over the whole series, however long the defect lasts: ``kp_rejected``
+    is then what either detector rejected and ``kp_rejected_pairwise`` this one's share (DESIGN.md "Rejecting keypoints by pairwise
+    distances").
     ``stac.report: on`` computes the marker errors of each phase's final result on the GPU and writes them as
     ``<result file>.report.json`` next to the file (DESIGN.md "Fit report"); the result files themselves do not change.
     ``stac.smooth: savgol | gaussian`` (needs ``postprocess: gpu``) low-pass filters the ``qpos`` of the ik_only run along time on
@@ -66,7 +70,7 @@ def run_stac(cfg, kp_data, kp_names, base_path=None, *, setup=None, device=None)
 
 def _run_fit(stac, cfg, series, fit_offsets_path, report) -> Path:
     """``fit_offsets`` on the first ``n_fit_frames`` of the series and the fit file -> the name the file really has."""
-    kp_data, kp_gap, kp_rejected = series
+    kp_data, kp_gap, kp_rejected, kp_pairwise = series
     kps = kp_data[: cfg.stac.n_fit_frames]
     print(f"Running fit. Mocap data shape: {kps.shape}")
     fit_data = stac.fit_offsets(kps)
@@ -74,6 +78,8 @@ def _run_fit(stac, cfg, series, fit_offsets_path, report) -> Path:
         fit_data.kp_gap = kp_gap[: fit_data.kp_data.shape[0]]
     if kp_rejected is not None:
         fit_data.kp_rejected = kp_rejected[: fit_data.kp_data.shape[0]]
+    if kp_pairwise is not None:
+        fit_data.kp_rejected_pairwise = kp_pairwise[: fit_data.kp_data.shape[0]]
     # multi-GPU: rank 0 holds the gathered result and writes it
     fit_offsets_path = _write_result(stac, cfg, fit_data, fit_offsets_path, report, dist.world()[0] == 0)
     print(f"saved fit to {fit_offsets_path}", flush=True)
@@ -83,7 +89,7 @@ def _run_fit(stac, cfg, series, fit_offsets_path, report) -> Path:
 def _run_ik(stac, series, fit_offsets_path, ik_only_path, pre, start):
     """``ik_only`` on the whole series with the offsets of the fit file, the host post-processing and the result file(s) -> what
     ``run_stac`` returns."""
-    kp_data, kp_gap, kp_rejected = series
+    kp_data, kp_gap, kp_rejected, kp_pairwise = series
     cfg = pre.cfg  # the caller's, until the fit file is read back
     if kp_data.shape[0] % cfg.stac.n_frames_per_clip != 0:
         raise ValueError(
@@ -123,6 +129,8 @@ def _run_ik(stac, series, fit_offsets_path, ik_only_path, pre, start):
         ik_data.kp_gap = kp_gap[lo * F:hi * F]
         if kp_rejected is not None:  # (handled exactly like kp_gap)
             ik_data.kp_rejected = kp_rejected[lo * F:hi * F]
+        if kp_pairwise is not None:
+            ik_data.kp_rejected_pairwise = kp_pairwise[lo * F:hi * F]
     if sharded:
         # every rank writes ITS clips under a shard name (never a partial result under the full-run name; its report is of these
         # clips, shard reports are not merged); rank 0 adds the manifest that io.load_stac_result() reads the run back through
@@ -159,6 +167,7 @@ class _Preflight:
         reference_marker_order, ...): refused before a ``Stac`` is built."""
         stac = self.cfg.stac
         self.reject_mode, self.reject_args = _reject_outliers_mode(self.cfg)
+        self.pairwise_mode, self.pairwise_args = _reject_pairwise_mode(self.cfg)
         self.report = _report_mode(self.cfg)
         self.smooth = _smooth_mode(self.cfg)
         self.marker_order = not stac.skip_ik_only and bool(stac.get("reference_marker_order", False))
@@ -187,23 +196,32 @@ class _Preflight:
 
 
 def _prepare_series(stac, cfg, kp_data, pre):
-    """``stac.reject_outliers`` then ``stac.fill_missing`` over the WHOLE series, once, on the GPU (every rank itself: same bits)
-    -> (kp_data, kp_gap or None, kp_rejected or None).  A missing run that crosses n_fit_frames or a clip border is so filled from
-    its true neighbours, and both phases see the filled array.  A rejected keypoint is three NaN, which the fill closes like any
-    missing one, so kp_gap > 0 there with no further code."""
-    kp_gap = kp_rejected = None
+    """``stac.reject_pairwise`` (its medians want the raw series), then ``stac.reject_outliers``, then ``stac.fill_missing`` over the
+    WHOLE series, once, on the GPU (every rank itself: same bits) -> (kp_data, kp_gap or None, kp_rejected or None: what either
+    detector rejected, kp_rejected_pairwise or None: the pairwise detector's share).  A missing run that crosses n_fit_frames or a
+    clip border is so filled from its true neighbours, and both phases see the filled array.  A rejected keypoint is three NaN,
+    which the fill closes like any missing one, so kp_gap > 0 there with no further code."""
+    kp_gap = kp_rejected = kp_pairwise = kp_hampel = None
+    if pre.pairwise_mode != "off":
+        kp_data, kp_pairwise = stac.reject_pairwise(kp_data, **pre.pairwise_args)
+        kp_rejected = kp_pairwise
     if pre.reject_mode != "off":
-        kp_data, kp_rejected = stac.reject_outliers(kp_data, **pre.reject_args)
+        kp_data, kp_hampel = stac.reject_outliers(kp_data, **pre.reject_args)
+        # (Hampel passes a keypoint that is missing already: the two detectors' sets are disjoint)
+        kp_rejected = kp_hampel if kp_pairwise is None else kp_hampel | kp_pairwise
     if pre.fill_mode != "off":
         kp_data, kp_gap = stac.fill_missing(kp_data, pre.fill_mode)
         n_fit = min(int(cfg.stac.n_fit_frames), kp_gap.shape[0])
         if not cfg.stac.skip_fit_offsets and n_fit > 0:  # (the offset phase fits filled positions like observed ones: DESIGN.md §10)
             print(f"fill_missing: {100.0 * np.count_nonzero(kp_gap[:n_fit]) / kp_gap[:n_fit].size:.3f} % of the keypoints of the "
                   f"{n_fit} fit frames are filled values")
-            if kp_rejected is not None:
-                print(f"reject_outliers: {100.0 * np.count_nonzero(kp_rejected[:n_fit]) / kp_rejected[:n_fit].size:.3f} % of the "
+            if kp_pairwise is not None:
+                print(f"reject_pairwise: {100.0 * np.count_nonzero(kp_pairwise[:n_fit]) / kp_pairwise[:n_fit].size:.3f} % of the "
+                      f"keypoints of the {n_fit} fit frames were rejected by their pairwise distances (and are among the filled ones)")
+            if kp_hampel is not None:
+                print(f"reject_outliers: {100.0 * np.count_nonzero(kp_hampel[:n_fit]) / kp_hampel[:n_fit].size:.3f} % of the "
                       f"keypoints of the {n_fit} fit frames were rejected as outliers (and are among the filled ones)")
-    return kp_data, kp_gap, kp_rejected
+    return kp_data, kp_gap, kp_rejected, kp_pairwise
 
 
 def _write_result(stac, cfg, data, path, report, writes: bool) -> Path:
@@ -292,6 +310,16 @@ def _reject_outliers_mode(cfg) -> tuple:
         raise ValueError("stac.reject_outliers = hampel turns outliers into missing keypoints (NaN), which the solver cannot take: "
                          "set stac.fill_missing to linear or hold as well")
     return mode, {"half_window": h, "n_sigma": n_sigma, "min_dev": min_dev}
+
+
+def _reject_pairwise_mode(cfg) -> tuple:
+    """``stac.reject_pairwise``: "off" (default) | "mad" -> (mode, keyword arguments of ``Stac.reject_pairwise`` from
+    ``stac.pairwise_nsigma`` / ``pairwise_min_dev`` / ``pairwise_votes``).  ``ValueError`` for a bad value of any of the four keys,
+    and for ``mad`` with ``fill_missing`` off: the solver cannot take the NaN of a rejected keypoint."""
+    mode, n_sigma, min_dev, votes = pairwise_options(cfg.stac)
+    if mode != "off" and _fill_missing_mode(cfg) == "off":
+        raise ValueError(PAIRWISE_NEEDS_FILL)
+    return mode, {"n_sigma": n_sigma, "min_dev": min_dev, "votes": votes}
 
 
 GATHER_AUTO_MAX_BYTES = 1 << 30  # above this much output a multi-GPU run keeps per-rank shard files ("auto")

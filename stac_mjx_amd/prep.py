@@ -1,6 +1,8 @@
 """Filling missing keypoints before the fit on the GPU: ``fill_missing`` over ``stac_prep_fill`` (csrc/stac_prep.hip) and
 ``summary`` of the gap lengths it returns; and, in front of it, ``reject_outliers`` over ``stac_prep_reject``
-(csrc/stac_outlier.hip): finite but wrong keypoints become missing ones (DESIGN.md "Rejecting keypoint outliers").
+(csrc/stac_outlier.hip): finite but wrong keypoints become missing ones (DESIGN.md "Rejecting keypoint outliers"); and
+``reject_pairwise`` over ``stac_prep_pairwise`` (csrc/stac_pairwise.hip), the detector without a time window (DESIGN.md
+"Rejecting keypoints by pairwise distances").
 
 A keypoint is missing in a frame when one of its coordinates is NaN or infinite.  Every track is filled along time on its own
 (``linear``: interpolation between its two valid neighbours in double; ``hold``: the nearer neighbour; leading and trailing runs
@@ -23,6 +25,7 @@ MAX_BLOCKS = 1024   # csrc/stac_prep.hpp: kPrepMaxBlocks (workgroups of a launch
 MODES = {"linear": 0, "hold": 1}  # include/stac_hip.h: STAC_PREP_LINEAR, STAC_PREP_HOLD
 MAX_HALF_WINDOW = 16  # csrc/stac_outlier.hpp: kOutlierMaxHalf (largest half-width of the outlier window)
 MAD_TO_SIGMA = 1.4826  # the median absolute deviation of a normal distribution is sigma / 1.4826
+PAIRWISE_MAX_KP = 64  # csrc/stac_pairwise.hpp: kPairwiseMaxKp (keypoints of reject_pairwise at most)
 
 
 def mode_code(mode) -> int:
@@ -92,6 +95,61 @@ def reject_outliers(kp: torch.Tensor, half_window: int = 5, n_sigma: float = 3.0
         rc = lib.stac_prep_reject(_ptr(kp), T, K, h, thr, floor, _ptr(out), _ptr(flag), stream_ptr(kp.device))
     check(lib, "stac_prep_reject", rc)
     return out, flag
+
+
+def pairwise_params(n_sigma, min_dev, votes):
+    """-> (thr, min_dev, votes) as ``stac_prep_pairwise`` takes them: ``thr = n_sigma * 1.4826`` in double.  ValueError for a
+    negative or non-finite ``n_sigma`` / ``min_dev`` or a ``votes`` that is not an integer >= 1."""
+    vals = []
+    for name, v in (("n_sigma", n_sigma), ("min_dev", min_dev)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
+            raise ValueError(f"reject_pairwise: {name} must be a finite number >= 0, not {v!r}")
+        vals.append(float(v))
+    if isinstance(votes, bool) or not isinstance(votes, int) or not 1 <= votes <= 2**31 - 1:
+        raise ValueError(f"reject_pairwise: votes must be an integer >= 1, not {votes!r}")
+    thr = vals[0] * MAD_TO_SIGMA
+    if not math.isfinite(thr):
+        raise ValueError(f"reject_pairwise: n_sigma = {n_sigma!r} is too large")
+    return thr, vals[1], votes
+
+
+def pairwise_workspace_bytes(n_frames: int, n_kp: int) -> int:
+    """Bytes of device workspace of one ``stac_prep_pairwise`` call (host only)."""
+    lib = load_library()
+    return int(check(lib, "stac_prep_pairwise_workspace", lib.stac_prep_pairwise_workspace(int(n_frames), int(n_kp))))
+
+
+def reject_pairwise(kp: torch.Tensor, n_sigma: float = 6.0, min_dev: float = 0.002, votes: int = 2):
+    """Device tensor [T, 3K] -> (out [T, 3K] float32, flag [T, K] uint8, stats), on the current stream of its device: a keypoint
+    that is in at least ``votes`` pairs whose distance lies further than ``n_sigma * 1.4826`` median absolute deviations, and
+    than ``min_dev``, from that pair's median over the whole series leaves as three NaN with flag 1 (the keypoint in the most
+    such pairs first, its pairs then count for nobody else), everything else bit for bit: DESIGN.md "Rejecting keypoints by
+    pairwise distances".  ``stats``: ``pair_n`` int64, ``pair_med`` and ``pair_mad`` float64, [K (K - 1) / 2] device tensors, the
+    pairs (a, b), a < b, in lexicographic order.  At most 64 keypoints.  The input is made contiguous float32 first and is never
+    written."""
+    thr, floor, votes = pairwise_params(n_sigma, min_dev, votes)
+    kp = device_tensor(kp, "reject_pairwise needs a CUDA tensor")
+    if kp.dim() != 2 or kp.shape[1] % 3 != 0 or kp.shape[1] == 0:
+        raise ValueError(f"reject_pairwise: kp must be [frames, 3 * keypoints], got {tuple(kp.shape)}")
+    T, K = int(kp.shape[0]), int(kp.shape[1]) // 3
+    P = K * (K - 1) // 2
+    out = torch.empty_like(kp)
+    flag = torch.empty((T, K), dtype=torch.uint8, device=kp.device)
+    # (room for one element also without a pair: the entry point takes no null pointer)
+    pair_n = torch.zeros(max(P, 1), dtype=torch.int64, device=kp.device)
+    pair_med = torch.full((max(P, 1),), math.nan, dtype=torch.float64, device=kp.device)
+    pair_mad = torch.full((max(P, 1),), math.nan, dtype=torch.float64, device=kp.device)
+    stats = {"pair_n": pair_n[:P], "pair_med": pair_med[:P], "pair_mad": pair_mad[:P]}
+    if T == 0:
+        return out, flag, stats
+    lib = load_library()
+    nbytes = pairwise_workspace_bytes(T, K)
+    work = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=kp.device)
+    with torch.cuda.device(kp.device):
+        rc = lib.stac_prep_pairwise(_ptr(kp), T, K, thr, floor, votes, _ptr(out), _ptr(flag), _ptr(pair_n), _ptr(pair_med), _ptr(pair_mad),
+                                    _ptr(work), nbytes, stream_ptr(kp.device))
+    check(lib, "stac_prep_pairwise", rc)
+    return out, flag, stats
 
 
 def summary(gap) -> dict:

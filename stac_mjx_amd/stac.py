@@ -124,6 +124,24 @@ class Stac:
                       f"{kp.shape[0]} frames rejected ({100.0 * int(count[k]) / kp.shape[0]:.3f} %)")
         return out.cpu().numpy(), flag.cpu().numpy()
 
+    # -- reject_pairwise (engine extension; DESIGN.md "Rejecting keypoints by pairwise distances") -----------------------
+    def reject_pairwise(self, kp_data, n_sigma=6.0, min_dev=0.002, votes=2):
+        """The pairwise-distance detector over the whole series ``kp_data`` [T, 3K] on the GPU (``prep.reject_pairwise``) ->
+        ``(out [T, 3K] float32, flag [T, K] uint8)`` as numpy arrays: a keypoint that is in at least ``votes`` pairs whose
+        distance lies further than ``n_sigma * 1.4826`` median absolute deviations, and than ``min_dev``, from that pair's median
+        over the series is three NaN in ``out`` and 1 in ``flag``; everything else is the input bit for bit.  No time window:
+        the length of a run of wrong values does not matter.  One log line per keypoint that had rejections."""
+        from . import prep
+
+        prep.pairwise_params(n_sigma, min_dev, votes)
+        kp = self._series_to_device(kp_data, "reject_pairwise")
+        out, flag, _ = prep.reject_pairwise(kp, n_sigma, min_dev, votes)
+        count = flag.sum(dim=0, dtype=torch.int64).cpu().numpy()
+        for k in np.flatnonzero(count):
+            self._log(f"reject_pairwise (mad, {n_sigma} sigma, {votes} votes): {self._kp_names[k]}: {int(count[k])} of "
+                      f"{kp.shape[0]} frames rejected ({100.0 * int(count[k]) / kp.shape[0]:.3f} %)")
+        return out.cpu().numpy(), flag.cpu().numpy()
+
     # -- fit_report (engine extension; DESIGN.md "Fit report") -----------------------------------------------------------
     def fit_report(self, data, permille=None, worst=None) -> dict:
         """The marker error of a result, on the GPU (``report.fit_errors``), as the summary of ``report.summarize``: per keypoint

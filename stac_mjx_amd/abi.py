@@ -2,6 +2,7 @@
 prototypes, ``declare`` that applies the table to a loaded library (``engine.load_library`` does, to whatever it loads), and the
 few helpers every caller of the library shares.  ``tests/test_host.py`` holds the table against the header and the structures against the compiler.
 A second table, ``PAIRWISE_PROTOTYPES``, holds the two functions of ``include/stac_hip_pairwise.h``; ``declare`` applies both.
+A third, ``SWAPS_PROTOTYPES``, holds the two of ``include/stac_hip_swaps.h`` in the same way.
 """
 
 from __future__ import annotations
@@ -103,6 +104,12 @@ PAIRWISE_PROTOTYPES = {
     "stac_prep_pairwise_workspace": (i64, [i64, i32]),
     "stac_prep_pairwise": (i32, [vp, i64, i32, f64, f64, i32, vp, vp, vp, vp, vp, vp, i64, vp]),
 }  # fmt: skip
+# every function include/stac_hip_swaps.h declares (the third header, like the second); tests/test_swaps_host.py holds this table
+# against that header.  The candidate table of stac_prep_swaps is HOST memory: an int32 pointer, not a device address.
+SWAPS_PROTOTYPES = {
+    "stac_prep_swaps_workspace": (i64, [i64, i32]),
+    "stac_prep_swaps": (i32, [vp, i64, i32, _i32p, i32, f64, f64, i32, vp, vp, vp, vp, vp, vp, i64, vp]),
+}  # fmt: skip
 
 
 class StacHipError(RuntimeError):
@@ -110,8 +117,8 @@ class StacHipError(RuntimeError):
 
 
 def declare(lib):
-    """Declares ``restype`` and ``argtypes`` of every function of both tables on ``lib`` (idempotent) -> ``lib``."""
-    for name, (restype, argtypes) in (*PROTOTYPES.items(), *PAIRWISE_PROTOTYPES.items()):
+    """Declares ``restype`` and ``argtypes`` of every function of the three tables on ``lib`` (idempotent) -> ``lib``."""
+    for name, (restype, argtypes) in (*PROTOTYPES.items(), *PAIRWISE_PROTOTYPES.items(), *SWAPS_PROTOTYPES.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     return lib

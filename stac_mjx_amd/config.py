@@ -38,6 +38,9 @@ _MUJOCO_REQUIRED = ("solver", "iterations", "ls_iterations")
 # reject_pairwise: off (default) | mad, with pairwise_nsigma (default 6.0), pairwise_min_dev (default 0.002, units of kp_data) and
 # pairwise_votes (default 2) -- keypoints that leave the distributions of their distances to the other keypoints over the whole series
 # become missing ones, in front of reject_outliers and fill_missing;
+# repair_swaps: off (default) | lr | [[nameA, nameB], ...], with swaps_nsigma (default 6.0), swaps_min_dev (default 0.002, units of
+# kp_data) and swaps_min_bad (default 3) -- two keypoints of a candidate pair that carry each other's label in a frame are exchanged
+# back, in front of everything else; it makes no NaN and needs no fill_missing;
 # report: off (default) | on, with report_quantiles (1 .. 8 permille values, default [500, 900, 990]) and report_worst (frames listed,
 # default 10) -- a <result file>.report.json next to every result file, read from the caller's config;
 # smooth: off (default) | savgol | gaussian, with smooth_window (half-width H, 1 .. 16, default 3: windows of 2 H + 1 frames),
@@ -47,7 +50,8 @@ _MUJOCO_REQUIRED = ("solver", "iterations", "ls_iterations")
 _STAC_EXTENSIONS = ("solver", "lanes_per_chain", "device", "time_indices", "fit_frames_per_clip", "reference_marker_order", "gather", "gather_max_bytes", "lm_maxiter", "postprocess", "fill_missing",
                     "reject_outliers", "outlier_window", "outlier_nsigma", "outlier_min_dev", "report", "report_quantiles", "report_worst",
                     "smooth", "smooth_window", "smooth_order", "smooth_sigma",
-                    "reject_pairwise", "pairwise_nsigma", "pairwise_min_dev", "pairwise_votes")
+                    "reject_pairwise", "pairwise_nsigma", "pairwise_min_dev", "pairwise_votes",
+                    "repair_swaps", "swaps_nsigma", "swaps_min_dev", "swaps_min_bad")
 _MODEL_EXTENSIONS = ("KP_NAMES_LABEL3D_PATH",)
 
 
@@ -131,6 +135,95 @@ def pairwise_options(stac) -> tuple:
     if isinstance(votes, bool) or not isinstance(votes, int) or not 1 <= votes <= 2**31 - 1:
         raise ConfigError(f"stac.pairwise_votes must be an integer >= 1, not {votes!r}")
     return mode, vals[0], vals[1], votes
+
+
+SWAPS_DEFAULTS = {"swaps_nsigma": 6.0, "swaps_min_dev": 0.002, "swaps_min_bad": 3}
+
+
+def lr_pairs(kp_names) -> list:
+    """The left / right keypoint pairs of a list of names as ``(index of the L name, index of the R name)``.  The partner of a name
+    is the name with a trailing ``L`` replaced by ``R`` if that name exists (the rodent's ``AnkleL``, the mouse's ``Knee_L`` and
+    ``Lisfranc_L``), otherwise the name with a leading ``L`` replaced by ``R`` if that exists (the fly's ``L1A``).  In the order of
+    the sorted names of the L side; a keypoint is in at most one pair (the first that claims it)."""
+    names = [str(n) for n in kp_names]
+    where = {n: i for i, n in reversed(list(enumerate(names)))}  # (a repeated name: its first index)
+    out, used = [], set()
+    for n in sorted(where):
+        partner = None
+        if n.endswith("L") and n[:-1] + "R" in where:
+            partner = n[:-1] + "R"
+        elif n.startswith("L") and "R" + n[1:] in where:
+            partner = "R" + n[1:]
+        if partner is None or n in used or partner in used:
+            continue
+        used.update((n, partner))
+        out.append((where[n], where[partner]))
+    return out
+
+
+def named_pairs(pairs, kp_names) -> list:
+    """``[[nameA, nameB], ...]`` -> ``[(index of A, index of B), ...]``.  ``ConfigError`` for a name that ``kp_names`` does not hold,
+    a pair of one name, or a keypoint in two pairs."""
+    names = [str(n) for n in kp_names]
+    out, used = [], set()
+    for a, b in pairs:
+        for n in (a, b):
+            if n not in names:
+                raise ConfigError(f"stac.repair_swaps names the keypoint {n!r}, which is not among the keypoints {names}")
+        if a == b:
+            raise ConfigError(f"stac.repair_swaps: the pair [{a}, {b}] names one keypoint twice")
+        for n in (a, b):
+            if n in used:
+                raise ConfigError(f"stac.repair_swaps: the keypoint {n!r} is in two pairs")
+        used.update((a, b))
+        out.append((names.index(a), names.index(b)))
+    return out
+
+
+def swaps_options(stac) -> tuple:
+    """``stac.repair_swaps`` and its three parameters out of a ``stac`` mapping -> (mode, n_sigma, min_dev, min_bad), absent keys at
+    their defaults; mode is "off" (default; a bare YAML ``off`` arrives as False), "lr" (the left / right pairs of the keypoint
+    names: ``lr_pairs``) or a list of ``[nameA, nameB]`` pairs.  ``ConfigError`` for anything else, a ``swaps_nsigma`` /
+    ``swaps_min_dev`` (units of kp_data) that is not a finite number >= 0, or a ``swaps_min_bad`` that is not an integer >= 1.
+    Whether the names exist is for ``swaps_candidates``, which knows the keypoints."""
+    import math
+
+    mode = _switch(stac, "repair_swaps")
+    if isinstance(mode, (list, tuple)):
+        if not mode:
+            raise ConfigError("stac.repair_swaps: an empty list of pairs repairs nothing: say off")
+        pairs = []
+        for p in mode:
+            if not isinstance(p, (list, tuple)) or len(p) != 2 or not all(isinstance(n, str) and n for n in p):
+                raise ConfigError(f"stac.repair_swaps: a candidate is a pair [nameA, nameB] of keypoint names, not {p!r}")
+            pairs.append((p[0], p[1]))
+        mode = pairs
+    elif not isinstance(mode, str) or mode not in ("off", "lr"):
+        raise ConfigError(f"stac.repair_swaps must be off, lr or a list of [nameA, nameB] pairs, not {mode!r}")
+    vals = []
+    for key in ("swaps_nsigma", "swaps_min_dev"):
+        v = stac.get(key, SWAPS_DEFAULTS[key])
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
+            raise ConfigError(f"stac.{key} must be a finite number >= 0, not {v!r}")
+        vals.append(float(v))
+    min_bad = stac.get("swaps_min_bad", SWAPS_DEFAULTS["swaps_min_bad"])
+    if isinstance(min_bad, bool) or not isinstance(min_bad, int) or not 1 <= min_bad <= 2**31 - 1:
+        raise ConfigError(f"stac.swaps_min_bad must be an integer >= 1, not {min_bad!r}")
+    return mode, vals[0], vals[1], min_bad
+
+
+def swaps_candidates(mode, kp_names) -> list:
+    """The candidates of a run as index pairs from the mode of ``swaps_options`` and the run's keypoint names: [] for off.
+    ``ConfigError`` for unknown names, a keypoint in two pairs, or ``lr`` with names that hold no left / right pair."""
+    if mode == "off":
+        return []
+    if mode == "lr":
+        pairs = lr_pairs(kp_names)
+        if not pairs:
+            raise ConfigError(f"stac.repair_swaps = lr finds no left / right pair among the keypoints {[str(n) for n in kp_names]}: "
+                              "name the pairs as [[nameA, nameB], ...]")
+        return pairs
+    return named_pairs(mode, kp_names)
 
 
 REPORT_DEFAULTS = {"report_quantiles": (500, 900, 990), "report_worst": 10}
@@ -338,7 +431,7 @@ def validate_config(cfg: dict) -> ConfigNode:
             raise ConfigError(f"stac.{k} must be a bool")
     postprocess_options(stac)
     for key, options in (("fill_missing", fill_missing_options), ("reject_outliers", outlier_options), ("report", report_options),
-                         ("smooth", smooth_options), ("reject_pairwise", pairwise_options)):
+                         ("smooth", smooth_options), ("reject_pairwise", pairwise_options), ("repair_swaps", swaps_options)):
         if isinstance(stac.get(key), bool):  # the file that is written with a result says off / on, not the boolean
             stac[key] = _switch(stac, key)
         options(stac)

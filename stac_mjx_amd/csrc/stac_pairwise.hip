@@ -22,13 +22,24 @@
 // wavefront then takes pairs with a lane per frame and writes 256-byte lines of the key rows.
 // The counting passes keep a histogram per workgroup in LDS (integer atomics on per-lane addresses) and add its non-empty bins to
 // global memory with 64-bit integer atomics: the counts do not depend on their order.
+//
+// Repairing swaps (rule: stac_swap.hpp; stac_prep_swaps below) is the same statistics part -- steps 0 to 3, the same launches -- and
+//   4'. pairwise_swap_kernel: one lane per frame, one wavefront per tile of 64 frames, like step 4.  The candidate table comes by
+//       value as kernel arguments (four candidates per 64-bit word) and goes into LDS by compile-time-indexed stores: no copy from
+//       host memory on the stream, no run-time-indexed private array.  Per candidate (the same for every lane) and third keypoint k
+//       a lane reads the keys of {a, k} and {b, k} of its frame (256 contiguous bytes of each row per wavefront); n, med and
+//       thr * mad of the two pairs are the same for every lane.  b0 and b1 live in registers, the frame's decisions are 32 bits in
+//       LDS.  The wavefront then writes the tile's out in the order of memory: element (frame, keypoint) reads kp at its partner if
+//       its candidate swaps, else at itself; flag [T][S] likewise.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 
 #include "../../include/stac_hip_pairwise.h"
+#include "../../include/stac_hip_swaps.h"
 #include "stac_host.hpp"
 #include "stac_pairwise.hpp"
+#include "stac_swap.hpp"
 
 namespace stac {
 
@@ -252,11 +263,82 @@ __global__ __launch_bounds__(64) void pairwise_decide_kernel(const float *__rest
     }
 }
 
+// One wavefront per workgroup, one lane per frame of a tile.  LDS: the candidate table, the partner and the candidate of every
+// keypoint, the decisions of the tile's frames (bit s: candidate s swaps).
+__global__ __launch_bounds__(64) void pairwise_swap_kernel(const uint32_t *__restrict__ kp, int64_t T, int32_t K, int32_t S, SwapCands cands,
+                                                           int64_t tiles, int64_t stride, const uint32_t *__restrict__ keys,
+                                                           const int64_t *__restrict__ pair_n, const double *__restrict__ pair_med,
+                                                           const double *__restrict__ pair_mad, double thr, double min_dev, int32_t min_bad,
+                                                           uint32_t *__restrict__ out, uint8_t *__restrict__ flag) {
+    __shared__ unsigned long long candw[kSwapCandWords];
+    __shared__ uint8_t partner[kPairwiseMaxKp], cand_of[kPairwiseMaxKp];
+    __shared__ uint32_t dec[kPairwiseTileFrames];
+    const int32_t lane = threadIdx.x;
+    if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < kSwapCandWords; ++i) candw[i] = cands.w[i];  // (compile-time indices: the arguments stay in registers)
+    }
+    partner[lane] = (uint8_t)lane;
+    cand_of[lane] = (uint8_t)kSwapNoCand;
+    __syncthreads();
+    const uint16_t *c16 = (const uint16_t *)candw;  // candidate s: a | b << 8
+    if (lane < S) {
+        const uint32_t c = c16[lane], a = c & 0xFFu, b = c >> 8;
+        partner[a] = (uint8_t)b;
+        partner[b] = (uint8_t)a;
+        cand_of[a] = (uint8_t)lane;
+        cand_of[b] = (uint8_t)lane;
+    }
+    __syncthreads();
+    for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const int64_t t0 = tile * kPairwiseTileFrames, t = t0 + lane;
+        uint32_t mask = 0u;
+        if (t < T) {
+            for (int32_t s = 0; s < S; ++s) {
+                const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane((int32_t)c16[s]);  // (the same for every lane)
+                const int32_t a = (int32_t)(c & 0xFFu), b = (int32_t)(c >> 8);
+                int32_t b0 = 0, b1 = 0;
+                for (int32_t k = 0; k < K; ++k) {
+                    if (k == a || k == b) continue;
+                    const int64_t pa = swap_pair(a, k, K), pb = swap_pair(b, k, K);
+                    const int64_t na = pair_n[pa], nb = pair_n[pb];
+                    if (na < 3 || nb < 3) continue;  // (the same for every lane)
+                    swap_count(keys[pa * stride + t], keys[pb * stride + t], na, nb, pair_med[pa], thr * pair_mad[pa], pair_med[pb],
+                               thr * pair_mad[pb], min_dev, &b0, &b1);
+                }
+                if (swap_decide(b0, b1, min_bad)) mask |= 1u << s;
+            }
+        }
+        dec[lane] = mask;
+        __syncthreads();
+        const int64_t left = T - t0;
+        const int32_t nf = left < kPairwiseTileFrames ? (int32_t)left : kPairwiseTileFrames;
+        const int64_t base = t0 * K;
+        for (int32_t e = lane; e < nf * K; e += kPairwiseTileFrames) {  // (frame, keypoint) pairs in the order of memory
+            const int32_t f = e / K, k = e - f * K;
+            const uint32_t s = cand_of[k];
+            const bool swaps = s != kSwapNoCand && ((dec[f] >> s) & 1u);
+            const int64_t to = 3 * (base + e), from = swaps ? 3 * (base + (int64_t)f * K + partner[k]) : to;
+            const uint32_t x = kp[from], y = kp[from + 1], z = kp[from + 2];
+            out[to] = x;
+            out[to + 1] = y;
+            out[to + 2] = z;
+        }
+        const int64_t fbase = t0 * S;
+        for (int32_t e = lane; e < nf * S; e += kPairwiseTileFrames) {  // (frame, candidate) pairs in the order of memory
+            const int32_t f = e / S, s = e - f * S;
+            flag[fbase + e] = (uint8_t)((dec[f] >> s) & 1u);
+        }
+        __syncthreads();  // dec is written again in the next sweep
+    }
+}
+
 }  // namespace
 
-static hipError_t launch_pairwise(const float *kp, int64_t T, int32_t K, double thr, double min_dev, int32_t votes, float *out, uint8_t *flag,
-                                  int64_t *pair_n, double *pair_med, double *pair_mad, void *workspace, hipStream_t s) {
-    const PairwiseLayout L = pairwise_layout(T, K);
+// The statistics part of both entry points: the keys of every (pair, frame) into the workspace, pair_n, pair_med, pair_mad.  Two memsets
+// and 13 launches (nothing for K == 1).
+static hipError_t launch_pairwise_stats(const float *kp, int64_t T, int32_t K, const PairwiseLayout &L, int64_t *pair_n, double *pair_med,
+                                        double *pair_mad, void *workspace, hipStream_t s) {
     char *w = (char *)workspace;
     uint32_t *keys = (uint32_t *)(w + L.keys);
     unsigned long long *hist[3] = {(unsigned long long *)(w + L.hist0), (unsigned long long *)(w + L.hist1), (unsigned long long *)(w + L.hist2)};
@@ -283,9 +365,31 @@ static hipError_t launch_pairwise(const float *kp, int64_t T, int32_t K, double 
             }
         }
     }
+    return hipSuccess;
+}
+
+static hipError_t launch_pairwise(const float *kp, int64_t T, int32_t K, double thr, double min_dev, int32_t votes, float *out, uint8_t *flag,
+                                  int64_t *pair_n, double *pair_med, double *pair_mad, void *workspace, hipStream_t s) {
+    const PairwiseLayout L = pairwise_layout(T, K);
+    const hipError_t e = launch_pairwise_stats(kp, T, K, L, pair_n, pair_med, pair_mad, workspace, s);
+    if (e != hipSuccess) return e;
+    const uint32_t *keys = (const uint32_t *)((const char *)workspace + L.keys);
     const unsigned gridd = (unsigned)(L.tiles < kPairwiseMaxWaves ? L.tiles : kPairwiseMaxWaves);
     hipLaunchKernelGGL(pairwise_decide_kernel, dim3(gridd), dim3(kPairwiseTileFrames), (size_t)(K + 1) * kPairwiseTileFrames * 8, s, kp, T, K, L.tiles,
                        L.stride, keys, pair_n, pair_med, pair_mad, thr, min_dev, votes, out, flag);
+    return hipGetLastError();
+}
+
+static hipError_t launch_swaps(const float *kp, int64_t T, int32_t K, const SwapCands &cands, int32_t S, double thr, double min_dev,
+                               int32_t min_bad, float *out, uint8_t *flag, int64_t *pair_n, double *pair_med, double *pair_mad, void *workspace,
+                               hipStream_t s) {
+    const PairwiseLayout L = pairwise_layout(T, K);
+    const hipError_t e = launch_pairwise_stats(kp, T, K, L, pair_n, pair_med, pair_mad, workspace, s);
+    if (e != hipSuccess) return e;
+    const uint32_t *keys = (const uint32_t *)((const char *)workspace + L.keys);
+    const unsigned grid = (unsigned)(L.tiles < kPairwiseMaxWaves ? L.tiles : kPairwiseMaxWaves);
+    hipLaunchKernelGGL(pairwise_swap_kernel, dim3(grid), dim3(kPairwiseTileFrames), 0, s, (const uint32_t *)kp, T, K, S, cands, L.tiles, L.stride,
+                       keys, pair_n, pair_med, pair_mad, thr, min_dev, min_bad, (uint32_t *)out, flag);
     return hipGetLastError();
 }
 
@@ -333,4 +437,62 @@ extern "C" int32_t stac_prep_pairwise(const float *kp, int64_t n_frames, int32_t
                                           " overlap: inputs, outputs and workspace are distinct buffers (in place is not possible)");
     return launch_result("stac_prep_pairwise", launch_pairwise(kp, n_frames, n_kp, thr, min_dev, votes, out, flag, pair_n, pair_med, pair_mad,
                                                                workspace, (hipStream_t)stream));
+}
+
+// ---- C ABI entry points (include/stac_hip_swaps.h) -------------------------------------------------------------------------------
+extern "C" int64_t stac_prep_swaps_workspace(int64_t n_frames, int32_t n_kp) {
+    if (n_frames >= 1 && n_kp > kPairwiseMaxKp)
+        return fail(STAC_ERR_CAPACITY, "stac_prep_swaps_workspace: n_kp = " + std::to_string(n_kp) + " is above the " +
+                                           std::to_string(kPairwiseMaxKp) + " keypoints of the pairwise statistics");
+    const PairwiseLayout L = pairwise_layout(n_frames, n_kp);
+    if (L.bytes < 0) return fail(STAC_ERR_INVALID, "stac_prep_swaps_workspace: n_frames >= 1, n_kp >= 1 (and a workspace size within int64)");
+    return L.bytes;
+}
+
+extern "C" int32_t stac_prep_swaps(const float *kp, int64_t n_frames, int32_t n_kp, const int32_t *cand, int32_t n_cand, double thr,
+                                   double min_dev, int32_t min_bad, float *out, uint8_t *flag, int64_t *pair_n, double *pair_med,
+                                   double *pair_mad, void *workspace, int64_t workspace_bytes, void *stream) {
+    if (n_frames < 1 || n_kp < 1) return fail(STAC_ERR_INVALID, "stac_prep_swaps: n_frames >= 1, n_kp >= 1");
+    if (n_kp > kPairwiseMaxKp)
+        return fail(STAC_ERR_CAPACITY, "stac_prep_swaps: n_kp = " + std::to_string(n_kp) + " is above the " + std::to_string(kPairwiseMaxKp) +
+                                           " keypoints of the pairwise statistics");
+    const PairwiseLayout L = pairwise_layout(n_frames, n_kp);
+    if (L.bytes < 0) return fail(STAC_ERR_INVALID, "stac_prep_swaps: array sizes beyond int64");
+    if (n_cand < 0) return fail(STAC_ERR_INVALID, "stac_prep_swaps: n_cand = " + std::to_string(n_cand) + " must be >= 0");
+    if (n_cand > 0 && !cand) return fail(STAC_ERR_INVALID, "stac_prep_swaps: null cand with n_cand > 0");
+    SwapCands cands;
+    int32_t at = 0;
+    const int bad = swap_pack(cand, n_cand, n_kp, &cands, &at);  // (cand is host memory)
+    if (bad) {
+        const char *why[] = {"", "has a keypoint outside 0 .. n_kp - 1", "names one keypoint twice (a == b)",
+                             "has a keypoint that an earlier candidate holds", "is one more than n_kp / 2 candidates can be"};
+        return fail(STAC_ERR_INVALID, "stac_prep_swaps: candidate " + std::to_string(at) + " (" + std::to_string(cand[2 * at]) + ", " +
+                                          std::to_string(cand[2 * at + 1]) + ") " + why[bad]);
+    }
+    if (!std::isfinite(thr) || thr < 0.0 || !std::isfinite(min_dev) || min_dev < 0.0)
+        return fail(STAC_ERR_INVALID, "stac_prep_swaps: thr and min_dev must be finite and >= 0");
+    if (min_bad < 1) return fail(STAC_ERR_INVALID, "stac_prep_swaps: min_bad = " + std::to_string(min_bad) + " must be >= 1");
+    if (!kp || !out || !flag || !pair_n || !pair_med || !pair_mad || !workspace)
+        return fail(STAC_ERR_INVALID, "stac_prep_swaps: null kp / out / flag / pair_n / pair_med / pair_mad / workspace");
+    if (workspace_bytes < L.bytes)
+        return fail(STAC_ERR_INVALID, "stac_prep_swaps: workspace_bytes = " + std::to_string(workspace_bytes) + ", " + std::to_string(L.bytes) +
+                                          " are needed (stac_prep_swaps_workspace)");
+    const int64_t NK = n_frames * n_kp, P8 = (L.pairs > 0 ? L.pairs : 1) * 8;
+    const HostBuf buf[7] = {{"kp", (uintptr_t)kp, NK * 12, 4},
+                            {"out", (uintptr_t)out, NK * 12, 4},
+                            {"flag", (uintptr_t)flag, n_frames * (n_cand > 0 ? n_cand : 1), 1},
+                            {"pair_n", (uintptr_t)pair_n, P8, 8},
+                            {"pair_med", (uintptr_t)pair_med, P8, 8},
+                            {"pair_mad", (uintptr_t)pair_mad, P8, 8},
+                            {"workspace", (uintptr_t)workspace, L.bytes, 8}};
+    for (int i = 0; i < 7; ++i)
+        if (buf[i].lo % buf[i].align != 0)
+            return fail(STAC_ERR_INVALID, std::string("stac_prep_swaps: ") + buf[i].name + " must be " + std::to_string(buf[i].align) +
+                                              "-byte aligned");
+    const HostBuf *a, *b;
+    if (find_overlap(buf, 7, &a, &b))
+        return fail(STAC_ERR_INVALID, std::string("stac_prep_swaps: ") + a->name + " and " + b->name +
+                                          " overlap: inputs, outputs and workspace are distinct buffers (in place is not possible)");
+    return launch_result("stac_prep_swaps", launch_swaps(kp, n_frames, n_kp, cands, n_cand, thr, min_dev, min_bad, out, flag, pair_n, pair_med,
+                                                         pair_mad, workspace, (hipStream_t)stream));
 }

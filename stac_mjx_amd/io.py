@@ -50,14 +50,18 @@ class StacData:
     # engine extension (stac.reject_pairwise): [frames, K] uint8, 1 = the keypoint was rejected by its pairwise distances; with it
     # kp_rejected is what either detector rejected.  Empty without the option, and then not written to the file.  (By keyword too.)
     kp_rejected_pairwise: np.ndarray = field(default_factory=lambda: np.array([]))
+    # engine extension (stac.repair_swaps): [frames, K] uint8, 1 = the keypoint and its partner carried each other's label in this
+    # frame and were exchanged back (kp_data holds the repaired series).  Empty without the option, and then not written to the
+    # file.  (By keyword too.)
+    kp_swapped: np.ndarray = field(default_factory=lambda: np.array([]))
     # engine extension (stac.reject_outliers): [frames, K] uint8, 1 = the keypoint was rejected as an outlier before the fill (so
     # kp_gap > 0 there); rows as kp_gap.  Empty without the option, and then not written to the file.
     kp_rejected: np.ndarray = field(default_factory=lambda: np.array([]))
 
     def as_dict(self) -> dict:
-        """The fields as ``save_data_to_h5`` takes them (an empty ``kp_gap`` / ``kp_rejected`` / ``kp_rejected_pairwise`` / ``qpos_raw`` is left out: the reference's fields alone)."""
+        """The fields as ``save_data_to_h5`` takes them (an empty ``kp_gap`` / ``kp_rejected`` / ``kp_rejected_pairwise`` / ``kp_swapped`` / ``qpos_raw`` is left out: the reference's fields alone)."""
         d = asdict(self)
-        for name in ("kp_gap", "kp_rejected", "kp_rejected_pairwise", "qpos_raw"):
+        for name in ("kp_gap", "kp_rejected", "kp_rejected_pairwise", "kp_swapped", "qpos_raw"):
             if not np.asarray(d[name]).size:
                 del d[name]
         return d
@@ -359,12 +363,14 @@ def _npz_write_parallel(path, members: dict, pool, level: int = _H5_GZIP_LEVEL) 
 
 
 def save_data_to_h5(config, kp_names, names_qpos, names_xpos, kp_data, marker_sites, offsets, qpos,
-                    xpos, xquat, qvel, file_path, kp_gap=None, kp_rejected=None, qpos_raw=None, kp_rejected_pairwise=None) -> Path:  # fmt: skip
+                    xpos, xquat, qvel, file_path, kp_gap=None, kp_rejected=None, qpos_raw=None, kp_rejected_pairwise=None,
+                    kp_swapped=None) -> Path:  # fmt: skip
     """Write the reference's output contract (io.py:194-237).  Returns the path actually written.  Same datasets, dtypes
     and gzip filter as the reference; the deflate work of the large arrays runs on every host core (see above).  A non-empty
     ``kp_gap`` (engine extension, ``stac.fill_missing``) adds one dataset of that name, a non-empty ``kp_rejected``
     (``stac.reject_outliers``) another, a non-empty ``qpos_raw`` (``stac.smooth``) a third, a non-empty ``kp_rejected_pairwise``
-    (``stac.reject_pairwise``) a fourth; without them the file holds the reference's."""
+    (``stac.reject_pairwise``) a fourth, a non-empty ``kp_swapped`` (``stac.repair_swaps``) a fifth; without them the file holds the
+    reference's."""
     file_path = Path(file_path)
     cfg_yaml = config.to_yaml() if isinstance(config, ConfigNode) else yaml.safe_dump(config, sort_keys=False)
     arrays = dict(kp_data=kp_data, marker_sites=marker_sites, offsets=offsets, qpos=qpos,
@@ -377,6 +383,8 @@ def save_data_to_h5(config, kp_names, names_qpos, names_xpos, kp_data, marker_si
         arrays["qpos_raw"] = np.asarray(qpos_raw)
     if kp_rejected_pairwise is not None and np.asarray(kp_rejected_pairwise).size:
         arrays["kp_rejected_pairwise"] = np.asarray(kp_rejected_pairwise, dtype=np.uint8)
+    if kp_swapped is not None and np.asarray(kp_swapped).size:
+        arrays["kp_swapped"] = np.asarray(kp_swapped, dtype=np.uint8)
     if h5py is not None and file_path.suffix in (".h5", ".hdf5"):
         with h5py.File(file_path, "w") as f, _pool() as pool:
             f.create_dataset("config", data=np.bytes_(cfg_yaml))
@@ -424,7 +432,8 @@ def load_stac_data(file_path):
         qvel=d["qvel"], xpos=d["xpos"], xquat=d["xquat"], kp_gap=d["kp_gap"] if "kp_gap" in d else np.array([]),
         kp_rejected=d["kp_rejected"] if "kp_rejected" in d else np.array([]),
         qpos_raw=d["qpos_raw"] if "qpos_raw" in d else np.array([]),
-        kp_rejected_pairwise=d["kp_rejected_pairwise"] if "kp_rejected_pairwise" in d else np.array([]))  # fmt: skip
+        kp_rejected_pairwise=d["kp_rejected_pairwise"] if "kp_rejected_pairwise" in d else np.array([]),
+        kp_swapped=d["kp_swapped"] if "kp_swapped" in d else np.array([]))  # fmt: skip
 
 
 # ---- per-rank shard files of a multi-GPU ik_only run (engine extension; main.run_stac with stac.gather = none / auto) ----
@@ -475,7 +484,7 @@ def load_sharded_stac_data(manifest):
                          offsets=first.offsets, kp_data=cat("kp_data"), names_qpos=first.names_qpos,
                          names_xpos=first.names_xpos, kp_names=first.kp_names, qvel=cat("qvel"), kp_gap=cat("kp_gap"),
                          kp_rejected=cat("kp_rejected"), qpos_raw=cat("qpos_raw"),
-                         kp_rejected_pairwise=cat("kp_rejected_pairwise"))
+                         kp_rejected_pairwise=cat("kp_rejected_pairwise"), kp_swapped=cat("kp_swapped"))
 
 
 def load_stac_result(path):

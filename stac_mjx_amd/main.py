@@ -9,7 +9,8 @@ import numpy as np
 
 from . import dist, io, utils
 from .config import (GATHER_NONE_CONTINUOUS, PAIRWISE_NEEDS_FILL, POSTPROCESS_GPU_MARKER_ORDER, compose_config, fill_missing_options,
-                     outlier_options, pairwise_options, postprocess_options, report_options, smooth_options)
+                     outlier_options, pairwise_options, postprocess_options, report_options, smooth_options, swaps_candidates,
+                     swaps_options)
 from .stac import Stac
 
 
@@ -35,6 +36,10 @@ def run_stac(cfg, kp_data, kp_names, base_path=None, *, setup=None, device=None)
     the distributions of their distances to the other keypoints over the whole series, however long the defect lasts: ``kp_rejected``
     is then what either detector rejected and ``kp_rejected_pairwise`` this one's share (DESIGN.md "Rejecting keypoints by pairwise
     distances").
+    ``stac.repair_swaps: lr`` (or a list of ``[nameA, nameB]`` pairs; needs no ``fill_missing``) first of all exchanges back, frame
+    by frame, two keypoints of a pair that carry each other's label, on the GPU: ``kp_data`` of both files is the repaired series and
+    ``kp_swapped`` marks both keypoints of every repaired pair (DESIGN.md "Repairing keypoint swaps"); unknown names and a keypoint
+    in two pairs are a ``ValueError`` before any work.
     ``stac.report: on`` computes the marker errors of each phase's final result on the GPU and writes them as
     ``<result file>.report.json`` next to the file (DESIGN.md "Fit report"); the result files themselves do not change.
     ``stac.smooth: savgol | gaussian`` (needs ``postprocess: gpu``) low-pass filters the ``qpos`` of the ik_only run along time on
@@ -53,7 +58,7 @@ def run_stac(cfg, kp_data, kp_names, base_path=None, *, setup=None, device=None)
     start = time.time()
     fit_offsets_path = base_path / cfg.stac.fit_offsets_path
     ik_only_path = base_path / cfg.stac.ik_only_path
-    pre = _Preflight(cfg, kp_data.shape[0], fit_offsets_path)
+    pre = _Preflight(cfg, kp_data.shape[0], fit_offsets_path, kp_names=kp_names)
     pre.check_config()
     stac = Stac(base_path / cfg.model.MJCF_PATH, cfg, kp_names, setup=setup, device=device)
     pre.check_run(dist.world()[1])
@@ -70,7 +75,7 @@ def run_stac(cfg, kp_data, kp_names, base_path=None, *, setup=None, device=None)
 
 def _run_fit(stac, cfg, series, fit_offsets_path, report) -> Path:
     """``fit_offsets`` on the first ``n_fit_frames`` of the series and the fit file -> the name the file really has."""
-    kp_data, kp_gap, kp_rejected, kp_pairwise = series
+    kp_data, kp_gap, kp_rejected, kp_pairwise, kp_swapped = series
     kps = kp_data[: cfg.stac.n_fit_frames]
     print(f"Running fit. Mocap data shape: {kps.shape}")
     fit_data = stac.fit_offsets(kps)
@@ -80,6 +85,8 @@ def _run_fit(stac, cfg, series, fit_offsets_path, report) -> Path:
         fit_data.kp_rejected = kp_rejected[: fit_data.kp_data.shape[0]]
     if kp_pairwise is not None:
         fit_data.kp_rejected_pairwise = kp_pairwise[: fit_data.kp_data.shape[0]]
+    if kp_swapped is not None:
+        fit_data.kp_swapped = kp_swapped[: fit_data.kp_data.shape[0]]
     # multi-GPU: rank 0 holds the gathered result and writes it
     fit_offsets_path = _write_result(stac, cfg, fit_data, fit_offsets_path, report, dist.world()[0] == 0)
     print(f"saved fit to {fit_offsets_path}", flush=True)
@@ -89,7 +96,7 @@ def _run_fit(stac, cfg, series, fit_offsets_path, report) -> Path:
 def _run_ik(stac, series, fit_offsets_path, ik_only_path, pre, start):
     """``ik_only`` on the whole series with the offsets of the fit file, the host post-processing and the result file(s) -> what
     ``run_stac`` returns."""
-    kp_data, kp_gap, kp_rejected, kp_pairwise = series
+    kp_data, kp_gap, kp_rejected, kp_pairwise, kp_swapped = series
     cfg = pre.cfg  # the caller's, until the fit file is read back
     if kp_data.shape[0] % cfg.stac.n_frames_per_clip != 0:
         raise ValueError(
@@ -131,6 +138,8 @@ def _run_ik(stac, series, fit_offsets_path, ik_only_path, pre, start):
             ik_data.kp_rejected = kp_rejected[lo * F:hi * F]
         if kp_pairwise is not None:
             ik_data.kp_rejected_pairwise = kp_pairwise[lo * F:hi * F]
+    if kp_swapped is not None:  # (sliced like kp_rejected_pairwise; it does not need the fill)
+        ik_data.kp_swapped = kp_swapped[lo * F:hi * F]
     if sharded:
         # every rank writes ITS clips under a shard name (never a partial result under the full-run name; its report is of these
         # clips, shard reports are not merged); rank 0 adds the manifest that io.load_stac_result() reads the run back through
@@ -152,8 +161,9 @@ class _Preflight:
     stored with the fit (it decides the clip length and ``continuous`` of the ik_only run): ``fit_cfg`` is the caller's when this run
     writes the fit, else it is read from the fit file, once, and only if a refusal asks for it."""
 
-    def __init__(self, cfg, n_frames: int, fit_offsets_path):
+    def __init__(self, cfg, n_frames: int, fit_offsets_path, kp_names=None):
         self.cfg, self.n_frames, self.fit_offsets_path = cfg, int(n_frames), fit_offsets_path
+        self.kp_names = kp_names  # (None: a caller that checks a config without a run; stac.repair_swaps then names no candidates)
         self._fit_cfg = None
 
     @property
@@ -168,6 +178,7 @@ class _Preflight:
         stac = self.cfg.stac
         self.reject_mode, self.reject_args = _reject_outliers_mode(self.cfg)
         self.pairwise_mode, self.pairwise_args = _reject_pairwise_mode(self.cfg)
+        self.swaps_pairs, self.swaps_args = _repair_swaps_mode(self.cfg, self.kp_names)
         self.report = _report_mode(self.cfg)
         self.smooth = _smooth_mode(self.cfg)
         self.marker_order = not stac.skip_ik_only and bool(stac.get("reference_marker_order", False))
@@ -196,12 +207,22 @@ class _Preflight:
 
 
 def _prepare_series(stac, cfg, kp_data, pre):
-    """``stac.reject_pairwise`` (its medians want the raw series), then ``stac.reject_outliers``, then ``stac.fill_missing`` over the
+    """``stac.repair_swaps`` (on the raw series), then ``stac.reject_pairwise`` (its medians are those of the repaired series), then
+    ``stac.reject_outliers``, then ``stac.fill_missing`` over the
     WHOLE series, once, on the GPU (every rank itself: same bits) -> (kp_data, kp_gap or None, kp_rejected or None: what either
-    detector rejected, kp_rejected_pairwise or None: the pairwise detector's share).  A missing run that crosses n_fit_frames or a
+    detector rejected, kp_rejected_pairwise or None: the pairwise detector's share, kp_swapped or None: 1 for both keypoints of a
+    repaired pair).  A missing run that crosses n_fit_frames or a
     clip border is so filled from its true neighbours, and both phases see the filled array.  A rejected keypoint is three NaN,
     which the fill closes like any missing one, so kp_gap > 0 there with no further code."""
-    kp_gap = kp_rejected = kp_pairwise = kp_hampel = None
+    kp_gap = kp_rejected = kp_pairwise = kp_hampel = kp_swapped = None
+    if pre.swaps_pairs:
+        kp_data, swap_flag = stac.repair_swaps(kp_data, pre.swaps_pairs, **pre.swaps_args)
+        kp_swapped = np.zeros((kp_data.shape[0], kp_data.shape[1] // 3), np.uint8)
+        for s, (a, b) in enumerate(pre.swaps_pairs):
+            kp_swapped[:, a] = kp_swapped[:, b] = swap_flag[:, s]
+        n_fit = min(int(cfg.stac.n_fit_frames), kp_swapped.shape[0])
+        if not cfg.stac.skip_fit_offsets and n_fit > 0:
+            print(f"repair_swaps: {int(np.count_nonzero(swap_flag[:n_fit]))} (frame, pair)s of the {n_fit} fit frames were exchanged back")
     if pre.pairwise_mode != "off":
         kp_data, kp_pairwise = stac.reject_pairwise(kp_data, **pre.pairwise_args)
         kp_rejected = kp_pairwise
@@ -221,7 +242,7 @@ def _prepare_series(stac, cfg, kp_data, pre):
             if kp_hampel is not None:
                 print(f"reject_outliers: {100.0 * np.count_nonzero(kp_hampel[:n_fit]) / kp_hampel[:n_fit].size:.3f} % of the "
                       f"keypoints of the {n_fit} fit frames were rejected as outliers (and are among the filled ones)")
-    return kp_data, kp_gap, kp_rejected, kp_pairwise
+    return kp_data, kp_gap, kp_rejected, kp_pairwise, kp_swapped
 
 
 def _write_result(stac, cfg, data, path, report, writes: bool) -> Path:
@@ -320,6 +341,16 @@ def _reject_pairwise_mode(cfg) -> tuple:
     if mode != "off" and _fill_missing_mode(cfg) == "off":
         raise ValueError(PAIRWISE_NEEDS_FILL)
     return mode, {"n_sigma": n_sigma, "min_dev": min_dev, "votes": votes}
+
+
+def _repair_swaps_mode(cfg, kp_names=None) -> tuple:
+    """``stac.repair_swaps``: off (default) | lr | [[nameA, nameB], ...] -> (the candidates as index pairs into ``kp_names``, [] for
+    off, keyword arguments of ``Stac.repair_swaps`` from ``stac.swaps_nsigma`` / ``swaps_min_dev`` / ``swaps_min_bad``).
+    ``ValueError`` for a bad value of any of the four keys, for names that ``kp_names`` does not hold, for a keypoint in two pairs
+    and for ``lr`` without a left / right pair among the names.  Without ``kp_names`` only the values are checked."""
+    mode, n_sigma, min_dev, min_bad = swaps_options(cfg.stac)
+    pairs = swaps_candidates(mode, kp_names) if kp_names is not None else []
+    return pairs, {"n_sigma": n_sigma, "min_dev": min_dev, "min_bad": min_bad}
 
 
 GATHER_AUTO_MAX_BYTES = 1 << 30  # above this much output a multi-GPU run keeps per-rank shard files ("auto")

@@ -142,6 +142,34 @@ class Stac:
                       f"{kp.shape[0]} frames rejected ({100.0 * int(count[k]) / kp.shape[0]:.3f} %)")
         return out.cpu().numpy(), flag.cpu().numpy()
 
+    # -- repair_swaps (engine extension; DESIGN.md "Repairing keypoint swaps") -------------------------------------------
+    def repair_swaps(self, kp_data, pairs=None, n_sigma=6.0, min_dev=0.002, min_bad=3):
+        """Exchanges back keypoints that carry each other's label, over the whole series ``kp_data`` [T, 3K] on the GPU
+        (``prep.repair_swaps``) -> ``(out [T, 3K] float32, flag [T, S] uint8)`` as numpy arrays: ``flag[t, s]`` is 1 where the two
+        keypoints of candidate ``s`` were exchanged in frame ``t``; everything else is the input bit for bit and no NaN is made.
+        ``pairs``: the candidates as pairs of keypoint indices or names (None: the left / right pairs that ``config.lr_pairs``
+        finds in the keypoint names).  One log line per candidate that had swaps."""
+        from . import prep
+        from .config import lr_pairs, named_pairs
+
+        prep.swaps_params(n_sigma, min_dev, min_bad)
+        names = list(self._kp_names)
+        if pairs is None:
+            cand = lr_pairs(names)
+        elif all(isinstance(v, str) for p in pairs for v in p):
+            cand = named_pairs(pairs, names)
+        else:
+            cand = pairs
+        cand = prep.swaps_pairs(cand, len(names))
+        kp = self._series_to_device(kp_data, "repair_swaps")
+        out, flag, _ = prep.repair_swaps(kp, cand, n_sigma, min_dev, min_bad)
+        count = flag.sum(dim=0, dtype=torch.int64).cpu().numpy()
+        for s in np.flatnonzero(count):
+            a, b = cand[s]
+            self._log(f"repair_swaps ({n_sigma} sigma, min_bad {min_bad}): {names[a]} / {names[b]}: {int(count[s])} of "
+                      f"{kp.shape[0]} frames exchanged ({100.0 * int(count[s]) / kp.shape[0]:.3f} %)")
+        return out.cpu().numpy(), flag.cpu().numpy()
+
     # -- fit_report (engine extension; DESIGN.md "Fit report") -----------------------------------------------------------
     def fit_report(self, data, permille=None, worst=None) -> dict:
         """The marker error of a result, on the GPU (``report.fit_errors``), as the summary of ``report.summarize``: per keypoint

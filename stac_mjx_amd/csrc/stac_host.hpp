@@ -143,7 +143,7 @@ struct stac_model {
     int32_t *d_ctl = nullptr;    // straggler hand-off: {finished, threshold, handed off, capacity}
     float *d_hand = nullptr;     // [hand_cap][3 nqpad + 12] solver states in transit
     int hand_cap = 0;
-    float *d_scratch = nullptr;  // grown on demand (xpos/xquat when the caller does not want them)
+    float *d_scratch = nullptr;  // unused: fk_kernel keeps the outputs a caller does not want in LDS, nothing grows this any more
     size_t scratch_floats = 0;
     int max_depth = 0;
     FullModel full() const {

@@ -283,9 +283,9 @@ static int plan_q(const stac_model *m, const stac_q_params *p, const QArgs &req,
                  hb, free0b, flags_b);
         }
         if (dbg.verbose) {
-            fprintf(stderr, "[stac] q_phase: chains=%d G=%d%s wpb=%d wpe=%d waves/CU=%d lds=%zu B/block chain_stride=%d floats plan=%d words queue=%d handoff=%d threshold=%d inst={%d,%d,%d,%d}\n",
+            fprintf(stderr, "[stac] q_phase: chains=%d G=%d%s wpb=%d wpe=%d waves/CU=%d lds=%zu B/block chain_stride=%d floats plan=%d words queue=%d handoff=%d threshold=%d keep_perm=%d keep_place=%d launch_root_fast=%d inst={%d,%d,%d,%d}\n",
                     nchains, G, lean ? " (lean)" : "", sh.wpb, sh.wpe, sh.waves_per_cu, L.lds, L.h.chain_stride, L.h.total_words - L.h.plan_skip,
-                    qslots, hcap, pl.threshold, L.inst.G, L.inst.nqr, L.inst.wpe, L.inst.specp);
+                    qslots, hcap, pl.threshold, (L.keep_perm && req.perm) ? 1 : 0, (L.keep_place && req.place) ? 1 : 0, L.root_fast, L.inst.G, L.inst.nqr, L.inst.wpe, L.inst.specp);
             if (L.keep_place && req.place) fprintf(stderr, "[stac] q_phase: chains placed by SIMD load (crowded = %d wavefronts or more)\n", L.place_crowded);
         }
         return STAC_OK;
@@ -749,6 +749,8 @@ extern "C" int32_t stac_q_phase(const stac_model *mc, const stac_q_params *p, co
         HIP_TRY(launch_chain_order(kp, C, F, K, rest, d_kpw, root_kp_idx, q0h[0], q0h[1], q0h[2], hist, keybits, perm, place, s));
         a.perm = perm; a.place = place;
     }
+    if (m->dbg.verbose)
+        fprintf(stderr, "[stac] q_phase: root program n_mlev=%d fk3r=%d root_fast=%d chain_order=%d order_chains=%zu\n", a.n_mlev_root, a.fk3r_n, a.root_fast, a.perm ? 1 : 0, m->order_chains);
     a.qpos_out = qpos_out; a.err_out = err_out; a.counters_out = counters_out; a.q_carry_out = q_carry_out;
     a.kpw_sorted = d_kpw + K;
     const int rc = p->solver == STAC_SOLVER_LM ? run_q_lm(m, p, a, C, hostm.data(), s) : run_q(m, p, a, C, s);

@@ -283,9 +283,9 @@ static int plan_q(const stac_model *m, const stac_q_params *p, const QArgs &req,
                  hb, free0b, flags_b);
         }
         if (dbg.verbose) {
-            fprintf(stderr, "[stac] q_phase: chains=%d G=%d%s wpb=%d wpe=%d waves/CU=%d lds=%zu B/block chain_stride=%d floats plan=%d words queue=%d handoff=%d threshold=%d keep_perm=%d keep_place=%d launch_root_fast=%d inst={%d,%d,%d,%d}\n",
+            fprintf(stderr, "[stac] q_phase: chains=%d G=%d%s wpb=%d wpe=%d waves/CU=%d lds=%zu B/block chain_stride=%d floats plan=%d words queue=%d handoff=%d threshold=%d keep_perm=%d keep_place=%d launch_root_fast=%d flags=%d inst={%d,%d,%d,%d}\n",
                     nchains, G, lean ? " (lean)" : "", sh.wpb, sh.wpe, sh.waves_per_cu, L.lds, L.h.chain_stride, L.h.total_words - L.h.plan_skip,
-                    qslots, hcap, pl.threshold, (L.keep_perm && req.perm) ? 1 : 0, (L.keep_place && req.place) ? 1 : 0, L.root_fast, L.inst.G, L.inst.nqr, L.inst.wpe, L.inst.specp);
+                    qslots, hcap, pl.threshold, (L.keep_perm && req.perm) ? 1 : 0, (L.keep_place && req.place) ? 1 : 0, L.root_fast, L.flags, L.inst.G, L.inst.nqr, L.inst.wpe, L.inst.specp);
             if (L.keep_place && req.place) fprintf(stderr, "[stac] q_phase: chains placed by SIMD load (crowded = %d wavefronts or more)\n", L.place_crowded);
         }
         return STAC_OK;

@@ -34,6 +34,12 @@ Fixtures are DATA only (inputs / expected outputs / compiled model tables), no r
                             frame of tests/data/test_synth_1_frames.nwb through load_data semantics, float32 [1, 3] (read
                             under /opt/conda/bin/python3.9 like the mouse mocap).  Written deterministically (fixed zip
                             timestamps), so that `--only synth` reproduces them byte for byte.
+  celegans_tables.npz / celegans_model_cfg.json
+                            models/celegans/celegans.xml with the keypoint sites of configs/model/celegans.yaml (a serial chain of
+                            25 bodies, 24 hinges under a free joint: nq = 31, K = 25; no root keypoint, no trunk keypoints, five
+                            part groups that match no joint); the model group under "model" and the stac group of
+                            configs/stac/stac_celegans.yaml under "stac".  The reference ships no C. elegans recording: the tests
+                            make their keypoints themselves.  Written deterministically (`--only celegans`).
   render_ref_digests.json   SHA-256 of rgb, seg, depth and amb of the mesh-free render scenes of
                             tests/render_cases.py::pinned_scenes, float and double build of the CPU restatement of the render
                             kernel (`--only render_digests`; needs no reference checkout).  The committed file was made at
@@ -115,6 +121,23 @@ def synth_fixtures(ref: Path):
     subprocess.run(["/opt/conda/bin/python3.9", "-c", code, str(ROOT), str(ref), str(HERE / "synth_kp_1.npy")], check=True)
 
 
+def celegans_fixtures(ref: Path):
+    """The one shipped model config without a recording: the tables and the two config groups."""
+    import yaml
+
+    model = yaml.safe_load(open(ref / "configs" / "model" / "celegans.yaml"))
+    stac = yaml.safe_load(open(ref / "configs" / "stac" / "stac_celegans.yaml"))
+    names = list(model["KEYPOINT_MODEL_PAIRS"].keys())
+    fs = build_fit_setup(ref / model["MJCF_PATH"], model, names)
+    t = fs.tables
+    assert (t.nbody, t.njnt, t.nq, t.nsite) == (26, 25, 31, 25)
+    assert fs.part_masks.shape == (5, 31) and not fs.part_masks.any() and fs.root_kp_idx == -1 and not fs.trunk_kps.any()
+    _save_npz_deterministic(HERE / "celegans_tables.npz", t.to_npz_dict())
+    with open(HERE / "celegans_model_cfg.json", "w") as fh:
+        json.dump({"model": model, "stac": stac}, fh, indent=1)
+        fh.write("\n")
+
+
 RENDER_DIGESTS_MADE_BY = ("tests/golden/make_fixtures.py --only render_digests at commit 045d64a, from that commit's mesh-free "
                           "tests/tools/render_ref.c; regenerated only when the frame rule is changed on purpose")
 
@@ -139,8 +162,8 @@ def render_digests():
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reference", default="/root/reference")
-    ap.add_argument("--only", choices=("all", "synth", "render_digests"), default="all",
-                    help="synth: write only the three synth fixtures (the others carry zip timestamps); "
+    ap.add_argument("--only", choices=("all", "synth", "celegans", "render_digests"), default="all",
+                    help="synth / celegans: write only the synth / C. elegans fixtures (the others carry zip timestamps); "
                          "render_digests: write only render_ref_digests.json (not part of `all`)")
     args = ap.parse_args()
     if args.only == "render_digests":
@@ -151,6 +174,10 @@ def main():
     if args.only == "synth":
         synth_fixtures(ref)
         print("synth fixtures written to", HERE)
+        return
+    if args.only == "celegans":
+        celegans_fixtures(ref)
+        print("celegans fixtures written to", HERE)
         return
 
     # 1. stored reference output -------------------------------------------------------------
@@ -227,6 +254,9 @@ def main():
 
     # 6. the reference's CI smoke case (synth) ----------------------------------------------------
     synth_fixtures(ref)
+
+    # 7. the C. elegans config (no recording) -------------------------------------------------------
+    celegans_fixtures(ref)
     print("fixtures written to", HERE)
 
 

@@ -9,6 +9,7 @@ overrides, schema check, attribute access.
 
 from __future__ import annotations
 
+import math
 from pathlib import Path
 from typing import Any, Iterable
 
@@ -59,6 +60,32 @@ class ConfigError(ValueError):
     pass
 
 
+INT32_MAX = 2**31 - 1  # what a count that crosses the C ABI as int32_t holds
+
+
+def checked_number(v, name, exc, positive: bool = False) -> float:
+    """``v`` as a float if it is a finite number (no bool) >= 0, or > 0 with ``positive``; else ``exc`` with "<name> must be ...".
+    The one value check of the ``*_options`` below (name: ``stac.<key>``, ConfigError) and of ``prep.*_params`` (name:
+    ``<function>: <parameter>``, ValueError)."""
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0 or (positive and not v > 0):
+        raise exc(f"{name} must be a finite number {'> 0' if positive else '>= 0'}, not {v!r}")
+    return float(v)
+
+
+def checked_int(v, name, exc, lo: int, hi=None, text=None) -> int:
+    """``v`` if it is an integer (no bool) in ``lo .. hi`` (``hi`` None: no upper bound); else ``exc`` with "<name> must be <text>":
+    ``text`` is "an integer in lo .. hi" or "an integer >= lo" unless given."""
+    if isinstance(v, bool) or not isinstance(v, int) or v < lo or (hi is not None and v > hi):
+        text = text or (f"an integer >= {lo}" if hi is None else f"an integer in {lo} .. {hi}")
+        raise exc(f"{name} must be {text}, not {v!r}")
+    return v
+
+
+def _sigma_options(stac, defaults, prefix) -> list:
+    """``stac.<prefix>_nsigma`` and ``stac.<prefix>_min_dev`` (absent: their defaults) as floats."""
+    return [checked_number(stac.get(key, defaults[key]), f"stac.{key}", ConfigError) for key in (prefix + "_nsigma", prefix + "_min_dev")]
+
+
 def _switch(stac, key):
     """``stac[key]`` of a key whose first value is ``off`` (absent: off).  YAML 1.1 reads a bare ``off`` / ``on`` as a boolean: False is
     off, and True is on for ``report``, the one key that has an ``on``.  A key without a value (None) is off, except ``fill_missing``."""
@@ -92,21 +119,13 @@ def outlier_options(stac) -> tuple:
     """``stac.reject_outliers`` and its three parameters out of a ``stac`` mapping -> (mode, half_window, n_sigma, min_dev), absent
     keys at their defaults.  ``ConfigError`` for anything else than off | hampel, a half-width that is not an integer in 1 .. 16,
     or an ``outlier_nsigma`` / ``outlier_min_dev`` that is not a finite number >= 0."""
-    import math
-
     mode = _switch(stac, "reject_outliers")
     if not isinstance(mode, str) or mode not in ("off", "hampel"):
         raise ConfigError(f"stac.reject_outliers must be off or hampel, not {mode!r}")
-    h = stac.get("outlier_window", OUTLIER_DEFAULTS["outlier_window"])
-    if isinstance(h, bool) or not isinstance(h, int) or not 1 <= h <= OUTLIER_MAX_WINDOW:
-        raise ConfigError(f"stac.outlier_window (the half-width in frames) must be an integer in 1 .. {OUTLIER_MAX_WINDOW}, not {h!r}")
-    vals = []
-    for key in ("outlier_nsigma", "outlier_min_dev"):
-        v = stac.get(key, OUTLIER_DEFAULTS[key])
-        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
-            raise ConfigError(f"stac.{key} must be a finite number >= 0, not {v!r}")
-        vals.append(float(v))
-    return mode, h, vals[0], vals[1]
+    h = checked_int(stac.get("outlier_window", OUTLIER_DEFAULTS["outlier_window"]), "stac.outlier_window (the half-width in frames)",
+                    ConfigError, 1, OUTLIER_MAX_WINDOW)
+    n_sigma, min_dev = _sigma_options(stac, OUTLIER_DEFAULTS, "outlier")
+    return mode, h, n_sigma, min_dev
 
 
 PAIRWISE_DEFAULTS = {"pairwise_nsigma": 6.0, "pairwise_min_dev": 0.002, "pairwise_votes": 2}
@@ -120,21 +139,13 @@ def pairwise_options(stac) -> tuple:
     at their defaults.  ``ConfigError`` for anything else than off | mad (a bare YAML ``off`` arrives as False), a
     ``pairwise_nsigma`` / ``pairwise_min_dev`` (units of kp_data) that is not a finite number >= 0, or a ``pairwise_votes`` that
     is not an integer >= 1."""
-    import math
-
     mode = _switch(stac, "reject_pairwise")
     if not isinstance(mode, str) or mode not in ("off", "mad"):
         raise ConfigError(f"stac.reject_pairwise must be off or mad, not {mode!r}")
-    vals = []
-    for key in ("pairwise_nsigma", "pairwise_min_dev"):
-        v = stac.get(key, PAIRWISE_DEFAULTS[key])
-        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
-            raise ConfigError(f"stac.{key} must be a finite number >= 0, not {v!r}")
-        vals.append(float(v))
-    votes = stac.get("pairwise_votes", PAIRWISE_DEFAULTS["pairwise_votes"])
-    if isinstance(votes, bool) or not isinstance(votes, int) or not 1 <= votes <= 2**31 - 1:
-        raise ConfigError(f"stac.pairwise_votes must be an integer >= 1, not {votes!r}")
-    return mode, vals[0], vals[1], votes
+    n_sigma, min_dev = _sigma_options(stac, PAIRWISE_DEFAULTS, "pairwise")
+    votes = checked_int(stac.get("pairwise_votes", PAIRWISE_DEFAULTS["pairwise_votes"]), "stac.pairwise_votes", ConfigError, 1, INT32_MAX,
+                        "an integer >= 1")
+    return mode, n_sigma, min_dev, votes
 
 
 SWAPS_DEFAULTS = {"swaps_nsigma": 6.0, "swaps_min_dev": 0.002, "swaps_min_bad": 3}
@@ -186,8 +197,6 @@ def swaps_options(stac) -> tuple:
     names: ``lr_pairs``) or a list of ``[nameA, nameB]`` pairs.  ``ConfigError`` for anything else, a ``swaps_nsigma`` /
     ``swaps_min_dev`` (units of kp_data) that is not a finite number >= 0, or a ``swaps_min_bad`` that is not an integer >= 1.
     Whether the names exist is for ``swaps_candidates``, which knows the keypoints."""
-    import math
-
     mode = _switch(stac, "repair_swaps")
     if isinstance(mode, (list, tuple)):
         if not mode:
@@ -200,16 +209,10 @@ def swaps_options(stac) -> tuple:
         mode = pairs
     elif not isinstance(mode, str) or mode not in ("off", "lr"):
         raise ConfigError(f"stac.repair_swaps must be off, lr or a list of [nameA, nameB] pairs, not {mode!r}")
-    vals = []
-    for key in ("swaps_nsigma", "swaps_min_dev"):
-        v = stac.get(key, SWAPS_DEFAULTS[key])
-        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
-            raise ConfigError(f"stac.{key} must be a finite number >= 0, not {v!r}")
-        vals.append(float(v))
-    min_bad = stac.get("swaps_min_bad", SWAPS_DEFAULTS["swaps_min_bad"])
-    if isinstance(min_bad, bool) or not isinstance(min_bad, int) or not 1 <= min_bad <= 2**31 - 1:
-        raise ConfigError(f"stac.swaps_min_bad must be an integer >= 1, not {min_bad!r}")
-    return mode, vals[0], vals[1], min_bad
+    n_sigma, min_dev = _sigma_options(stac, SWAPS_DEFAULTS, "swaps")
+    min_bad = checked_int(stac.get("swaps_min_bad", SWAPS_DEFAULTS["swaps_min_bad"]), "stac.swaps_min_bad", ConfigError, 1, INT32_MAX,
+                          "an integer >= 1")
+    return mode, n_sigma, min_dev, min_bad
 
 
 def swaps_candidates(mode, kp_names) -> list:
@@ -243,9 +246,7 @@ def report_options(stac) -> tuple:
     for v in q:
         if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= 1000:
             raise ConfigError(f"stac.report_quantiles holds permille values, integers in 0 .. 1000, not {v!r}")
-    w = stac.get("report_worst", REPORT_DEFAULTS["report_worst"])
-    if isinstance(w, bool) or not isinstance(w, int) or w < 0:
-        raise ConfigError(f"stac.report_worst must be an integer >= 0, not {w!r}")
+    w = checked_int(stac.get("report_worst", REPORT_DEFAULTS["report_worst"]), "stac.report_worst", ConfigError, 0)
     return mode == "on", tuple(q), w
 
 
@@ -259,26 +260,21 @@ def smooth_options(stac) -> dict:
     than off | savgol | gaussian (a bare YAML ``off`` arrives as False), a half-width that is not an integer in 1 .. 16, an order
     outside 0 .. 2 H, a sigma that is not a finite number > 0, and for smoothing without ``postprocess: gpu`` (there is no host
     path) or with ``reference_marker_order: true`` (the rows of marker_sites must be the rows of qpos)."""
-    import math
-
     kind = _switch(stac, "smooth")
     if not isinstance(kind, str) or kind not in ("off", "savgol", "gaussian"):
         raise ConfigError(f"stac.smooth must be off, savgol or gaussian, not {kind!r}")
-    h = stac.get("smooth_window", SMOOTH_DEFAULTS["smooth_window"])
-    if isinstance(h, bool) or not isinstance(h, int) or not 1 <= h <= SMOOTH_MAX_WINDOW:
-        raise ConfigError(f"stac.smooth_window (the half-width in frames) must be an integer in 1 .. {SMOOTH_MAX_WINDOW}, not {h!r}")
-    order = stac.get("smooth_order", SMOOTH_DEFAULTS["smooth_order"])
-    if isinstance(order, bool) or not isinstance(order, int) or order < 0 or (kind == "savgol" and order > 2 * h):
-        raise ConfigError(f"stac.smooth_order must be an integer with 0 <= order < {2 * h + 1} (the window), not {order!r}")
-    sigma = stac.get("smooth_sigma", h / 2.0)
-    if isinstance(sigma, bool) or not isinstance(sigma, (int, float)) or not math.isfinite(sigma) or not sigma > 0:
-        raise ConfigError(f"stac.smooth_sigma (in frames) must be a finite number > 0, not {sigma!r}")
+    h = checked_int(stac.get("smooth_window", SMOOTH_DEFAULTS["smooth_window"]), "stac.smooth_window (the half-width in frames)",
+                    ConfigError, 1, SMOOTH_MAX_WINDOW)
+    # (the order is held to the window for savgol only: gaussian does not read it)
+    order = checked_int(stac.get("smooth_order", SMOOTH_DEFAULTS["smooth_order"]), "stac.smooth_order", ConfigError, 0,
+                        2 * h if kind == "savgol" else None, f"an integer with 0 <= order < {2 * h + 1} (the window)")
+    sigma = checked_number(stac.get("smooth_sigma", h / 2.0), "stac.smooth_sigma (in frames)", ConfigError, positive=True)
     if kind != "off":
         if stac.get("postprocess", "host") != "gpu":
             raise ConfigError(f"stac.smooth = {kind} runs on the device only (there is no host path for smoothing): set stac.postprocess to gpu as well")
         if bool(stac.get("reference_marker_order", False)):
             raise ConfigError(smooth_marker_order_refusal(kind))
-    return {"kind": kind, "half_window": h, "order": order if kind == "savgol" else None, "sigma": float(sigma) if kind == "gaussian" else None}
+    return {"kind": kind, "half_window": h, "order": order if kind == "savgol" else None, "sigma": sigma if kind == "gaussian" else None}
 
 
 # Refusals that both run_stac (before any work) and Stac.ik_only (for its direct callers) raise: one text each

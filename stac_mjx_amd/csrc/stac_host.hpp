@@ -54,6 +54,10 @@ struct DeviceGuard {
 // one that was not given) overlaps nothing.
 struct HostBuf { const char *name; uintptr_t lo; int64_t bytes; int align; };
 bool find_overlap(const HostBuf *buf, int n, const HostBuf **a, const HostBuf **b);
+// The check of a whole argument list: STAC_OK, or fail(STAC_ERR_INVALID, ...) for the first buffer whose address is not a multiple of its
+// align ("<who>: <name> must be <align>-byte aligned"), else for the first overlapping pair ("<who>: <a> and <b> overlap: inputs, outputs
+// and workspace are distinct buffers" + tail)
+int check_buffers(const char *who, const HostBuf *buf, int n, const char *tail = "");
 
 // Developer switches: read from the environment ONCE, at stac_model_create, so that a variable
 // set later cannot change the launch shape of a model in use.  -1 = not set.

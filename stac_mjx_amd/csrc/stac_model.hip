@@ -25,6 +25,17 @@ bool find_overlap(const HostBuf *buf, int n, const HostBuf **a, const HostBuf **
     return false;
 }
 
+int check_buffers(const char *who, const HostBuf *buf, int n, const char *tail) {
+    for (int i = 0; i < n; ++i)
+        if (buf[i].lo % buf[i].align != 0)
+            return fail(STAC_ERR_INVALID, std::string(who) + ": " + buf[i].name + " must be " + std::to_string(buf[i].align) + "-byte aligned");
+    const HostBuf *a, *b;
+    if (find_overlap(buf, n, &a, &b))
+        return fail(STAC_ERR_INVALID, std::string(who) + ": " + a->name + " and " + b->name +
+                                          " overlap: inputs, outputs and workspace are distinct buffers" + tail);
+    return STAC_OK;
+}
+
 extern "C" const char *stac_last_error(void) { return g_err.c_str(); }
 extern "C" int32_t stac_last_error_code(void) { return g_err_code; }
 extern "C" int32_t stac_abi_version(void) { return STAC_HIP_ABI_VERSION; }

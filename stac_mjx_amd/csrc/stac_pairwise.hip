@@ -405,36 +405,48 @@ extern "C" int64_t stac_prep_pairwise_workspace(int64_t n_frames, int32_t n_kp) 
     return L.bytes;
 }
 
+// The argument checks that stac_prep_pairwise and stac_prep_swaps share, in the order both make them: sizes, capacity (`holds`: what
+// the message says the keypoints are limited by), layout, then `own()`, the entry point's checks of what it alone takes, then thr /
+// min_dev, the count (votes / min_bad), null pointers, workspace size, and alignment and overlap of the buffers (flag: flag_cols bytes
+// per frame).  STAC_OK, or the status of the first check that fails.
+template <class Own>
+static int32_t check_pairwise_args(const std::string &fn, const char *holds, const float *kp, int64_t n_frames, int32_t n_kp, double thr,
+                                   double min_dev, const char *count_name, int32_t count, const float *out, const uint8_t *flag,
+                                   int64_t flag_cols, const int64_t *pair_n, const double *pair_med, const double *pair_mad,
+                                   const void *workspace, int64_t workspace_bytes, Own own) {
+    if (n_frames < 1 || n_kp < 1) return fail(STAC_ERR_INVALID, fn + ": n_frames >= 1, n_kp >= 1");
+    if (n_kp > kPairwiseMaxKp)
+        return fail(STAC_ERR_CAPACITY, fn + ": n_kp = " + std::to_string(n_kp) + " is above the " + std::to_string(kPairwiseMaxKp) + " keypoints " +
+                                           holds);
+    const PairwiseLayout L = pairwise_layout(n_frames, n_kp);
+    if (L.bytes < 0) return fail(STAC_ERR_INVALID, fn + ": array sizes beyond int64");
+    if (const int32_t rc = own()) return rc;
+    if (!std::isfinite(thr) || thr < 0.0 || !std::isfinite(min_dev) || min_dev < 0.0)
+        return fail(STAC_ERR_INVALID, fn + ": thr and min_dev must be finite and >= 0");
+    if (count < 1) return fail(STAC_ERR_INVALID, fn + ": " + count_name + " = " + std::to_string(count) + " must be >= 1");
+    if (!kp || !out || !flag || !pair_n || !pair_med || !pair_mad || !workspace)
+        return fail(STAC_ERR_INVALID, fn + ": null kp / out / flag / pair_n / pair_med / pair_mad / workspace");
+    if (workspace_bytes < L.bytes)
+        return fail(STAC_ERR_INVALID, fn + ": workspace_bytes = " + std::to_string(workspace_bytes) + ", " + std::to_string(L.bytes) +
+                                          " are needed (" + fn + "_workspace)");
+    const int64_t NK = n_frames * n_kp, P8 = (L.pairs > 0 ? L.pairs : 1) * 8;
+    const HostBuf buf[7] = {{"kp", (uintptr_t)kp, NK * 12, 4},
+                            {"out", (uintptr_t)out, NK * 12, 4},
+                            {"flag", (uintptr_t)flag, n_frames * flag_cols, 1},
+                            {"pair_n", (uintptr_t)pair_n, P8, 8},
+                            {"pair_med", (uintptr_t)pair_med, P8, 8},
+                            {"pair_mad", (uintptr_t)pair_mad, P8, 8},
+                            {"workspace", (uintptr_t)workspace, L.bytes, 8}};
+    return check_buffers(fn.c_str(), buf, 7, " (in place is not possible)");
+}
+
 extern "C" int32_t stac_prep_pairwise(const float *kp, int64_t n_frames, int32_t n_kp, double thr, double min_dev, int32_t votes, float *out,
                                       uint8_t *flag, int64_t *pair_n, double *pair_med, double *pair_mad, void *workspace,
                                       int64_t workspace_bytes, void *stream) {
-    if (n_frames < 1 || n_kp < 1) return fail(STAC_ERR_INVALID, "stac_prep_pairwise: n_frames >= 1, n_kp >= 1");
-    if (n_kp > kPairwiseMaxKp)
-        return fail(STAC_ERR_CAPACITY, "stac_prep_pairwise: n_kp = " + std::to_string(n_kp) + " is above the " + std::to_string(kPairwiseMaxKp) +
-                                           " keypoints that a frame's words of 64 bits hold");
-    const PairwiseLayout L = pairwise_layout(n_frames, n_kp);
-    if (L.bytes < 0) return fail(STAC_ERR_INVALID, "stac_prep_pairwise: array sizes beyond int64");
-    if (!std::isfinite(thr) || thr < 0.0 || !std::isfinite(min_dev) || min_dev < 0.0)
-        return fail(STAC_ERR_INVALID, "stac_prep_pairwise: thr and min_dev must be finite and >= 0");
-    if (votes < 1) return fail(STAC_ERR_INVALID, "stac_prep_pairwise: votes = " + std::to_string(votes) + " must be >= 1");
-    if (!kp || !out || !flag || !pair_n || !pair_med || !pair_mad || !workspace)
-        return fail(STAC_ERR_INVALID, "stac_prep_pairwise: null kp / out / flag / pair_n / pair_med / pair_mad / workspace");
-    if (workspace_bytes < L.bytes)
-        return fail(STAC_ERR_INVALID, "stac_prep_pairwise: workspace_bytes = " + std::to_string(workspace_bytes) + ", " + std::to_string(L.bytes) +
-                                          " are needed (stac_prep_pairwise_workspace)");
-    const int64_t NK = n_frames * n_kp, P8 = (L.pairs > 0 ? L.pairs : 1) * 8;
-    const HostBuf buf[7] = {{"kp", (uintptr_t)kp, NK * 12, 4},          {"out", (uintptr_t)out, NK * 12, 4},
-                            {"flag", (uintptr_t)flag, NK, 1},           {"pair_n", (uintptr_t)pair_n, P8, 8},
-                            {"pair_med", (uintptr_t)pair_med, P8, 8},   {"pair_mad", (uintptr_t)pair_mad, P8, 8},
-                            {"workspace", (uintptr_t)workspace, L.bytes, 8}};
-    for (int i = 0; i < 7; ++i)
-        if (buf[i].lo % buf[i].align != 0)
-            return fail(STAC_ERR_INVALID, std::string("stac_prep_pairwise: ") + buf[i].name + " must be " + std::to_string(buf[i].align) +
-                                              "-byte aligned");
-    const HostBuf *a, *b;
-    if (find_overlap(buf, 7, &a, &b))
-        return fail(STAC_ERR_INVALID, std::string("stac_prep_pairwise: ") + a->name + " and " + b->name +
-                                          " overlap: inputs, outputs and workspace are distinct buffers (in place is not possible)");
+    if (const int32_t rc = check_pairwise_args("stac_prep_pairwise", "that a frame's words of 64 bits hold", kp, n_frames, n_kp, thr, min_dev,
+                                               "votes", votes, out, flag, n_kp, pair_n, pair_med, pair_mad, workspace, workspace_bytes,
+                                               [] { return (int32_t)STAC_OK; }))
+        return rc;
     return launch_result("stac_prep_pairwise", launch_pairwise(kp, n_frames, n_kp, thr, min_dev, votes, out, flag, pair_n, pair_med, pair_mad,
                                                                workspace, (hipStream_t)stream));
 }
@@ -452,47 +464,24 @@ extern "C" int64_t stac_prep_swaps_workspace(int64_t n_frames, int32_t n_kp) {
 extern "C" int32_t stac_prep_swaps(const float *kp, int64_t n_frames, int32_t n_kp, const int32_t *cand, int32_t n_cand, double thr,
                                    double min_dev, int32_t min_bad, float *out, uint8_t *flag, int64_t *pair_n, double *pair_med,
                                    double *pair_mad, void *workspace, int64_t workspace_bytes, void *stream) {
-    if (n_frames < 1 || n_kp < 1) return fail(STAC_ERR_INVALID, "stac_prep_swaps: n_frames >= 1, n_kp >= 1");
-    if (n_kp > kPairwiseMaxKp)
-        return fail(STAC_ERR_CAPACITY, "stac_prep_swaps: n_kp = " + std::to_string(n_kp) + " is above the " + std::to_string(kPairwiseMaxKp) +
-                                           " keypoints of the pairwise statistics");
-    const PairwiseLayout L = pairwise_layout(n_frames, n_kp);
-    if (L.bytes < 0) return fail(STAC_ERR_INVALID, "stac_prep_swaps: array sizes beyond int64");
-    if (n_cand < 0) return fail(STAC_ERR_INVALID, "stac_prep_swaps: n_cand = " + std::to_string(n_cand) + " must be >= 0");
-    if (n_cand > 0 && !cand) return fail(STAC_ERR_INVALID, "stac_prep_swaps: null cand with n_cand > 0");
     SwapCands cands;
-    int32_t at = 0;
-    const int bad = swap_pack(cand, n_cand, n_kp, &cands, &at);  // (cand is host memory)
-    if (bad) {
-        const char *why[] = {"", "has a keypoint outside 0 .. n_kp - 1", "names one keypoint twice (a == b)",
-                             "has a keypoint that an earlier candidate holds", "is one more than n_kp / 2 candidates can be"};
-        return fail(STAC_ERR_INVALID, "stac_prep_swaps: candidate " + std::to_string(at) + " (" + std::to_string(cand[2 * at]) + ", " +
-                                          std::to_string(cand[2 * at + 1]) + ") " + why[bad]);
-    }
-    if (!std::isfinite(thr) || thr < 0.0 || !std::isfinite(min_dev) || min_dev < 0.0)
-        return fail(STAC_ERR_INVALID, "stac_prep_swaps: thr and min_dev must be finite and >= 0");
-    if (min_bad < 1) return fail(STAC_ERR_INVALID, "stac_prep_swaps: min_bad = " + std::to_string(min_bad) + " must be >= 1");
-    if (!kp || !out || !flag || !pair_n || !pair_med || !pair_mad || !workspace)
-        return fail(STAC_ERR_INVALID, "stac_prep_swaps: null kp / out / flag / pair_n / pair_med / pair_mad / workspace");
-    if (workspace_bytes < L.bytes)
-        return fail(STAC_ERR_INVALID, "stac_prep_swaps: workspace_bytes = " + std::to_string(workspace_bytes) + ", " + std::to_string(L.bytes) +
-                                          " are needed (stac_prep_swaps_workspace)");
-    const int64_t NK = n_frames * n_kp, P8 = (L.pairs > 0 ? L.pairs : 1) * 8;
-    const HostBuf buf[7] = {{"kp", (uintptr_t)kp, NK * 12, 4},
-                            {"out", (uintptr_t)out, NK * 12, 4},
-                            {"flag", (uintptr_t)flag, n_frames * (n_cand > 0 ? n_cand : 1), 1},
-                            {"pair_n", (uintptr_t)pair_n, P8, 8},
-                            {"pair_med", (uintptr_t)pair_med, P8, 8},
-                            {"pair_mad", (uintptr_t)pair_mad, P8, 8},
-                            {"workspace", (uintptr_t)workspace, L.bytes, 8}};
-    for (int i = 0; i < 7; ++i)
-        if (buf[i].lo % buf[i].align != 0)
-            return fail(STAC_ERR_INVALID, std::string("stac_prep_swaps: ") + buf[i].name + " must be " + std::to_string(buf[i].align) +
-                                              "-byte aligned");
-    const HostBuf *a, *b;
-    if (find_overlap(buf, 7, &a, &b))
-        return fail(STAC_ERR_INVALID, std::string("stac_prep_swaps: ") + a->name + " and " + b->name +
-                                          " overlap: inputs, outputs and workspace are distinct buffers (in place is not possible)");
+    const auto candidates = [&]() -> int32_t {  // (after the sizes: swap_pack counts on 1 <= n_kp <= kPairwiseMaxKp)
+        if (n_cand < 0) return fail(STAC_ERR_INVALID, "stac_prep_swaps: n_cand = " + std::to_string(n_cand) + " must be >= 0");
+        if (n_cand > 0 && !cand) return fail(STAC_ERR_INVALID, "stac_prep_swaps: null cand with n_cand > 0");
+        int32_t at = 0;
+        const int bad = swap_pack(cand, n_cand, n_kp, &cands, &at);  // (cand is host memory)
+        if (bad) {
+            const char *why[] = {"", "has a keypoint outside 0 .. n_kp - 1", "names one keypoint twice (a == b)",
+                                 "has a keypoint that an earlier candidate holds", "is one more than n_kp / 2 candidates can be"};
+            return fail(STAC_ERR_INVALID, "stac_prep_swaps: candidate " + std::to_string(at) + " (" + std::to_string(cand[2 * at]) + ", " +
+                                              std::to_string(cand[2 * at + 1]) + ") " + why[bad]);
+        }
+        return STAC_OK;
+    };
+    if (const int32_t rc = check_pairwise_args("stac_prep_swaps", "of the pairwise statistics", kp, n_frames, n_kp, thr, min_dev, "min_bad",
+                                               min_bad, out, flag, n_cand > 0 ? n_cand : 1, pair_n, pair_med, pair_mad, workspace,
+                                               workspace_bytes, candidates))
+        return rc;
     return launch_result("stac_prep_swaps", launch_swaps(kp, n_frames, n_kp, cands, n_cand, thr, min_dev, min_bad, out, flag, pair_n, pair_med,
                                                          pair_mad, workspace, (hipStream_t)stream));
 }

@@ -333,14 +333,7 @@ extern "C" int32_t stac_report_errors(const stac_report_params *p) {
         {"frame_n", (uintptr_t)p->frame_n, p->n_frames * 4, 4}, {"count", (uintptr_t)p->count, K * 8, 8}, {"sum", (uintptr_t)p->sum, K * 8, 8},
         {"max", (uintptr_t)p->max, K * 4, 4}, {"argmax", (uintptr_t)p->argmax, K * 8, 8}, {"hist", (uintptr_t)p->hist, K * kReportBins0 * 8, 8},
         {"quant", (uintptr_t)p->quant, K * Q * 4, 4}, {"workspace", (uintptr_t)p->workspace, L.bytes, 8}};
-    for (int i = 0; i < 13; ++i)
-        if (buf[i].lo % buf[i].align != 0)
-            return fail(STAC_ERR_INVALID, std::string("stac_report_errors: ") + buf[i].name + " must be " + std::to_string(buf[i].align) +
-                                              "-byte aligned");
-    const HostBuf *a, *b;
-    if (find_overlap(buf, 13, &a, &b))  // (gap == NULL: zero bytes, overlaps nothing)
-        return fail(STAC_ERR_INVALID, std::string("stac_report_errors: ") + a->name + " and " + b->name +
-                                          " overlap: inputs, outputs and workspace are distinct buffers");
+    if (const int rc = check_buffers("stac_report_errors", buf, 13)) return rc;  // (gap == NULL: zero bytes, overlaps nothing)
     return launch_result("stac_report_errors",
                          launch_report_errors(p->markers, p->kp, p->gap, p->n_frames, p->n_kp, p->n_quant, p->permille, p->sqerr, p->frame_sse,
                                               p->frame_n, p->count, p->sum, p->max, p->argmax, p->hist, p->quant, p->workspace,

@@ -26,6 +26,13 @@ except Exception:  # pragma: no cover - depends on the image
     h5py = None
 
 
+# The optional result fields (engine extensions) as (name, the dtype save_data_to_h5 writes them with or None: as given), in the order
+# of their datasets in a result file.  Each is a StacData field that is empty without its option, and is then neither in as_dict()
+# nor in the file; as_dict, save_data_to_h5, load_stac_data and load_sharded_stac_data go by this table.
+OPTIONAL_FIELDS = (("kp_gap", None), ("kp_rejected", np.uint8), ("qpos_raw", None), ("kp_rejected_pairwise", np.uint8),
+                   ("kp_swapped", np.uint8))
+
+
 @dataclass
 class StacData:
     """Output record (same fields as ``stac_mjx.io.StacData``)."""
@@ -59,9 +66,9 @@ class StacData:
     kp_rejected: np.ndarray = field(default_factory=lambda: np.array([]))
 
     def as_dict(self) -> dict:
-        """The fields as ``save_data_to_h5`` takes them (an empty ``kp_gap`` / ``kp_rejected`` / ``kp_rejected_pairwise`` / ``kp_swapped`` / ``qpos_raw`` is left out: the reference's fields alone)."""
+        """The fields as ``save_data_to_h5`` takes them (an empty field of ``OPTIONAL_FIELDS`` is left out: the reference's fields alone)."""
         d = asdict(self)
-        for name in ("kp_gap", "kp_rejected", "kp_rejected_pairwise", "kp_swapped", "qpos_raw"):
+        for name, _ in OPTIONAL_FIELDS:
             if not np.asarray(d[name]).size:
                 del d[name]
         return d
@@ -375,16 +382,11 @@ def save_data_to_h5(config, kp_names, names_qpos, names_xpos, kp_data, marker_si
     cfg_yaml = config.to_yaml() if isinstance(config, ConfigNode) else yaml.safe_dump(config, sort_keys=False)
     arrays = dict(kp_data=kp_data, marker_sites=marker_sites, offsets=offsets, qpos=qpos,
                   qvel=np.asarray(qvel), xpos=xpos, xquat=xquat)  # fmt: skip
-    if kp_gap is not None and np.asarray(kp_gap).size:
-        arrays["kp_gap"] = np.asarray(kp_gap)
-    if kp_rejected is not None and np.asarray(kp_rejected).size:
-        arrays["kp_rejected"] = np.asarray(kp_rejected, dtype=np.uint8)
-    if qpos_raw is not None and np.asarray(qpos_raw).size:
-        arrays["qpos_raw"] = np.asarray(qpos_raw)
-    if kp_rejected_pairwise is not None and np.asarray(kp_rejected_pairwise).size:
-        arrays["kp_rejected_pairwise"] = np.asarray(kp_rejected_pairwise, dtype=np.uint8)
-    if kp_swapped is not None and np.asarray(kp_swapped).size:
-        arrays["kp_swapped"] = np.asarray(kp_swapped, dtype=np.uint8)
+    given = dict(kp_gap=kp_gap, kp_rejected=kp_rejected, qpos_raw=qpos_raw, kp_rejected_pairwise=kp_rejected_pairwise,
+                 kp_swapped=kp_swapped)
+    for name, dtype in OPTIONAL_FIELDS:
+        if given[name] is not None and np.asarray(given[name]).size:
+            arrays[name] = np.asarray(given[name], dtype=dtype)
     if h5py is not None and file_path.suffix in (".h5", ".hdf5"):
         with h5py.File(file_path, "w") as f, _pool() as pool:
             f.create_dataset("config", data=np.bytes_(cfg_yaml))
@@ -429,11 +431,8 @@ def load_stac_data(file_path):
     return config, StacData(
         kp_names=names(d["kp_names"]), names_qpos=names(d["names_qpos"]), names_xpos=names(d["names_xpos"]),
         kp_data=d["kp_data"], marker_sites=d["marker_sites"], offsets=d["offsets"], qpos=d["qpos"],
-        qvel=d["qvel"], xpos=d["xpos"], xquat=d["xquat"], kp_gap=d["kp_gap"] if "kp_gap" in d else np.array([]),
-        kp_rejected=d["kp_rejected"] if "kp_rejected" in d else np.array([]),
-        qpos_raw=d["qpos_raw"] if "qpos_raw" in d else np.array([]),
-        kp_rejected_pairwise=d["kp_rejected_pairwise"] if "kp_rejected_pairwise" in d else np.array([]),
-        kp_swapped=d["kp_swapped"] if "kp_swapped" in d else np.array([]))  # fmt: skip
+        qvel=d["qvel"], xpos=d["xpos"], xquat=d["xquat"],
+        **{name: d[name] if name in d else np.array([]) for name, _ in OPTIONAL_FIELDS})  # fmt: skip
 
 
 # ---- per-rank shard files of a multi-GPU ik_only run (engine extension; main.run_stac with stac.gather = none / auto) ----
@@ -482,9 +481,8 @@ def load_sharded_stac_data(manifest):
     first = parts[0]
     return cfg, StacData(qpos=cat("qpos"), xpos=cat("xpos"), xquat=cat("xquat"), marker_sites=cat("marker_sites"),
                          offsets=first.offsets, kp_data=cat("kp_data"), names_qpos=first.names_qpos,
-                         names_xpos=first.names_xpos, kp_names=first.kp_names, qvel=cat("qvel"), kp_gap=cat("kp_gap"),
-                         kp_rejected=cat("kp_rejected"), qpos_raw=cat("qpos_raw"),
-                         kp_rejected_pairwise=cat("kp_rejected_pairwise"), kp_swapped=cat("kp_swapped"))
+                         names_xpos=first.names_xpos, kp_names=first.kp_names, qvel=cat("qvel"),
+                         **{name: cat(name) for name, _ in OPTIONAL_FIELDS})
 
 
 def load_stac_result(path):

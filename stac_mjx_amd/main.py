@@ -3,6 +3,7 @@
 from __future__ import annotations
 
 import time
+from dataclasses import dataclass, field
 from pathlib import Path
 
 import numpy as np
@@ -75,18 +76,10 @@ def run_stac(cfg, kp_data, kp_names, base_path=None, *, setup=None, device=None)
 
 def _run_fit(stac, cfg, series, fit_offsets_path, report) -> Path:
     """``fit_offsets`` on the first ``n_fit_frames`` of the series and the fit file -> the name the file really has."""
-    kp_data, kp_gap, kp_rejected, kp_pairwise, kp_swapped = series
-    kps = kp_data[: cfg.stac.n_fit_frames]
+    kps = series.kp_data[: cfg.stac.n_fit_frames]
     print(f"Running fit. Mocap data shape: {kps.shape}")
     fit_data = stac.fit_offsets(kps)
-    if kp_gap is not None:  # (the rows of the fit file are the first rows of the series, in order)
-        fit_data.kp_gap = kp_gap[: fit_data.kp_data.shape[0]]
-    if kp_rejected is not None:
-        fit_data.kp_rejected = kp_rejected[: fit_data.kp_data.shape[0]]
-    if kp_pairwise is not None:
-        fit_data.kp_rejected_pairwise = kp_pairwise[: fit_data.kp_data.shape[0]]
-    if kp_swapped is not None:
-        fit_data.kp_swapped = kp_swapped[: fit_data.kp_data.shape[0]]
+    series.attach(fit_data, 0, fit_data.kp_data.shape[0])  # (the rows of the fit file are the first rows of the series, in order)
     # multi-GPU: rank 0 holds the gathered result and writes it
     fit_offsets_path = _write_result(stac, cfg, fit_data, fit_offsets_path, report, dist.world()[0] == 0)
     print(f"saved fit to {fit_offsets_path}", flush=True)
@@ -96,7 +89,7 @@ def _run_fit(stac, cfg, series, fit_offsets_path, report) -> Path:
 def _run_ik(stac, series, fit_offsets_path, ik_only_path, pre, start):
     """``ik_only`` on the whole series with the offsets of the fit file, the host post-processing and the result file(s) -> what
     ``run_stac`` returns."""
-    kp_data, kp_gap, kp_rejected, kp_pairwise, kp_swapped = series
+    kp_data = series.kp_data
     cfg = pre.cfg  # the caller's, until the fit file is read back
     if kp_data.shape[0] % cfg.stac.n_frames_per_clip != 0:
         raise ValueError(
@@ -132,14 +125,8 @@ def _run_ik(stac, series, fit_offsets_path, ik_only_path, pre, start):
         qvels = [utils.compute_velocity_from_kinematics(c, dt=stac._timestep, freejoint=stac._freejoint) for c in batched]
         ik_data.qvel = np.stack(qvels).reshape(-1, qvels[0].shape[-1])
     lo, hi = dist.shard_range(n_clips) if sharded else (0, n_clips)
-    if kp_gap is not None:  # rows of the input series, not passed through the cross-fade; a shard file carries the rows of its clips
-        ik_data.kp_gap = kp_gap[lo * F:hi * F]
-        if kp_rejected is not None:  # (handled exactly like kp_gap)
-            ik_data.kp_rejected = kp_rejected[lo * F:hi * F]
-        if kp_pairwise is not None:
-            ik_data.kp_rejected_pairwise = kp_pairwise[lo * F:hi * F]
-    if kp_swapped is not None:  # (sliced like kp_rejected_pairwise; it does not need the fill)
-        ik_data.kp_swapped = kp_swapped[lo * F:hi * F]
+    # (rows of the input series, not passed through the cross-fade; a shard file carries the rows of its clips)
+    series.attach(ik_data, lo * F, hi * F)
     if sharded:
         # every rank writes ITS clips under a shard name (never a partial result under the full-run name; its report is of these
         # clips, shard reports are not merged); rank 0 adds the manifest that io.load_stac_result() reads the run back through
@@ -206,14 +193,28 @@ class _Preflight:
         self.fill_mode = _fill_missing_mode(self.cfg)
 
 
-def _prepare_series(stac, cfg, kp_data, pre):
+@dataclass
+class _Series:
+    """What ``_prepare_series`` leaves: the prepared ``kp_data`` [T, 3K] and ``marks``, result-field name (``io.OPTIONAL_FIELDS``) ->
+    [T, K] array whose row i is about row i of the series, of the fields that this run produced alone."""
+
+    kp_data: np.ndarray
+    marks: dict = field(default_factory=dict)
+
+    def attach(self, data, lo: int, hi: int):
+        """The rows ``lo:hi`` of every mark become the field of that name of ``data`` (a ``StacData`` of those rows of the series)."""
+        for name, mark in self.marks.items():
+            setattr(data, name, mark[lo:hi])
+
+
+def _prepare_series(stac, cfg, kp_data, pre) -> _Series:
     """``stac.repair_swaps`` (on the raw series), then ``stac.reject_pairwise`` (its medians are those of the repaired series), then
-    ``stac.reject_outliers``, then ``stac.fill_missing`` over the
-    WHOLE series, once, on the GPU (every rank itself: same bits) -> (kp_data, kp_gap or None, kp_rejected or None: what either
-    detector rejected, kp_rejected_pairwise or None: the pairwise detector's share, kp_swapped or None: 1 for both keypoints of a
-    repaired pair).  A missing run that crosses n_fit_frames or a
-    clip border is so filled from its true neighbours, and both phases see the filled array.  A rejected keypoint is three NaN,
-    which the fill closes like any missing one, so kp_gap > 0 there with no further code."""
+    ``stac.reject_outliers``, then ``stac.fill_missing`` over the WHOLE series, once, on the GPU (every rank itself: same bits) -> the
+    prepared series and its marks: kp_swapped (1 for both keypoints of a repaired pair), kp_rejected_pairwise (the pairwise detector's
+    share), kp_rejected (what either detector rejected) and kp_gap, each only with its stage on.  A missing run that crosses
+    n_fit_frames or a clip border is so filled from its true neighbours, and both phases see the filled array.  A rejected keypoint is
+    three NaN, which the fill closes like any missing one, so kp_gap > 0 there with no further code (and the pre-flight refuses a
+    rejecter without the fill, so kp_rejected never comes without kp_gap)."""
     kp_gap = kp_rejected = kp_pairwise = kp_hampel = kp_swapped = None
     if pre.swaps_pairs:
         kp_data, swap_flag = stac.repair_swaps(kp_data, pre.swaps_pairs, **pre.swaps_args)
@@ -242,7 +243,8 @@ def _prepare_series(stac, cfg, kp_data, pre):
             if kp_hampel is not None:
                 print(f"reject_outliers: {100.0 * np.count_nonzero(kp_hampel[:n_fit]) / kp_hampel[:n_fit].size:.3f} % of the "
                       f"keypoints of the {n_fit} fit frames were rejected as outliers (and are among the filled ones)")
-    return kp_data, kp_gap, kp_rejected, kp_pairwise, kp_swapped
+    marks = {"kp_swapped": kp_swapped, "kp_rejected_pairwise": kp_pairwise, "kp_rejected": kp_rejected, "kp_gap": kp_gap}
+    return _Series(kp_data, {name: mark for name, mark in marks.items() if mark is not None})
 
 
 def _write_result(stac, cfg, data, path, report, writes: bool) -> Path:

@@ -9,6 +9,10 @@ A keypoint is missing in a frame when one of its coordinates is NaN or infinite.
 (``linear``: interpolation between its two valid neighbours in double; ``hold``: the nearer neighbour; leading and trailing runs
 copy their one neighbour), valid values pass bit for bit, and ``gap`` holds, per frame and keypoint, 0 or the length of the
 missing run: DESIGN.md "Filling missing keypoints".
+
+What the four wrappers share is said once: ``_series`` (the ``[T, 3K]`` argument), ``_workspace`` (size and allocation),
+``_pair_stats`` (the buffers of the pairwise statistics), ``_pair_params`` / ``_mad_threshold`` over the value checkers of
+``config``.  A fifth stage: DESIGN.md "Adding a preparation stage".
 """
 
 from __future__ import annotations
@@ -21,6 +25,7 @@ import torch
 
 from .abi import _ptr, check, device_tensor, stream_ptr
 from .abi import declare as bind  # noqa: F401  (the name callers of the raw library know: the whole table, idempotent)
+from .config import INT32_MAX, checked_int, checked_number
 from .engine import load_library
 
 TILE_FRAMES = 64    # csrc/stac_prep.hpp: kPrepTileFrames (frames of a tile of the staged scan)
@@ -39,25 +44,60 @@ def mode_code(mode) -> int:
 
 def workspace_bytes(n_frames: int, n_kp: int) -> int:
     """Bytes of device workspace of one ``stac_prep_fill`` call (host only)."""
+    return _workspace("stac_prep_fill", n_frames, n_kp)[0]
+
+
+def _series(kp, fn):
+    """-> (kp as a contiguous float32 device tensor, T, K) of the series argument [T, 3K] of the wrapper ``fn``."""
+    kp = device_tensor(kp, f"{fn} needs a CUDA tensor")
+    if kp.dim() != 2 or kp.shape[1] % 3 != 0 or kp.shape[1] == 0:
+        raise ValueError(f"{fn}: kp must be [frames, 3 * keypoints], got {tuple(kp.shape)}")
+    return kp, int(kp.shape[0]), int(kp.shape[1]) // 3
+
+
+def _workspace(entry, n_frames, n_kp, device=None):
+    """Bytes of device workspace of one call of the entry point ``entry`` (host only) and, with ``device``, that many bytes there
+    as an int64 tensor: (bytes, tensor)."""
     lib = load_library()
-    return int(check(lib, "stac_prep_fill_workspace", lib.stac_prep_fill_workspace(int(n_frames), int(n_kp))))
+    nbytes = int(check(lib, entry + "_workspace", getattr(lib, entry + "_workspace")(int(n_frames), int(n_kp))))
+    return nbytes, None if device is None else torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device)
+
+
+def _pair_stats(K, device):
+    """The statistics buffers of the K (K - 1) / 2 keypoint pairs, with room for one element also without a pair (the entry points
+    take no null pointer), and ``stats``, the views of their pairs: ``pair_n`` int64 zeros, ``pair_med`` / ``pair_mad`` float64 NaN."""
+    P = K * (K - 1) // 2
+    bufs = (torch.zeros(max(P, 1), dtype=torch.int64, device=device), torch.full((max(P, 1),), math.nan, dtype=torch.float64, device=device),
+            torch.full((max(P, 1),), math.nan, dtype=torch.float64, device=device))
+    return bufs, {name: b[:P] for name, b in zip(("pair_n", "pair_med", "pair_mad"), bufs)}
+
+
+def _mad_threshold(fn, n_sigma) -> float:
+    """``thr = n_sigma * 1.4826`` in double, as the entry points take it."""
+    thr = float(n_sigma) * MAD_TO_SIGMA
+    if not math.isfinite(thr):
+        raise ValueError(f"{fn}: n_sigma = {n_sigma!r} is too large")
+    return thr
+
+
+def _pair_params(fn, n_sigma, min_dev, count_name, count):
+    checked_number(n_sigma, f"{fn}: n_sigma", ValueError)
+    floor = checked_number(min_dev, f"{fn}: min_dev", ValueError)
+    checked_int(count, f"{fn}: {count_name}", ValueError, 1, INT32_MAX, "an integer >= 1")
+    return _mad_threshold(fn, n_sigma), floor, count
 
 
 def fill_missing(kp: torch.Tensor, mode: str = "linear"):
     """Device tensor [T, 3K] -> (filled [T, 3K] float32, gap [T, K] int32), on the current stream of its device.  The input is
     made contiguous float32 first and is never written."""
     code = mode_code(mode)
-    kp = device_tensor(kp, "fill_missing needs a CUDA tensor")
-    if kp.dim() != 2 or kp.shape[1] % 3 != 0 or kp.shape[1] == 0:
-        raise ValueError(f"fill_missing: kp must be [frames, 3 * keypoints], got {tuple(kp.shape)}")
-    T, K = int(kp.shape[0]), int(kp.shape[1]) // 3
+    kp, T, K = _series(kp, "fill_missing")
     out = torch.empty_like(kp)
     gap = torch.empty((T, K), dtype=torch.int32, device=kp.device)
     if T == 0:
         return out, gap
     lib = load_library()
-    nbytes = workspace_bytes(T, K)
-    work = torch.empty(nbytes // 8, dtype=torch.int64, device=kp.device)
+    nbytes, work = _workspace("stac_prep_fill", T, K, kp.device)
     with torch.cuda.device(kp.device):
         rc = lib.stac_prep_fill(_ptr(kp), T, K, code, _ptr(out), _ptr(gap), _ptr(work), nbytes, stream_ptr(kp.device))
     check(lib, "stac_prep_fill", rc)
@@ -67,17 +107,10 @@ def fill_missing(kp: torch.Tensor, mode: str = "linear"):
 def outlier_params(half_window, n_sigma, min_dev):
     """-> (h, thr, min_dev) as ``stac_prep_reject`` takes them: ``thr = n_sigma * 1.4826`` in double.  ValueError for a half-width
     outside 1 .. 16 or a negative or non-finite ``n_sigma`` / ``min_dev``."""
-    if isinstance(half_window, bool) or not isinstance(half_window, int) or not 1 <= half_window <= MAX_HALF_WINDOW:
-        raise ValueError(f"reject_outliers: half_window must be an integer in 1 .. {MAX_HALF_WINDOW}, not {half_window!r}")
-    vals = []
-    for name, v in (("n_sigma", n_sigma), ("min_dev", min_dev)):
-        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
-            raise ValueError(f"reject_outliers: {name} must be a finite number >= 0, not {v!r}")
-        vals.append(float(v))
-    thr = vals[0] * MAD_TO_SIGMA
-    if not math.isfinite(thr):
-        raise ValueError(f"reject_outliers: n_sigma = {n_sigma!r} is too large")
-    return half_window, thr, vals[1]
+    checked_int(half_window, "reject_outliers: half_window", ValueError, 1, MAX_HALF_WINDOW)
+    checked_number(n_sigma, "reject_outliers: n_sigma", ValueError)
+    floor = checked_number(min_dev, "reject_outliers: min_dev", ValueError)
+    return half_window, _mad_threshold("reject_outliers", n_sigma), floor
 
 
 def reject_outliers(kp: torch.Tensor, half_window: int = 5, n_sigma: float = 3.0, min_dev: float = 0.0):
@@ -85,10 +118,7 @@ def reject_outliers(kp: torch.Tensor, half_window: int = 5, n_sigma: float = 3.0
     identifier per track and coordinate over the frames t - half_window .. t + half_window; a rejected keypoint leaves as three
     NaN with flag 1, everything else bit for bit.  The input is made contiguous float32 first and is never written."""
     h, thr, floor = outlier_params(half_window, n_sigma, min_dev)
-    kp = device_tensor(kp, "reject_outliers needs a CUDA tensor")
-    if kp.dim() != 2 or kp.shape[1] % 3 != 0 or kp.shape[1] == 0:
-        raise ValueError(f"reject_outliers: kp must be [frames, 3 * keypoints], got {tuple(kp.shape)}")
-    T, K = int(kp.shape[0]), int(kp.shape[1]) // 3
+    kp, T, K = _series(kp, "reject_outliers")
     out = torch.empty_like(kp)
     flag = torch.empty((T, K), dtype=torch.uint8, device=kp.device)
     if T == 0:
@@ -103,23 +133,12 @@ def reject_outliers(kp: torch.Tensor, half_window: int = 5, n_sigma: float = 3.0
 def pairwise_params(n_sigma, min_dev, votes):
     """-> (thr, min_dev, votes) as ``stac_prep_pairwise`` takes them: ``thr = n_sigma * 1.4826`` in double.  ValueError for a
     negative or non-finite ``n_sigma`` / ``min_dev`` or a ``votes`` that is not an integer >= 1."""
-    vals = []
-    for name, v in (("n_sigma", n_sigma), ("min_dev", min_dev)):
-        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
-            raise ValueError(f"reject_pairwise: {name} must be a finite number >= 0, not {v!r}")
-        vals.append(float(v))
-    if isinstance(votes, bool) or not isinstance(votes, int) or not 1 <= votes <= 2**31 - 1:
-        raise ValueError(f"reject_pairwise: votes must be an integer >= 1, not {votes!r}")
-    thr = vals[0] * MAD_TO_SIGMA
-    if not math.isfinite(thr):
-        raise ValueError(f"reject_pairwise: n_sigma = {n_sigma!r} is too large")
-    return thr, vals[1], votes
+    return _pair_params("reject_pairwise", n_sigma, min_dev, "votes", votes)
 
 
 def pairwise_workspace_bytes(n_frames: int, n_kp: int) -> int:
     """Bytes of device workspace of one ``stac_prep_pairwise`` call (host only)."""
-    lib = load_library()
-    return int(check(lib, "stac_prep_pairwise_workspace", lib.stac_prep_pairwise_workspace(int(n_frames), int(n_kp))))
+    return _workspace("stac_prep_pairwise", n_frames, n_kp)[0]
 
 
 def reject_pairwise(kp: torch.Tensor, n_sigma: float = 6.0, min_dev: float = 0.002, votes: int = 2):
@@ -131,23 +150,14 @@ def reject_pairwise(kp: torch.Tensor, n_sigma: float = 6.0, min_dev: float = 0.0
     pairs (a, b), a < b, in lexicographic order.  At most 64 keypoints.  The input is made contiguous float32 first and is never
     written."""
     thr, floor, votes = pairwise_params(n_sigma, min_dev, votes)
-    kp = device_tensor(kp, "reject_pairwise needs a CUDA tensor")
-    if kp.dim() != 2 or kp.shape[1] % 3 != 0 or kp.shape[1] == 0:
-        raise ValueError(f"reject_pairwise: kp must be [frames, 3 * keypoints], got {tuple(kp.shape)}")
-    T, K = int(kp.shape[0]), int(kp.shape[1]) // 3
-    P = K * (K - 1) // 2
+    kp, T, K = _series(kp, "reject_pairwise")
     out = torch.empty_like(kp)
     flag = torch.empty((T, K), dtype=torch.uint8, device=kp.device)
-    # (room for one element also without a pair: the entry point takes no null pointer)
-    pair_n = torch.zeros(max(P, 1), dtype=torch.int64, device=kp.device)
-    pair_med = torch.full((max(P, 1),), math.nan, dtype=torch.float64, device=kp.device)
-    pair_mad = torch.full((max(P, 1),), math.nan, dtype=torch.float64, device=kp.device)
-    stats = {"pair_n": pair_n[:P], "pair_med": pair_med[:P], "pair_mad": pair_mad[:P]}
+    (pair_n, pair_med, pair_mad), stats = _pair_stats(K, kp.device)
     if T == 0:
         return out, flag, stats
     lib = load_library()
-    nbytes = pairwise_workspace_bytes(T, K)
-    work = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=kp.device)
+    nbytes, work = _workspace("stac_prep_pairwise", T, K, kp.device)
     with torch.cuda.device(kp.device):
         rc = lib.stac_prep_pairwise(_ptr(kp), T, K, thr, floor, votes, _ptr(out), _ptr(flag), _ptr(pair_n), _ptr(pair_med), _ptr(pair_mad),
                                     _ptr(work), nbytes, stream_ptr(kp.device))
@@ -158,17 +168,7 @@ def reject_pairwise(kp: torch.Tensor, n_sigma: float = 6.0, min_dev: float = 0.0
 def swaps_params(n_sigma, min_dev, min_bad):
     """-> (thr, min_dev, min_bad) as ``stac_prep_swaps`` takes them: ``thr = n_sigma * 1.4826`` in double.  ValueError for a
     negative or non-finite ``n_sigma`` / ``min_dev`` or a ``min_bad`` that is not an integer >= 1."""
-    vals = []
-    for name, v in (("n_sigma", n_sigma), ("min_dev", min_dev)):
-        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
-            raise ValueError(f"repair_swaps: {name} must be a finite number >= 0, not {v!r}")
-        vals.append(float(v))
-    if isinstance(min_bad, bool) or not isinstance(min_bad, int) or not 1 <= min_bad <= 2**31 - 1:
-        raise ValueError(f"repair_swaps: min_bad must be an integer >= 1, not {min_bad!r}")
-    thr = vals[0] * MAD_TO_SIGMA
-    if not math.isfinite(thr):
-        raise ValueError(f"repair_swaps: n_sigma = {n_sigma!r} is too large")
-    return thr, vals[1], min_bad
+    return _pair_params("repair_swaps", n_sigma, min_dev, "min_bad", min_bad)
 
 
 def swaps_pairs(pairs, n_kp: int) -> list:
@@ -191,8 +191,7 @@ def swaps_pairs(pairs, n_kp: int) -> list:
 
 def swaps_workspace_bytes(n_frames: int, n_kp: int) -> int:
     """Bytes of device workspace of one ``stac_prep_swaps`` call (host only)."""
-    lib = load_library()
-    return int(check(lib, "stac_prep_swaps_workspace", lib.stac_prep_swaps_workspace(int(n_frames), int(n_kp))))
+    return _workspace("stac_prep_swaps", n_frames, n_kp)[0]
 
 
 def repair_swaps(kp: torch.Tensor, pairs, n_sigma: float = 6.0, min_dev: float = 0.002, min_bad: int = 3):
@@ -204,23 +203,16 @@ def repair_swaps(kp: torch.Tensor, pairs, n_sigma: float = 6.0, min_dev: float =
     ``reject_pairwise``'s, of the series as given.  At most 64 keypoints.  The input is made contiguous float32 first and is
     never written."""
     thr, floor, min_bad = swaps_params(n_sigma, min_dev, min_bad)
-    kp = device_tensor(kp, "repair_swaps needs a CUDA tensor")
-    if kp.dim() != 2 or kp.shape[1] % 3 != 0 or kp.shape[1] == 0:
-        raise ValueError(f"repair_swaps: kp must be [frames, 3 * keypoints], got {tuple(kp.shape)}")
-    T, K = int(kp.shape[0]), int(kp.shape[1]) // 3
+    kp, T, K = _series(kp, "repair_swaps")
     cand = swaps_pairs(pairs, K)
-    S, P = len(cand), K * (K - 1) // 2
+    S = len(cand)
     out = torch.empty_like(kp)
     flag = torch.zeros((T, max(S, 1)), dtype=torch.uint8, device=kp.device)  # (room for a column also without a candidate)
-    pair_n = torch.zeros(max(P, 1), dtype=torch.int64, device=kp.device)
-    pair_med = torch.full((max(P, 1),), math.nan, dtype=torch.float64, device=kp.device)
-    pair_mad = torch.full((max(P, 1),), math.nan, dtype=torch.float64, device=kp.device)
-    stats = {"pair_n": pair_n[:P], "pair_med": pair_med[:P], "pair_mad": pair_mad[:P]}
+    (pair_n, pair_med, pair_mad), stats = _pair_stats(K, kp.device)
     if T == 0:
         return out, flag[:, :S], stats
     lib = load_library()
-    nbytes = swaps_workspace_bytes(T, K)
-    work = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=kp.device)
+    nbytes, work = _workspace("stac_prep_swaps", T, K, kp.device)
     table = (ctypes.c_int32 * max(2 * S, 1))(*[v for ab in cand for v in ab])  # host memory: read before the call returns
     with torch.cuda.device(kp.device):
         rc = lib.stac_prep_swaps(_ptr(kp), T, K, table if S else None, S, thr, floor, min_bad, _ptr(out), _ptr(flag), _ptr(pair_n),

@@ -84,6 +84,15 @@ class Stac:
             kp = kp.copy()
         return torch.as_tensor(kp).to(self.engine.device)
 
+    def _log_flagged(self, out, flag, head, names, verb):
+        """The tail of a preparation stage: one log line per column of ``flag`` [T, columns] that is not all zero
+        ("<head>: <names[column]>: n of T frames <verb> (share)"), then ``(out, flag)`` as numpy arrays."""
+        T = flag.shape[0]
+        count = flag.sum(dim=0, dtype=torch.int64).cpu().numpy()
+        for c in np.flatnonzero(count):
+            self._log(f"{head}: {names[c]}: {int(count[c])} of {T} frames {verb} ({100.0 * int(count[c]) / T:.3f} %)")
+        return out.cpu().numpy(), flag.cpu().numpy()
+
     # -- fill_missing (engine extension; DESIGN.md "Filling missing keypoints") ----------------------------------------
     def fill_missing(self, kp_data, mode=None):
         """Fills the missing keypoints (a NaN or infinite coordinate) of the whole series ``kp_data`` [T, 3K] along time on the
@@ -118,11 +127,7 @@ class Stac:
         prep.outlier_params(half_window, n_sigma, min_dev)
         kp = self._series_to_device(kp_data, "reject_outliers")
         out, flag = prep.reject_outliers(kp, half_window, n_sigma, min_dev)
-        count = flag.sum(dim=0, dtype=torch.int64).cpu().numpy()
-        for k in np.flatnonzero(count):
-            self._log(f"reject_outliers (hampel, window {half_window}, {n_sigma} sigma): {self._kp_names[k]}: {int(count[k])} of "
-                      f"{kp.shape[0]} frames rejected ({100.0 * int(count[k]) / kp.shape[0]:.3f} %)")
-        return out.cpu().numpy(), flag.cpu().numpy()
+        return self._log_flagged(out, flag, f"reject_outliers (hampel, window {half_window}, {n_sigma} sigma)", self._kp_names, "rejected")
 
     # -- reject_pairwise (engine extension; DESIGN.md "Rejecting keypoints by pairwise distances") -----------------------
     def reject_pairwise(self, kp_data, n_sigma=6.0, min_dev=0.002, votes=2):
@@ -136,11 +141,7 @@ class Stac:
         prep.pairwise_params(n_sigma, min_dev, votes)
         kp = self._series_to_device(kp_data, "reject_pairwise")
         out, flag, _ = prep.reject_pairwise(kp, n_sigma, min_dev, votes)
-        count = flag.sum(dim=0, dtype=torch.int64).cpu().numpy()
-        for k in np.flatnonzero(count):
-            self._log(f"reject_pairwise (mad, {n_sigma} sigma, {votes} votes): {self._kp_names[k]}: {int(count[k])} of "
-                      f"{kp.shape[0]} frames rejected ({100.0 * int(count[k]) / kp.shape[0]:.3f} %)")
-        return out.cpu().numpy(), flag.cpu().numpy()
+        return self._log_flagged(out, flag, f"reject_pairwise (mad, {n_sigma} sigma, {votes} votes)", self._kp_names, "rejected")
 
     # -- repair_swaps (engine extension; DESIGN.md "Repairing keypoint swaps") -------------------------------------------
     def repair_swaps(self, kp_data, pairs=None, n_sigma=6.0, min_dev=0.002, min_bad=3):
@@ -163,12 +164,8 @@ class Stac:
         cand = prep.swaps_pairs(cand, len(names))
         kp = self._series_to_device(kp_data, "repair_swaps")
         out, flag, _ = prep.repair_swaps(kp, cand, n_sigma, min_dev, min_bad)
-        count = flag.sum(dim=0, dtype=torch.int64).cpu().numpy()
-        for s in np.flatnonzero(count):
-            a, b = cand[s]
-            self._log(f"repair_swaps ({n_sigma} sigma, min_bad {min_bad}): {names[a]} / {names[b]}: {int(count[s])} of "
-                      f"{kp.shape[0]} frames exchanged ({100.0 * int(count[s]) / kp.shape[0]:.3f} %)")
-        return out.cpu().numpy(), flag.cpu().numpy()
+        return self._log_flagged(out, flag, f"repair_swaps ({n_sigma} sigma, min_bad {min_bad})", [f"{names[a]} / {names[b]}" for a, b in cand],
+                                 "exchanged")
 
     # -- fit_report (engine extension; DESIGN.md "Fit report") -----------------------------------------------------------
     def fit_report(self, data, permille=None, worst=None) -> dict:

@@ -2,7 +2,8 @@
 prototypes, ``declare`` that applies the table to a loaded library (``engine.load_library`` does, to whatever it loads), and the
 few helpers every caller of the library shares.  ``tests/test_host.py`` holds the table against the header and the structures against the compiler.
 A second table, ``PAIRWISE_PROTOTYPES``, holds the two functions of ``include/stac_hip_pairwise.h``; ``declare`` applies both.
-A third, ``SWAPS_PROTOTYPES``, holds the two of ``include/stac_hip_swaps.h`` in the same way.
+A third, ``SWAPS_PROTOTYPES``, holds the two of ``include/stac_hip_swaps.h`` in the same way, a fourth, ``DONOR_PROTOTYPES``, the two of
+``include/stac_hip_donor.h``.
 """
 
 from __future__ import annotations
@@ -110,6 +111,12 @@ SWAPS_PROTOTYPES = {
     "stac_prep_swaps_workspace": (i64, [i64, i32]),
     "stac_prep_swaps": (i32, [vp, i64, i32, _i32p, i32, f64, f64, i32, vp, vp, vp, vp, vp, vp, i64, vp]),
 }  # fmt: skip
+# every function include/stac_hip_donor.h declares (the fourth header, like the second); tests/test_donor_host.py holds this table
+# against that header.  The donor table of stac_prep_donor is DEVICE memory.
+DONOR_PROTOTYPES = {
+    "stac_prep_donor_workspace": (i64, [i64, i32]),
+    "stac_prep_donor": (i32, [vp, i64, i32, vp, i32, vp, vp, vp, vp, i64, vp]),
+}  # fmt: skip
 
 
 class StacHipError(RuntimeError):
@@ -117,8 +124,8 @@ class StacHipError(RuntimeError):
 
 
 def declare(lib):
-    """Declares ``restype`` and ``argtypes`` of every function of the three tables on ``lib`` (idempotent) -> ``lib``."""
-    for name, (restype, argtypes) in (*PROTOTYPES.items(), *PAIRWISE_PROTOTYPES.items(), *SWAPS_PROTOTYPES.items()):
+    """Declares ``restype`` and ``argtypes`` of every function of the four tables on ``lib`` (idempotent) -> ``lib``."""
+    for name, (restype, argtypes) in (*PROTOTYPES.items(), *PAIRWISE_PROTOTYPES.items(), *SWAPS_PROTOTYPES.items(), *DONOR_PROTOTYPES.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     return lib

@@ -42,6 +42,9 @@ _MUJOCO_REQUIRED = ("solver", "iterations", "ls_iterations")
 # repair_swaps: off (default) | lr | [[nameA, nameB], ...], with swaps_nsigma (default 6.0), swaps_min_dev (default 0.002, units of
 # kp_data) and swaps_min_bad (default 3) -- two keypoints of a candidate pair that carry each other's label in a frame are exchanged
 # back, in front of everything else; it makes no NaN and needs no fill_missing;
+# fill_donors: off (default) | auto, with fill_donors_triples (donor triples per keypoint, 1 .. 8, default 4) -- a missing keypoint is
+# carried through its gap by the local frame of three rigid partners that are still tracked, after the rejecters and directly in front
+# of fill_missing, which closes what is left;
 # report: off (default) | on, with report_quantiles (1 .. 8 permille values, default [500, 900, 990]) and report_worst (frames listed,
 # default 10) -- a <result file>.report.json next to every result file, read from the caller's config;
 # smooth: off (default) | savgol | gaussian, with smooth_window (half-width H, 1 .. 16, default 3: windows of 2 H + 1 frames),
@@ -52,7 +55,8 @@ _STAC_EXTENSIONS = ("solver", "lanes_per_chain", "device", "time_indices", "fit_
                     "reject_outliers", "outlier_window", "outlier_nsigma", "outlier_min_dev", "report", "report_quantiles", "report_worst",
                     "smooth", "smooth_window", "smooth_order", "smooth_sigma",
                     "reject_pairwise", "pairwise_nsigma", "pairwise_min_dev", "pairwise_votes",
-                    "repair_swaps", "swaps_nsigma", "swaps_min_dev", "swaps_min_bad")
+                    "repair_swaps", "swaps_nsigma", "swaps_min_dev", "swaps_min_bad",
+                    "fill_donors", "fill_donors_triples")
 _MODEL_EXTENSIONS = ("KP_NAMES_LABEL3D_PATH",)
 
 
@@ -227,6 +231,25 @@ def swaps_candidates(mode, kp_names) -> list:
                               "name the pairs as [[nameA, nameB], ...]")
         return pairs
     return named_pairs(mode, kp_names)
+
+
+DONOR_DEFAULTS = {"fill_donors_triples": 4}
+DONOR_MAX_TRIPLES = 8  # csrc/stac_donor.hpp: kDonorMaxTriples
+# the one text of run_stac's pre-flight and of main._fill_donors_mode
+DONORS_NEED_FILL = ("stac.fill_donors = auto leaves missing what no donor triple can fill (NaN), which the solver cannot take: "
+                    "set stac.fill_missing to linear or hold as well")
+
+
+def donor_options(stac) -> tuple:
+    """``stac.fill_donors`` and its parameter out of a ``stac`` mapping -> (mode, n_triples), absent keys at their defaults.
+    ``ConfigError`` for anything else than off | auto (a bare YAML ``off`` arrives as False) or a ``fill_donors_triples`` that is not
+    an integer in 1 .. 8."""
+    mode = _switch(stac, "fill_donors")
+    if not isinstance(mode, str) or mode not in ("off", "auto"):
+        raise ConfigError(f"stac.fill_donors must be off or auto, not {mode!r}")
+    n_triples = checked_int(stac.get("fill_donors_triples", DONOR_DEFAULTS["fill_donors_triples"]), "stac.fill_donors_triples", ConfigError,
+                            1, DONOR_MAX_TRIPLES)
+    return mode, n_triples
 
 
 REPORT_DEFAULTS = {"report_quantiles": (500, 900, 990), "report_worst": 10}
@@ -427,7 +450,8 @@ def validate_config(cfg: dict) -> ConfigNode:
             raise ConfigError(f"stac.{k} must be a bool")
     postprocess_options(stac)
     for key, options in (("fill_missing", fill_missing_options), ("reject_outliers", outlier_options), ("report", report_options),
-                         ("smooth", smooth_options), ("reject_pairwise", pairwise_options), ("repair_swaps", swaps_options)):
+                         ("smooth", smooth_options), ("reject_pairwise", pairwise_options), ("repair_swaps", swaps_options),
+                         ("fill_donors", donor_options)):
         if isinstance(stac.get(key), bool):  # the file that is written with a result says off / on, not the boolean
             stac[key] = _switch(stac, key)
         options(stac)

@@ -15,74 +15,13 @@
 
 #include "stac_host.hpp"
 #include "stac_prep.hpp"
+#include "stac_prep_tile.hpp"
 
 namespace stac {
 
 namespace {
 
-constexpr int kPrepThreads = 256;
-constexpr int kPrepWaves = kPrepThreads / 64;
-constexpr int kPrepChunk = 64;                                            // keypoints of a chunk
-constexpr int kPrepPairs = kPrepTileFrames * kPrepChunk / kPrepThreads;  // (frame, keypoint) pairs of a thread: 16
-constexpr int kPrepFlagRow = kPrepChunk + 4;  // bytes of a frame's flags in LDS: 17 dwords, so the 64 rows a ballot reads differ in bank
-constexpr int kCarryThreads = 1024;
-
-static_assert(kPrepTileFrames == 64, "a tile is what one 64-lane ballot covers");
-
-struct PrepShared {
-    uint8_t flags[kPrepTileFrames][kPrepFlagRow];
-    unsigned long long mask[kPrepChunk];
-};
-
-// Walks the pairs of this thread in (tile, chunk): pair e = i * 256 + threadIdx.x is frame e / kc, keypoint e % kc of the chunk
-struct PrepWalk {
-    uint32_t f, k, qf, qk, kc;
-    __device__ PrepWalk(uint32_t kc_) : kc(kc_) {
-        f = threadIdx.x / kc;
-        k = threadIdx.x - f * kc;
-        qf = kPrepThreads / kc;
-        qk = kPrepThreads - qf * kc;
-    }
-    __device__ void next() {
-        f += qf;
-        k += qk;
-        if (k >= kc) {
-            k -= kc;
-            ++f;
-        }
-    }
-};
-
-// Stage A + B of kernels 1 and 3: loads the pairs of (tile at frame t0, keypoints k0 .. k0 + kc - 1) into v and leaves the
-// validity mask of every keypoint of the chunk (bit f = frame t0 + f is valid; frames >= T are not) in sh.mask.
-__device__ __forceinline__ void prep_tile_masks(const float *__restrict__ kp, int64_t T, int64_t K3, int64_t t0, int32_t k0, int32_t kc,
-                                                float (&v)[kPrepPairs][3], PrepShared &sh) {
-    PrepWalk w((uint32_t)kc);
-#pragma unroll
-    for (int i = 0; i < kPrepPairs; ++i) {
-        v[i][0] = v[i][1] = v[i][2] = 0.0f;
-        if (w.f < (uint32_t)kPrepTileFrames) {
-            const int64_t t = t0 + w.f;
-            bool ok = false;
-            if (t < T) {
-                const float *s = kp + t * K3 + 3 * (int64_t)(k0 + (int32_t)w.k);
-                v[i][0] = s[0];
-                v[i][1] = s[1];
-                v[i][2] = s[2];
-                ok = !prep_missing(v[i][0], v[i][1], v[i][2]);
-            }
-            sh.flags[w.f][w.k] = ok ? 1 : 0;
-        }
-        w.next();
-    }
-    __syncthreads();
-    const int lane = threadIdx.x & 63;
-    for (int k = threadIdx.x >> 6; k < kc; k += kPrepWaves) {
-        const unsigned long long m = __ballot(sh.flags[lane][k] != 0);
-        if (lane == 0) sh.mask[k] = m;
-    }
-    __syncthreads();
-}
+constexpr int kCarryThreads = 1024;  // (the tile walk, the masks and the other constants: stac_prep_tile.hpp)
 
 __global__ __launch_bounds__(kPrepThreads) void prep_summary_kernel(const float *__restrict__ kp, int64_t T, int32_t K, int64_t tiles,
                                                                    int32_t chunks, int64_t *__restrict__ first,
@@ -191,8 +130,8 @@ __global__ __launch_bounds__(kPrepThreads) void prep_fill_kernel(const float *__
 
 }  // namespace
 
-static hipError_t launch_prep_fill(const float *kp, int64_t T, int32_t K, int32_t mode, float *out, int32_t *gap, void *workspace,
-                            hipStream_t s) {
+// Stages 1 and 2 (declared in stac_prep_tile.hpp: the donor fill of stac_donor.hip starts with the same two launches)
+hipError_t launch_prep_scan(const float *kp, int64_t T, int32_t K, void *workspace, hipStream_t s) {
     const int64_t tiles = prep_tiles(T, kPrepTileFrames);
     const int32_t chunks = (K + kPrepChunk - 1) / kPrepChunk;
     int64_t *first = (int64_t *)workspace, *last = first + (int64_t)K * tiles, *prev = last + (int64_t)K * tiles,
@@ -203,7 +142,17 @@ static hipError_t launch_prep_fill(const float *kp, int64_t T, int32_t K, int32_
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(prep_carry_kernel, dim3((unsigned)K), dim3(kCarryThreads), 0, s, first, last, prev, next, tiles);
-    e = hipGetLastError();
+    return hipGetLastError();
+}
+
+static hipError_t launch_prep_fill(const float *kp, int64_t T, int32_t K, int32_t mode, float *out, int32_t *gap, void *workspace,
+                            hipStream_t s) {
+    const int64_t tiles = prep_tiles(T, kPrepTileFrames);
+    const int32_t chunks = (K + kPrepChunk - 1) / kPrepChunk;
+    const int64_t *prev = (const int64_t *)workspace + 2 * (int64_t)K * tiles, *next = prev + (int64_t)K * tiles;
+    const int64_t work = tiles * chunks;
+    const unsigned grid = (unsigned)(work < kPrepMaxBlocks ? work : kPrepMaxBlocks);
+    const hipError_t e = launch_prep_scan(kp, T, K, workspace, s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(prep_fill_kernel, dim3(grid), dim3(kPrepThreads), 0, s, kp, T, K, mode, tiles, chunks, prev, next, out, gap);
     return hipGetLastError();

@@ -9,8 +9,8 @@ from pathlib import Path
 import numpy as np
 
 from . import dist, io, utils
-from .config import (GATHER_NONE_CONTINUOUS, PAIRWISE_NEEDS_FILL, POSTPROCESS_GPU_MARKER_ORDER, compose_config, fill_missing_options,
-                     outlier_options, pairwise_options, postprocess_options, report_options, smooth_options, swaps_candidates,
+from .config import (DONORS_NEED_FILL, GATHER_NONE_CONTINUOUS, PAIRWISE_NEEDS_FILL, POSTPROCESS_GPU_MARKER_ORDER, compose_config, donor_options,
+                     fill_missing_options, outlier_options, pairwise_options, postprocess_options, report_options, smooth_options, swaps_candidates,
                      swaps_options)
 from .stac import Stac
 
@@ -41,6 +41,9 @@ def run_stac(cfg, kp_data, kp_names, base_path=None, *, setup=None, device=None)
     by frame, two keypoints of a pair that carry each other's label, on the GPU: ``kp_data`` of both files is the repaired series and
     ``kp_swapped`` marks both keypoints of every repaired pair (DESIGN.md "Repairing keypoint swaps"); unknown names and a keypoint
     in two pairs are a ``ValueError`` before any work.
+    ``stac.fill_donors: auto`` (needs ``fill_missing``) fills, after the rejecters and directly in front of ``fill_missing``, a missing
+    keypoint from the local frame of three rigid partners that are still tracked, on the GPU; what it cannot fill stays missing for
+    ``fill_missing``, and ``kp_gap`` marks both kinds (DESIGN.md "Filling gaps from donor keypoints").
     ``stac.report: on`` computes the marker errors of each phase's final result on the GPU and writes them as
     ``<result file>.report.json`` next to the file (DESIGN.md "Fit report"); the result files themselves do not change.
     ``stac.smooth: savgol | gaussian`` (needs ``postprocess: gpu``) low-pass filters the ``qpos`` of the ik_only run along time on
@@ -166,6 +169,7 @@ class _Preflight:
         self.reject_mode, self.reject_args = _reject_outliers_mode(self.cfg)
         self.pairwise_mode, self.pairwise_args = _reject_pairwise_mode(self.cfg)
         self.swaps_pairs, self.swaps_args = _repair_swaps_mode(self.cfg, self.kp_names)
+        self.donors_mode, self.donors_triples = _fill_donors_mode(self.cfg)
         self.report = _report_mode(self.cfg)
         self.smooth = _smooth_mode(self.cfg)
         self.marker_order = not stac.skip_ik_only and bool(stac.get("reference_marker_order", False))
@@ -209,7 +213,8 @@ class _Series:
 
 def _prepare_series(stac, cfg, kp_data, pre) -> _Series:
     """``stac.repair_swaps`` (on the raw series), then ``stac.reject_pairwise`` (its medians are those of the repaired series), then
-    ``stac.reject_outliers``, then ``stac.fill_missing`` over the WHOLE series, once, on the GPU (every rank itself: same bits) -> the
+    ``stac.reject_outliers``, then ``stac.fill_donors`` (what it fills is no longer missing; ``kp_gap`` is then ITS gap, the gap of the
+    series before anything was filled), then ``stac.fill_missing`` over the WHOLE series, once, on the GPU (every rank itself: same bits) -> the
     prepared series and its marks: kp_swapped (1 for both keypoints of a repaired pair), kp_rejected_pairwise (the pairwise detector's
     share), kp_rejected (what either detector rejected) and kp_gap, each only with its stage on.  A missing run that crosses
     n_fit_frames or a clip border is so filled from its true neighbours, and both phases see the filled array.  A rejected keypoint is
@@ -231,8 +236,22 @@ def _prepare_series(stac, cfg, kp_data, pre) -> _Series:
         kp_data, kp_hampel = stac.reject_outliers(kp_data, **pre.reject_args)
         # (Hampel passes a keypoint that is missing already: the two detectors' sets are disjoint)
         kp_rejected = kp_hampel if kp_pairwise is None else kp_hampel | kp_pairwise
+    donor_gap = None
+    if pre.donors_mode != "off":  # (the pre-flight refuses it without the fill)
+        from . import prep
+
+        # the pairwise statistics of a stage of this run if one has them (reject_pairwise's over repair_swaps'), else of this series
+        don = prep.donor_table(stac.pair_stats, kp_data.shape[1] // 3, pre.donors_triples) if pre.pairwise_mode != "off" or pre.swaps_pairs else None
+        kp_data, donor_gap, src = stac.fill_donors(kp_data, don, pre.donors_triples)
+        n_fit = min(int(cfg.stac.n_fit_frames), src.shape[0])
+        if not cfg.stac.skip_fit_offsets and n_fit > 0:
+            share = lambda sel: 100.0 * np.count_nonzero(sel) / src[:n_fit].size  # noqa: E731
+            ranks = ", ".join(f"triple {d + 1}: {share(src[:n_fit] == d + 1):.3f} %" for d in range(pre.donors_triples))
+            print(f"fill_donors: of the keypoints of the {n_fit} fit frames, filled by {ranks}; left to fill_missing: {share(src[:n_fit] == 255):.3f} %")
     if pre.fill_mode != "off":
         kp_data, kp_gap = stac.fill_missing(kp_data, pre.fill_mode)
+        if donor_gap is not None:  # kp_gap is the gap of the series before anything was filled: donor-filled values are filled values
+            kp_gap = donor_gap
         n_fit = min(int(cfg.stac.n_fit_frames), kp_gap.shape[0])
         if not cfg.stac.skip_fit_offsets and n_fit > 0:  # (the offset phase fits filled positions like observed ones: DESIGN.md §10)
             print(f"fill_missing: {100.0 * np.count_nonzero(kp_gap[:n_fit]) / kp_gap[:n_fit].size:.3f} % of the keypoints of the "
@@ -343,6 +362,15 @@ def _reject_pairwise_mode(cfg) -> tuple:
     if mode != "off" and _fill_missing_mode(cfg) == "off":
         raise ValueError(PAIRWISE_NEEDS_FILL)
     return mode, {"n_sigma": n_sigma, "min_dev": min_dev, "votes": votes}
+
+
+def _fill_donors_mode(cfg) -> tuple:
+    """``stac.fill_donors``: "off" (default) | "auto" -> (mode, ``stac.fill_donors_triples``).  ``ValueError`` for a bad value of
+    either key, and for ``auto`` with ``fill_missing`` off: what no donor triple can fill stays NaN, which the solver cannot take."""
+    mode, n_triples = donor_options(cfg.stac)
+    if mode != "off" and _fill_missing_mode(cfg) == "off":
+        raise ValueError(DONORS_NEED_FILL)
+    return mode, n_triples
 
 
 def _repair_swaps_mode(cfg, kp_names=None) -> tuple:

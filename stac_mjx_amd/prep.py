@@ -3,7 +3,9 @@
 (csrc/stac_outlier.hip): finite but wrong keypoints become missing ones (DESIGN.md "Rejecting keypoint outliers"); and
 ``reject_pairwise`` over ``stac_prep_pairwise`` (csrc/stac_pairwise.hip), the detector without a time window (DESIGN.md
 "Rejecting keypoints by pairwise distances"); and, in front of all of them, ``repair_swaps`` over ``stac_prep_swaps`` (the same
-unit): two keypoints that carry each other's label in a frame are exchanged back (DESIGN.md "Repairing keypoint swaps").
+unit): two keypoints that carry each other's label in a frame are exchanged back (DESIGN.md "Repairing keypoint swaps"); and,
+directly in front of ``fill_missing``, ``fill_donors`` over ``stac_prep_donor`` (csrc/stac_donor.hip): a missing keypoint is carried
+through its gap by three rigid partners that are still tracked (DESIGN.md "Filling gaps from donor keypoints").
 
 A keypoint is missing in a frame when one of its coordinates is NaN or infinite.  Every track is filled along time on its own
 (``linear``: interpolation between its two valid neighbours in double; ``hold``: the nearer neighbour; leading and trailing runs
@@ -34,6 +36,7 @@ MODES = {"linear": 0, "hold": 1}  # include/stac_hip.h: STAC_PREP_LINEAR, STAC_P
 MAX_HALF_WINDOW = 16  # csrc/stac_outlier.hpp: kOutlierMaxHalf (largest half-width of the outlier window)
 MAD_TO_SIGMA = 1.4826  # the median absolute deviation of a normal distribution is sigma / 1.4826
 PAIRWISE_MAX_KP = 64  # csrc/stac_pairwise.hpp: kPairwiseMaxKp (keypoints of reject_pairwise at most)
+DONOR_MAX_TRIPLES = 8  # csrc/stac_donor.hpp: kDonorMaxTriples (donor triples of a keypoint at most; kDonorMaxKp is 64 as well)
 
 
 def mode_code(mode) -> int:
@@ -219,6 +222,75 @@ def repair_swaps(kp: torch.Tensor, pairs, n_sigma: float = 6.0, min_dev: float =
                                  _ptr(pair_med), _ptr(pair_mad), _ptr(work), nbytes, stream_ptr(kp.device))
     check(lib, "stac_prep_swaps", rc)
     return out, flag[:, :S], stats
+
+
+def donor_triples(n_triples) -> int:
+    """``n_triples`` as ``stac_prep_donor`` takes it; ValueError for anything but an integer in 1 .. 8."""
+    return checked_int(n_triples, "fill_donors: n_triples", ValueError, 1, DONOR_MAX_TRIPLES)
+
+
+def donor_workspace_bytes(n_frames: int, n_kp: int) -> int:
+    """Bytes of device workspace of one ``stac_prep_donor`` call (host only)."""
+    return _workspace("stac_prep_donor", n_frames, n_kp)[0]
+
+
+def donor_table(stats, K: int, n_triples: int = 4) -> np.ndarray:
+    """The automatic donor table ``[K, n_triples, 3]`` int32 from the pairwise statistics of ``reject_pairwise`` (``pair_n`` and
+    ``pair_mad`` over the pairs (a, b), a < b, in lexicographic order; tensors or arrays), on the host.  The candidates of keypoint k
+    are the other keypoints whose pair with k has ``pair_n >= 3`` (and a ``pair_mad`` that is a number), ordered by (``pair_mad``,
+    index): the partners it keeps the steadiest distance to.  With c0 .. c3 the first four, the triples are (c0, c1, c2), (c0, c1, c3),
+    (c0, c2, c3), (c1, c2, c3), those that exist, cut to ``n_triples``; fewer than three candidates give none.  A row that is no
+    triple is (-1, -1, -1): the end of that keypoint's list."""
+    n_triples = donor_triples(n_triples)
+    K = checked_int(K, "donor_table: K", ValueError, 1, PAIRWISE_MAX_KP)
+    host = lambda v: v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)  # noqa: E731
+    pair_n, pair_mad = host(stats["pair_n"]).astype(np.int64), host(stats["pair_mad"]).astype(np.float64)
+    P = K * (K - 1) // 2
+    if pair_n.shape != (P,) or pair_mad.shape != (P,):
+        raise ValueError(f"donor_table: pair_n and pair_mad must be [{P}], the pairs of {K} keypoints, got {pair_n.shape} and {pair_mad.shape}")
+    don = np.full((K, n_triples, 3), -1, np.int32)
+    for k in range(K):
+        cand = []
+        for j in range(K):
+            if j != k:
+                a, b = min(j, k), max(j, k)
+                p = a * (2 * K - a - 1) // 2 + (b - a - 1)
+                if pair_n[p] >= 3 and not math.isnan(pair_mad[p]):
+                    cand.append((float(pair_mad[p]), j))
+        c = [j for _, j in sorted(cand)[:4]]
+        rows = [(c[x], c[y], c[z]) for x, y, z in ((0, 1, 2), (0, 1, 3), (0, 2, 3), (1, 2, 3)) if z < len(c)]
+        for d, row in enumerate(rows[:n_triples]):
+            don[k, d] = row
+    return don
+
+
+def fill_donors(kp: torch.Tensor, don):
+    """Device tensor [T, 3K] and a donor table ``don`` [K, D, 3] (int32; a tensor or an array, D in 1 .. 8) -> (out [T, 3K] float32,
+    gap [T, K] int32, src [T, K] uint8), on the current stream of its device: a missing keypoint is filled by the first usable donor
+    triple of its list -- its coordinates in the frame of the three donors, interpolated between the two ends of the gap, carried
+    back by the donors' frame in its own frame -- and stays missing if there is none; everything else passes bit for bit: DESIGN.md
+    "Filling gaps from donor keypoints".  ``gap`` is ``fill_missing``'s of the input; ``src`` is 0 where observed, d + 1 where triple
+    d filled, 255 where missing and left so.  At most 64 keypoints.  The input is made contiguous float32 first and is never
+    written."""
+    kp, T, K = _series(kp, "fill_donors")
+    don = don if isinstance(don, torch.Tensor) else torch.as_tensor(np.array(don))  # (a copy: torch does not wrap a read-only array)
+    if don.dim() != 3 or don.shape[0] != K or don.shape[2] != 3 or don.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"fill_donors: don must be an integer table [{K}, triples, 3], got {tuple(don.shape)} {don.dtype}")
+    D = donor_triples(int(don.shape[1]))
+    if don.dtype == torch.int64:  # (by value: an index beyond int32 ends a list like any index out of range)
+        don = don.clamp(-1, INT32_MAX)
+    don = don.to(device=kp.device, dtype=torch.int32).contiguous()
+    out = torch.empty_like(kp)
+    gap = torch.empty((T, K), dtype=torch.int32, device=kp.device)
+    src = torch.empty((T, K), dtype=torch.uint8, device=kp.device)
+    if T == 0:
+        return out, gap, src
+    lib = load_library()
+    nbytes, work = _workspace("stac_prep_donor", T, K, kp.device)
+    with torch.cuda.device(kp.device):
+        rc = lib.stac_prep_donor(_ptr(kp), T, K, _ptr(don), D, _ptr(out), _ptr(gap), _ptr(src), _ptr(work), nbytes, stream_ptr(kp.device))
+    check(lib, "stac_prep_donor", rc)
+    return out, gap, src
 
 
 def summary(gap) -> dict:

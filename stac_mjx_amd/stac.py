@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import dist, prng, utils
-from .config import GATHER_NONE_CONTINUOUS, POSTPROCESS_GPU_MARKER_ORDER, report_options, smooth_marker_order_refusal
+from .config import GATHER_NONE_CONTINUOUS, INT32_MAX, POSTPROCESS_GPU_MARKER_ORDER, report_options, smooth_marker_order_refusal
 from .engine import Engine
 from .fit_model import FitSetup, build_fit_setup
 from .io import StacData
@@ -52,6 +52,7 @@ class Stac:
         self._t_last = 0.0
         self._timestep = s.tables.timestep
         self._renderer = None
+        self.pair_stats = None  # the pairwise statistics of the last reject_pairwise / repair_swaps call (device tensors)
 
     # -- helpers ------------------------------------------------------------------------------------
     def _log(self, *a):
@@ -140,7 +141,7 @@ class Stac:
 
         prep.pairwise_params(n_sigma, min_dev, votes)
         kp = self._series_to_device(kp_data, "reject_pairwise")
-        out, flag, _ = prep.reject_pairwise(kp, n_sigma, min_dev, votes)
+        out, flag, self.pair_stats = prep.reject_pairwise(kp, n_sigma, min_dev, votes)  # (kept for fill_donors: device tensors)
         return self._log_flagged(out, flag, f"reject_pairwise (mad, {n_sigma} sigma, {votes} votes)", self._kp_names, "rejected")
 
     # -- repair_swaps (engine extension; DESIGN.md "Repairing keypoint swaps") -------------------------------------------
@@ -163,9 +164,29 @@ class Stac:
             cand = pairs
         cand = prep.swaps_pairs(cand, len(names))
         kp = self._series_to_device(kp_data, "repair_swaps")
-        out, flag, _ = prep.repair_swaps(kp, cand, n_sigma, min_dev, min_bad)
+        out, flag, self.pair_stats = prep.repair_swaps(kp, cand, n_sigma, min_dev, min_bad)  # (kept for fill_donors: device tensors)
         return self._log_flagged(out, flag, f"repair_swaps ({n_sigma} sigma, min_bad {min_bad})", [f"{names[a]} / {names[b]}" for a, b in cand],
                                  "exchanged")
+
+    # -- fill_donors (engine extension; DESIGN.md "Filling gaps from donor keypoints") -------------------------------------
+    def fill_donors(self, kp_data, don=None, n_triples=4):
+        """Fills the missing keypoints of the whole series ``kp_data`` [T, 3K] from the local frame of three other keypoints that
+        are still tracked, on the GPU (``prep.fill_donors``) -> ``(out [T, 3K] float32, gap [T, K] int32, src [T, K] uint8)`` as
+        numpy arrays: ``gap`` is ``fill_missing``'s of the input, ``src`` is 0 where the keypoint was observed, d + 1 where donor
+        triple d filled it and 255 where it stays missing (for ``fill_missing`` to close).  ``don``: the donor table [K, D, 3]
+        (None: ``prep.donor_table`` with ``n_triples`` rows from the pairwise statistics of this series, by one
+        ``prep.reject_pairwise`` call that rejects nothing).  One log line per keypoint that had donor fills."""
+        from . import prep
+
+        kp = self._series_to_device(kp_data, "fill_donors")
+        if don is None:
+            prep.donor_triples(n_triples)
+            # (votes that no frame can reach: a keypoint is in at most K - 1 pairs)
+            don = prep.donor_table(prep.reject_pairwise(kp, votes=INT32_MAX)[2], len(self._kp_names), n_triples) if kp.shape[0] else \
+                np.full((len(self._kp_names), n_triples, 3), -1, np.int32)
+        out, gap, src = prep.fill_donors(kp, don)
+        out, _ = self._log_flagged(out, ((src > 0) & (src < 255)).to(torch.uint8), "fill_donors", self._kp_names, "filled from donors")
+        return out, gap.cpu().numpy(), src.cpu().numpy()
 
     # -- fit_report (engine extension; DESIGN.md "Fit report") -----------------------------------------------------------
     def fit_report(self, data, permille=None, worst=None) -> dict:

@@ -3,7 +3,7 @@ prototypes, ``declare`` that applies the table to a loaded library (``engine.loa
 few helpers every caller of the library shares.  ``tests/test_host.py`` holds the table against the header and the structures against the compiler.
 A second table, ``PAIRWISE_PROTOTYPES``, holds the two functions of ``include/stac_hip_pairwise.h``; ``declare`` applies both.
 A third, ``SWAPS_PROTOTYPES``, holds the two of ``include/stac_hip_swaps.h`` in the same way, a fourth, ``DONOR_PROTOTYPES``, the two of
-``include/stac_hip_donor.h``.
+``include/stac_hip_donor.h``, a fifth, ``RESAMPLE_PROTOTYPES``, the two of ``include/stac_hip_resample.h``.
 """
 
 from __future__ import annotations
@@ -117,6 +117,12 @@ DONOR_PROTOTYPES = {
     "stac_prep_donor_workspace": (i64, [i64, i32]),
     "stac_prep_donor": (i32, [vp, i64, i32, vp, i32, vp, vp, vp, vp, i64, vp]),
 }  # fmt: skip
+# every function include/stac_hip_resample.h declares (the fifth header, like the second); tests/test_resample_host.py holds this table
+# against that header.  The tap table of stac_post_resample is DEVICE memory, its quaternion columns are HOST memory.
+RESAMPLE_PROTOTYPES = {
+    "stac_post_resample_rows": (i64, [i64, i32, i32]),
+    "stac_post_resample": (i32, [vp, i64, i32, i64, i32, i32, i32, vp, _i32p, i32, vp, vp, vp, i64, vp]),
+}  # fmt: skip
 
 
 class StacHipError(RuntimeError):
@@ -124,8 +130,9 @@ class StacHipError(RuntimeError):
 
 
 def declare(lib):
-    """Declares ``restype`` and ``argtypes`` of every function of the four tables on ``lib`` (idempotent) -> ``lib``."""
-    for name, (restype, argtypes) in (*PROTOTYPES.items(), *PAIRWISE_PROTOTYPES.items(), *SWAPS_PROTOTYPES.items(), *DONOR_PROTOTYPES.items()):
+    """Declares ``restype`` and ``argtypes`` of every function of the five tables on ``lib`` (idempotent) -> ``lib``."""
+    for name, (restype, argtypes) in (*PROTOTYPES.items(), *PAIRWISE_PROTOTYPES.items(), *SWAPS_PROTOTYPES.items(), *DONOR_PROTOTYPES.items(),
+                                      *RESAMPLE_PROTOTYPES.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     return lib

@@ -50,13 +50,18 @@ _MUJOCO_REQUIRED = ("solver", "iterations", "ls_iterations")
 # smooth: off (default) | savgol | gaussian, with smooth_window (half-width H, 1 .. 16, default 3: windows of 2 H + 1 frames),
 # smooth_order (savgol: the polynomial order, 0 <= order < 2 H + 1, default 2) and smooth_sigma (gaussian: frames, > 0, default H / 2)
 # -- the qpos of an ik_only run is low-pass filtered per clip on the GPU between the stitch and qvel, the file gains qpos_raw and its
-# xpos / xquat / marker_sites are those of the smoothed pose; needs postprocess = gpu, read from the caller's config)
+# xpos / xquat / marker_sites are those of the smoothed pose; needs postprocess = gpu, read from the caller's config;
+# resample: off (default) | kaiser, with mocap_hz (the rate of the recording), resample_hz (the rate wanted), resample_lobes (zero
+# crossings of the sinc on each side, 1 .. 16, default 10) and resample_beta (the Kaiser window's, >= 0, default 5.0) -- the ik_only
+# result is resampled per clip on the GPU into a second file next to the first, which does not change; needs postprocess = gpu, read
+# from the caller's config)
 _STAC_EXTENSIONS = ("solver", "lanes_per_chain", "device", "time_indices", "fit_frames_per_clip", "reference_marker_order", "gather", "gather_max_bytes", "lm_maxiter", "postprocess", "fill_missing",
                     "reject_outliers", "outlier_window", "outlier_nsigma", "outlier_min_dev", "report", "report_quantiles", "report_worst",
                     "smooth", "smooth_window", "smooth_order", "smooth_sigma",
                     "reject_pairwise", "pairwise_nsigma", "pairwise_min_dev", "pairwise_votes",
                     "repair_swaps", "swaps_nsigma", "swaps_min_dev", "swaps_min_bad",
-                    "fill_donors", "fill_donors_triples")
+                    "fill_donors", "fill_donors_triples",
+                    "resample", "mocap_hz", "resample_hz", "resample_lobes", "resample_beta")
 _MODEL_EXTENSIONS = ("KP_NAMES_LABEL3D_PATH",)
 
 
@@ -300,6 +305,67 @@ def smooth_options(stac) -> dict:
     return {"kind": kind, "half_window": h, "order": order if kind == "savgol" else None, "sigma": sigma if kind == "gaussian" else None}
 
 
+RESAMPLE_DEFAULTS = {"resample_lobes": 10, "resample_beta": 5.0}
+RESAMPLE_MAX_LOBES = 16  # post.RESAMPLE_MAX_LOBES
+RESAMPLE_MAX_UP, RESAMPLE_MAX_DOWN, RESAMPLE_MAX_WIN = 32, 64, 256  # csrc/stac_resample.hpp: kResampleMaxUp, kResampleMaxDown, kResampleMaxWin
+# the one text of run_stac's pre-flight for a run whose ik_only output is sharded
+RESAMPLE_SHARDED = ("stac.resample = kaiser resamples the whole ik_only result on rank 0, but this run writes per-rank shards "
+                    "(stac.gather resolves to none): use gather = rank0, or call Stac.resample_result on the manifest afterwards")
+
+
+def resample_ratio(from_hz, to_hz, exc=ConfigError, names=("stac.mocap_hz", "stac.resample_hz")) -> tuple:
+    """``to_hz / from_hz`` in lowest terms -> (U, D), read through the decimal text of the two numbers so that 29.97 is exact.
+    ``exc`` for a rate that is not a finite number > 0 and for U > 32 or D > 64."""
+    from fractions import Fraction
+
+    for name, v in zip(names, (from_hz, to_hz)):
+        checked_number(v, name, exc, positive=True)
+    ratio = Fraction(str(to_hz)) / Fraction(str(from_hz))
+    if ratio.numerator > RESAMPLE_MAX_UP or ratio.denominator > RESAMPLE_MAX_DOWN:
+        raise exc(f"{names[1]} / {names[0].split(': ')[-1]} = {to_hz!r} / {from_hz!r} is {ratio.numerator} / {ratio.denominator} in lowest terms; "
+                  f"up to {RESAMPLE_MAX_UP} / {RESAMPLE_MAX_DOWN} can be resampled")
+    return ratio.numerator, ratio.denominator
+
+
+def resample_window(U, D, lobes) -> int:
+    """Taps W of an output of the Kaiser table for U / D with ``lobes`` (post.resample_taps)."""
+    return 2 * ((lobes * max(U, D)) // U + 1)
+
+
+def resample_options(stac) -> dict:
+    """``stac.resample`` and its parameters out of a ``stac`` mapping -> ``{"kind", "from_hz", "to_hz", "up", "down", "lobes",
+    "beta"}``, absent keys at their defaults (the rates and the ratio are None for off).  ``ConfigError`` for anything else than
+    off | kaiser (a bare YAML ``off`` arrives as False), ``resample_lobes`` that is not an integer in 1 .. 16, a
+    ``resample_beta`` that is not a finite number >= 0, a rate (when given) that is not a finite number > 0, and with kaiser for a
+    missing rate, a ratio beyond 32 / 64, a window of more than 256 taps, and for resampling without ``postprocess: gpu`` (there
+    is no host path) or with ``reference_marker_order: true`` (the rows of marker_sites must be the rows of qpos)."""
+    kind = _switch(stac, "resample")
+    if not isinstance(kind, str) or kind not in ("off", "kaiser"):
+        raise ConfigError(f"stac.resample must be off or kaiser, not {kind!r}")
+    lobes = checked_int(stac.get("resample_lobes", RESAMPLE_DEFAULTS["resample_lobes"]), "stac.resample_lobes", ConfigError, 1, RESAMPLE_MAX_LOBES)
+    beta = checked_number(stac.get("resample_beta", RESAMPLE_DEFAULTS["resample_beta"]), "stac.resample_beta", ConfigError)
+    rates = {}
+    for key in ("mocap_hz", "resample_hz"):
+        rates[key] = stac.get(key)
+        if rates[key] is not None:
+            checked_number(rates[key], f"stac.{key}", ConfigError, positive=True)
+    up = down = None
+    if kind != "off":
+        for key in ("mocap_hz", "resample_hz"):
+            if rates[key] is None:
+                raise ConfigError(f"stac.resample = {kind} needs stac.{key}: the rate of the recording (mocap_hz) and the rate wanted (resample_hz)")
+        up, down = resample_ratio(rates["mocap_hz"], rates["resample_hz"])
+        if resample_window(up, down, lobes) > RESAMPLE_MAX_WIN:
+            raise ConfigError(f"stac.resample_lobes = {lobes} at {up} / {down} needs {resample_window(up, down, lobes)} taps per output, "
+                              f"at most {RESAMPLE_MAX_WIN}: fewer lobes")
+        if stac.get("postprocess", "host") != "gpu":
+            raise ConfigError(f"stac.resample = {kind} runs on the device only (there is no host path for resampling): set stac.postprocess to gpu as well")
+        if bool(stac.get("reference_marker_order", False)):
+            raise ConfigError(f"stac.resample = {kind} recomputes marker_sites from the resampled qpos row by row, which the reference's "
+                              "frame-major row order of marker_sites (stac.reference_marker_order: true) cannot hold")
+    return {"kind": kind, "from_hz": rates["mocap_hz"], "to_hz": rates["resample_hz"], "up": up, "down": down, "lobes": lobes, "beta": beta}
+
+
 # Refusals that both run_stac (before any work) and Stac.ik_only (for its direct callers) raise: one text each
 GATHER_NONE_CONTINUOUS = ("stac.gather = none writes per-rank shards, but stac.continuous cross-fades neighbouring "
                           "clips across shard borders: use gather = rank0 (or all, or auto) for continuous runs")
@@ -451,7 +517,7 @@ def validate_config(cfg: dict) -> ConfigNode:
     postprocess_options(stac)
     for key, options in (("fill_missing", fill_missing_options), ("reject_outliers", outlier_options), ("report", report_options),
                          ("smooth", smooth_options), ("reject_pairwise", pairwise_options), ("repair_swaps", swaps_options),
-                         ("fill_donors", donor_options)):
+                         ("fill_donors", donor_options), ("resample", resample_options)):
         if isinstance(stac.get(key), bool):  # the file that is written with a result says off / on, not the boolean
             stac[key] = _switch(stac, key)
         options(stac)

@@ -9,9 +9,9 @@ from pathlib import Path
 import numpy as np
 
 from . import dist, io, utils
-from .config import (DONORS_NEED_FILL, GATHER_NONE_CONTINUOUS, PAIRWISE_NEEDS_FILL, POSTPROCESS_GPU_MARKER_ORDER, compose_config, donor_options,
-                     fill_missing_options, outlier_options, pairwise_options, postprocess_options, report_options, smooth_options, swaps_candidates,
-                     swaps_options)
+from .config import (DONORS_NEED_FILL, GATHER_NONE_CONTINUOUS, PAIRWISE_NEEDS_FILL, POSTPROCESS_GPU_MARKER_ORDER, RESAMPLE_SHARDED, compose_config,
+                     donor_options, fill_missing_options, outlier_options, pairwise_options, postprocess_options, report_options, resample_options,
+                     smooth_options, swaps_candidates, swaps_options)
 from .stac import Stac
 
 
@@ -50,6 +50,9 @@ def run_stac(cfg, kp_data, kp_names, base_path=None, *, setup=None, device=None)
     the GPU, per clip, after the stitch and before ``qvel``: the file's ``qpos`` / ``xpos`` / ``xquat`` / ``marker_sites`` / ``qvel``
     are those of the smoothed pose and ``qpos_raw`` keeps the fitted one (DESIGN.md "Smoothing fitted poses"); clips shorter than
     the window of ``2 * smooth_window + 1`` frames are a ``ValueError``.
+    ``stac.resample: kaiser`` with ``stac.mocap_hz`` and ``stac.resample_hz`` (needs ``postprocess: gpu``) writes, after the ik_only
+    file and without changing it, a second file next to it (``resampled_path``) that holds the result at the other rate, resampled per
+    clip on the GPU by ``Stac.resample_result`` (DESIGN.md "Resampling fitted poses"); the two paths returned are those of today.
     """
     base_path = Path.cwd() if base_path is None else Path(base_path)
     kp_data = np.asarray(kp_data)
@@ -112,6 +115,8 @@ def _run_ik(stac, series, fit_offsets_path, ik_only_path, pre, start):
     sharded = world_size > 1 and mode == "none"
     if sharded and cfg.stac.continuous:  # (explicit gather = none with a fit file whose config turned out continuous)
         raise ValueError(GATHER_NONE_CONTINUOUS)
+    if sharded and pre.resample is not None:  # (gather = auto that resolved to none by the size of the output)
+        raise ValueError(RESAMPLE_SHARDED)
     post = {"continuous": bool(cfg.stac.continuous), "n_frames_per_clip": F, "infer_qvels": bool(cfg.stac.infer_qvels)} if pre.post_gpu else None
     if pre.smooth is not None:  # (postprocess = gpu: _smooth_mode)
         _check_smooth_clip(pre.smooth, _smooth_clip_len(cfg, kp_data.shape[0]))
@@ -119,6 +124,8 @@ def _run_ik(stac, series, fit_offsets_path, ik_only_path, pre, start):
     ik_data = stac.ik_only(kp_data, fit_data.offsets, gather=mode, **({"post": post} if pre.post_gpu else {}))
     if rank != 0 and not sharded and mode != "all":
         dist.barrier()  # this rank holds its own shard only: rank 0 post-processes and writes the gathered result
+        if pre.resample is not None:
+            dist.barrier()  # ... and the resampled one
         return fit_offsets_path, io.resolve_output_path(ik_only_path)
     if cfg.stac.continuous and post is None:
         ik_data = utils.handle_edge_effects(ik_data, F)
@@ -142,8 +149,42 @@ def _run_ik(stac, series, fit_offsets_path, ik_only_path, pre, start):
               f"Finished in {(time.time() - start) / 60:.2f} minutes")
         return fit_offsets_path, manifest
     ik_only_path = _write_result(stac, cfg, ik_data, ik_only_path, pre.report, rank == 0)
+    if pre.resample is not None:
+        _write_resampled(stac, cfg, ik_data, ik_only_path, pre, rank == 0)
     print(f"Saved ik_only to {ik_only_path}. Finished in {(time.time() - start) / 60:.2f} minutes")
     return fit_offsets_path, ik_only_path
+
+
+def resampled_path(ik_only_path, to_hz) -> Path:
+    """``ik_only.h5`` and 50 -> ``ik_only.50hz.h5`` (29.97 -> ``ik_only.29.97hz.h5``): where ``stac.resample`` writes its file."""
+    p = Path(ik_only_path)
+    return p.with_name(f"{p.stem}.{to_hz:g}hz{p.suffix}")
+
+
+def _write_resampled(stac, cfg, ik_data, ik_only_path, pre, writes: bool) -> Path:
+    """``stac.resample``: the packaged ik_only result at ``stac.resample_hz`` as a second file next to the first, through the writer
+    of every result file (and with its own report under ``stac.report: on``).  The config stored in it is the first file's with the
+    five keys of the caller's and, where the run is not continuous, ``n_frames_per_clip`` set to the rows of a resampled clip, so that
+    ``fit_report`` and ``smooth_result`` of that file cut the right clips."""
+    from . import post as gpost
+    from .config import validate_config
+
+    opt = pre.resample
+    path = resampled_path(ik_only_path, opt["to_hz"])
+    if writes:
+        stored = cfg.to_dict()
+        stored["stac"].update({"resample": opt["kind"], "mocap_hz": opt["from_hz"], "resample_hz": opt["to_hz"], "resample_lobes": opt["lobes"],
+                               "resample_beta": opt["beta"], "postprocess": "gpu"})
+        if "reference_marker_order" in stored["stac"]:  # (the caller's decides the rows of this run, and the pre-flight refused a true one)
+            stored["stac"]["reference_marker_order"] = False
+        if not cfg.stac.continuous:
+            stored["stac"]["n_frames_per_clip"] = gpost.resample_rows(int(cfg.stac.n_frames_per_clip), opt["up"], opt["down"])
+        stored = validate_config(stored)
+        # (the clips are those of the config stored with the ik_only file; the Stac object keeps the caller's)
+        data = stac.resample_result(ik_data, opt["from_hz"], opt["to_hz"], lobes=opt["lobes"], beta=opt["beta"], cfg=cfg)
+    path = _write_result(stac, stored if writes else cfg, data if writes else None, path, pre.report, writes)
+    print(f"resample: saved the ik_only result at {opt['to_hz']:g} Hz to {path}", flush=True)
+    return path
 
 
 class _Preflight:
@@ -172,6 +213,9 @@ class _Preflight:
         self.donors_mode, self.donors_triples = _fill_donors_mode(self.cfg)
         self.report = _report_mode(self.cfg)
         self.smooth = _smooth_mode(self.cfg)
+        self.resample = _resample_mode(self.cfg)
+        if stac.skip_ik_only:  # (checked all the same; there is no ik_only file to resample)
+            self.resample = None
         self.marker_order = not stac.skip_ik_only and bool(stac.get("reference_marker_order", False))
         if self.report[0] and self.marker_order:
             F = int(self.fit_cfg.stac.n_frames_per_clip)
@@ -189,6 +233,8 @@ class _Preflight:
             # an EXPLICIT gather = none cannot serve a continuous run (cross-fades reach across shard borders)
             if self.fit_cfg.stac.continuous:
                 raise ValueError(GATHER_NONE_CONTINUOUS)
+            if self.resample is not None:
+                raise ValueError(RESAMPLE_SHARDED)
         # stac.postprocess (engine extension, read from the caller's config like gather): "host" (default) = the numpy functions
         # of utils.py; "gpu" = ik_only stitches and infers qvel on the device (post.py) and the two host steps are skipped
         self.post_gpu = _postprocess_mode(self.cfg) == "gpu"
@@ -313,6 +359,14 @@ def _smooth_mode(cfg):
     ``post["smooth"]`` of ``Stac.ik_only`` takes them.  ``ValueError`` for a bad value of any of the four keys, and for smoothing
     without ``postprocess: gpu`` or with ``reference_marker_order: true``."""
     opt = smooth_options(cfg.stac)
+    return None if opt["kind"] == "off" else opt
+
+
+def _resample_mode(cfg):
+    """``stac.resample``: "off" (default) | "kaiser" -> None, or the options of ``config.resample_options``.  ``ValueError`` for a
+    bad value of any of the five keys, a missing rate, a ratio or window that the kernel does not take, and for resampling without
+    ``postprocess: gpu`` or with ``reference_marker_order: true``."""
+    opt = resample_options(cfg.stac)
     return None if opt["kind"] == "off" else opt
 
 

@@ -255,6 +255,64 @@ class Stac:
 
         return replace(data, qpos_raw=raw, **host)
 
+    # -- resample_result (engine extension; DESIGN.md "Resampling fitted poses") ---------------------------------------------
+    def resample_result(self, data, from_hz, to_hz, lobes=10, beta=5.0, *, cfg=None) -> StacData:
+        """A stored ``ik_only`` result at another frame rate, on the GPU (``post.resample``): the sibling of ``smooth_result``.
+        ``data``: the path of a result file (a ``*.manifest.json`` reads a sharded run), whose stored config decides the clips -- a
+        continuous run is one clip, else clips of its ``n_frames_per_clip`` rows -- or a ``StacData``, with ``cfg`` (None: this
+        object's config).  Every clip of L rows becomes one of ``post.resample_rows(L, U, D)`` rows (U / D = ``to_hz / from_hz``): ``qpos`` is
+        resampled with this model's quaternion columns and the engine's bounds, ``kp_data`` with the same filter as plain columns;
+        ``xpos`` / ``xquat`` / ``marker_sites`` are the kinematics of the new ``qpos`` under the stored ``offsets``; ``qvel`` is
+        inferred again when the result had one, with the real step ``1 / to_hz`` (the source file's was the model's ``timestep``);
+        every per-frame mark (``kp_gap``, ``kp_rejected``, ...) is that of the nearest input row
+        (``post.resample_source_rows``); ``qpos_raw`` is empty, its rows no longer correspond.  A NaN spreads over the outputs
+        whose window holds it, and the first and last row of a clip are held beyond its ends, not extrapolated.
+        The engine's offsets are left as they were."""
+        from dataclasses import replace
+
+        from . import io
+        from . import post as gpost
+
+        U, D = gpost.resample_ratio(from_hz, to_hz)
+        taps = gpost.resample_taps(U, D, lobes=lobes, beta=beta)
+        cfg = self.cfg if cfg is None else cfg
+        if not isinstance(data, StacData):
+            cfg, data = io.load_stac_result(data)
+        qpos = np.asarray(data.qpos, dtype=np.float32)
+        kp = np.asarray(data.kp_data, dtype=np.float32)
+        nq, K = self.setup.tables.nq, self.setup.tables.nsite
+        if qpos.ndim != 2 or qpos.shape[1] != nq:
+            raise ValueError(f"resample_result: qpos must be [frames, {nq}], got {qpos.shape}")
+        N = qpos.shape[0]
+        if kp.ndim != 2 or kp.shape[0] != N:
+            raise ValueError(f"resample_result: kp_data {kp.shape} does not have the {N} rows of qpos")
+        L = N if bool(cfg.stac.continuous) else int(cfg.stac.n_frames_per_clip)
+        if N == 0 or L < 1 or N % L != 0:
+            raise ValueError(f"resample_result: cannot cut {N} rows into clips of {L} frames")
+        Lo = gpost.resample_rows(L, U, D)
+        eng = self.engine
+        to_dev = lambda a: torch.as_tensor(np.array(a)).to(eng.device)  # noqa: E731  (a copy: torch does not wrap a read-only array)
+        keep = eng.get_site_pos()
+        eng.set_site_pos(torch.as_tensor(np.array(data.offsets, dtype=np.float32)).reshape(K, 3))
+        try:
+            taps_dev = to_dev(taps)
+            q = gpost.resample(to_dev(qpos), L, U, D, taps_dev, self._quat_cols(), lb=eng.lb, ub=eng.ub)
+            fk = eng.fk(q, want=("xpos", "xquat", "site_xpos"))
+            out = {"qpos": q, "xpos": fk["xpos"], "xquat": fk["xquat"], "marker_sites": fk["site_xpos"],
+                   "kp_data": gpost.resample(to_dev(kp), L, U, D, taps_dev)}
+            if np.asarray(data.qvel).size:
+                out["qvel"] = gpost.infer_qvel(q, Lo, 1.0 / float(to_hz), self._freejoint)
+            host = {k: v.cpu().numpy() for k, v in out.items()}
+        finally:
+            eng.set_site_pos(keep)
+        src = (np.arange(N // L, dtype=np.int64)[:, None] * L + gpost.resample_source_rows(L, U, D)[None, :]).reshape(-1)
+        for name, _ in io.OPTIONAL_FIELDS:
+            mark = np.asarray(getattr(data, name))
+            if name != "qpos_raw" and mark.size:
+                host[name] = mark[src]
+        self._log(f"resample_result: {from_hz} -> {to_hz} Hz ({U} / {D}, {taps.shape[1]} taps): {N // L} clip(s) of {L} rows -> {Lo} rows each")
+        return replace(data, qpos_raw=np.array([]), **host)
+
     # -- fit_offsets (stac.py:253-354) ------------------------------------------------------------------
     def fit_offsets(self, kp_data, time_indices=None) -> StacData:
         """Alternate pose and offset optimisation.

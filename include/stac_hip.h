@@ -309,6 +309,34 @@ int32_t stac_post_qvel(const float *qpos, int64_t N, int32_t nq, int32_t F, doub
 int32_t stac_post_smooth(const float *qpos, int64_t N, int32_t nq, int32_t clip_len, int32_t half_window, const float *taps,
                          const int32_t *quat_cols, int32_t n_quat, const float *lb, const float *ub, float *out, void *stream);
 
+/* Resampling fitted poses to another frame rate (stac.resample). */
+
+/* HOST.  Output rows of one clip of clip_len input rows resampled up by `up` and down by `down`:
+ * ((clip_len - 1) * up) / down + 1 -- output m sits at input position m * down / up and none lies beyond the last sample.
+ * Negative (STAC_ERR_INVALID) for clip_len < 1 (or beyond 2^56), up outside 1 .. 32 or down outside 1 .. 64. */
+int64_t stac_post_resample_rows(int64_t clip_len, int32_t up, int32_t down);
+
+/* Resamples x [n_rows][n_cols], whole clips of clip_len rows, along time by up / down with a polyphase filter
+ * (csrc/stac_resample.hpp states the rule) into out [out_rows][n_cols], out_rows =
+ * (n_rows / clip_len) * stac_post_resample_rows(clip_len, up, down): the outputs of a clip follow those of the clip before.
+ * Output m of a clip, at n = (m * down) / up and phase r = (m * down) % up, is the sum over j = 0 .. W - 1 of
+ * taps_dev[r][j] * (input row n + j - H + 1 of the clip, the index clamped to 0 .. clip_len - 1), H = half / up + 1, W = 2 H,
+ * in float32, one rounding per operation in the order of j.  No window reaches into another clip.
+ * taps_dev [up][W], DEVICE memory (post.resample_taps makes it; `half` is the filter's half-length lobes * max(up, down)).
+ * quat_cols [n_quat], HOST memory: the first columns of the quaternion blocks of a row (n_quat <= 64, blocks inside the row and
+ * disjoint); the rows of a block's window are brought into the hemisphere of the block in input row n (a zero or NaN dot product
+ * counts as +), weighted, summed and divided by the float32 norm, and where the norm is not > 0 the output is that block.
+ * lb, ub [n_cols], both or neither (NULL): every other column is clamped to them with comparisons, so a NaN passes; a zero tap
+ * is multiplied like any other, so a NaN in a window reaches the output.
+ * W <= 256.  x, taps_dev, lb, ub, out 4-byte aligned; no two buffers may overlap -- in place is not possible.  A bad size or
+ * ratio, W > 256, rows that are not whole clips, out_rows different from the rule's value, overlapping or misplaced quaternion
+ * blocks, lb without ub, a bad pointer, alignment or overlap is STAC_ERR_INVALID before anything is launched.
+ * One launch on `stream`; no copy from or to the host, no synchronisation, no workgroup waits for another, no atomics:
+ * a second call gives the same bits, and the call can be captured. */
+int32_t stac_post_resample(const float *x, int64_t n_rows, int32_t n_cols, int64_t clip_len, int32_t up, int32_t down, int32_t half,
+                           const float *taps_dev, const int32_t *quat_cols, int32_t n_quat, const float *lb, const float *ub, float *out,
+                           int64_t out_rows, void *stream);
+
 /* ---- Filling missing keypoints before the fit (no stac_model needed; the current device is used) --------------------
  * DESIGN.md "Filling missing keypoints".  Replaces the gap filling that every user of the reference writes by hand in
  * front of stac_mjx.main.run_stac (stac_mjx/main.py:33-139 takes kp_data as it comes and has no answer to a NaN: the
@@ -353,6 +381,101 @@ int32_t stac_prep_fill(const float *kp, int64_t n_frames, int32_t n_kp, int32_t 
  * One launch on `stream`, no workspace; no workgroup waits for another. */
 int32_t stac_prep_reject(const float *kp, int64_t n_frames, int32_t n_kp, int32_t half_window, double thr, double min_dev,
                          float *out, uint8_t *flag, void *stream);
+
+/* ---- Rejecting keypoints that break pairwise distances (stac.reject_pairwise; no stac_model needed) -----------------
+ * DESIGN.md section 14. */
+
+/* HOST.  Bytes of device workspace that stac_prep_pairwise needs for a series of n_frames x n_kp keypoints: 4 bytes per
+ * pair of keypoints and frame (rounded up to whole tiles of 64 frames) plus 57 376 bytes per pair; 8 for n_kp == 1.
+ * Negative (STAC_ERR_INVALID) for n_frames < 1 or n_kp < 1 or a size beyond int64, STAC_ERR_CAPACITY for n_kp > 64. */
+int64_t stac_prep_pairwise_workspace(int64_t n_frames, int32_t n_kp);
+
+/* Rejects the keypoints of kp [n_frames][3 n_kp] that break the distributions of the pairwise distances over the whole
+ * series (csrc/stac_pairwise.hpp states the rule).  For the P = n_kp (n_kp - 1) / 2 pairs (a, b),
+ * a < b, in lexicographic order: the float32 distance in every frame where both keypoints are present (no coordinate NaN
+ * or infinite) and the distance is finite; its exact median and median absolute deviation over those n frames (n < 3: the
+ * pair decides nothing); the pair is bad in a frame iff its deviation from the median exceeds both thr * mad and min_dev.
+ * Per frame the keypoint in the most bad pairs (ties: the lowest index) is rejected while that count is at least `votes`,
+ * and its pairs are removed before the next is looked for.
+ * out [n_frames][3 n_kp]: a rejected keypoint is three quiet NaN 0x7FC00000, every other element is kp's bit for bit.
+ * flag [n_frames][n_kp]: 1 where rejected.  pair_n [P] (n), pair_med [P], pair_mad [P] (quiet NaN where n < 3): room
+ * for at least one element each, also for n_kp == 1.
+ * thr and min_dev finite and >= 0 (the host passes thr = nsigma * 1.4826); votes >= 1; n_kp <= 64 (STAC_ERR_CAPACITY
+ * above).  workspace: at least stac_prep_pairwise_workspace bytes, its contents do not matter; it may be reused once the
+ * call has finished on `stream`.  kp, out 4-byte aligned, pair_n, pair_med, pair_mad, workspace 8-byte aligned; no two
+ * buffers may overlap -- in place is not possible (all of it STAC_ERR_INVALID, before anything is launched).
+ * Two memsets and 14 launches on `stream` (one launch for n_kp == 1); no copy to the host, no synchronisation, no
+ * workgroup waits for another, no floating-point atomics: a second call gives the same bits. */
+int32_t stac_prep_pairwise(const float *kp, int64_t n_frames, int32_t n_kp, double thr, double min_dev, int32_t votes,
+                           float *out, uint8_t *flag, int64_t *pair_n, double *pair_med, double *pair_mad,
+                           void *workspace, int64_t workspace_bytes, void *stream);
+
+/* ---- Repairing left / right keypoint swaps before the fit (stac.repair_swaps; no stac_model needed) -----------------
+ * DESIGN.md section 15. */
+
+/* HOST.  Bytes of device workspace that stac_prep_swaps needs for a series of n_frames x n_kp keypoints: those of
+ * stac_prep_pairwise_workspace, whatever the candidates.  Negative (STAC_ERR_INVALID) for
+ * n_frames < 1 or n_kp < 1 or a size beyond int64, STAC_ERR_CAPACITY for n_kp > 64. */
+int64_t stac_prep_swaps_workspace(int64_t n_frames, int32_t n_kp);
+
+/* Exchanges, frame by frame, the two keypoints of a candidate pair of kp [n_frames][3 n_kp] where the pairwise distances
+ * say that they carry each other's label (csrc/stac_swap.hpp states the rule).  The statistics are
+ * those of stac_prep_pairwise over kp as given: for the P = n_kp (n_kp - 1) / 2 pairs, n, the exact median and the exact
+ * median absolute deviation of the float32 distance; a distance d is bad for a pair iff its deviation from that pair's
+ * median exceeds both thr * mad and min_dev.  For a candidate (a, b) in a frame, every third keypoint k whose pairs
+ * {a, k} and {b, k} both have n >= 3 and are both valid in the frame adds to b0 whether d(a, k) is bad for {a, k} and
+ * whether d(b, k) is bad for {b, k} (the frame as labelled), and to b1 whether d(b, k) is bad for {a, k} and whether
+ * d(a, k) is bad for {b, k} (the labels exchanged).  The candidate swaps in the frame iff b0 >= min_bad and
+ * 2 b1 <= b0.  Every decision is taken from the input frame alone.
+ * cand: HOST memory, [n_cand][2] keypoint indices (a, b) in either order, a != b, both in 0 .. n_kp - 1, every keypoint
+ * in at most one candidate (so n_cand <= n_kp / 2 <= 32); it is read before the call returns and may be NULL for
+ * n_cand == 0.
+ * out [n_frames][3 n_kp]: where a candidate swaps, the three words of a and of b exchanged bit for bit; every other
+ * element is kp's bit for bit.  flag [n_frames][n_cand]: 1 where the candidate swaps (room for n_frames bytes also for
+ * n_cand == 0, where nothing is written to it).  pair_n [P], pair_med [P], pair_mad [P]: as stac_prep_pairwise writes
+ * them for the same kp, bit for bit (room for at least one element each).
+ * thr and min_dev finite and >= 0 (the host passes thr = nsigma * 1.4826); min_bad >= 1; n_kp <= 64 (STAC_ERR_CAPACITY
+ * above).  workspace: at least stac_prep_swaps_workspace bytes, its contents do not matter; it may be reused once the
+ * call has finished on `stream`.  kp, out 4-byte aligned, pair_n, pair_med, pair_mad, workspace 8-byte aligned; no two
+ * device buffers may overlap -- in place is not possible.  A bad candidate table, size, parameter, pointer, alignment
+ * or overlap is STAC_ERR_INVALID before anything is launched.
+ * Two memsets and 14 launches on `stream` (one launch for n_kp == 1): the statistics part of stac_prep_pairwise and one
+ * decision launch that takes the candidate table by value.  No copy from or to the host, no synchronisation, no workgroup
+ * waits for another, no floating-point atomics: a second call gives the same bits, and the call can be captured. */
+int32_t stac_prep_swaps(const float *kp, int64_t n_frames, int32_t n_kp, const int32_t *cand /* HOST [n_cand][2] */,
+                        int32_t n_cand, double thr, double min_dev, int32_t min_bad, float *out,
+                        uint8_t *flag /* [n_frames][max(n_cand,1)] */, int64_t *pair_n, double *pair_med,
+                        double *pair_mad, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* ---- Filling long keypoint gaps from rigid neighbours (stac.fill_donors; no stac_model needed) ----------------------
+ * DESIGN.md section 17. */
+
+/* HOST.  Bytes of device workspace that stac_prep_donor needs for a series of n_frames x n_kp keypoints: those of
+ * stac_prep_fill_workspace.  Negative (STAC_ERR_INVALID) for n_frames < 1 or n_kp < 1 or a size beyond int64,
+ * STAC_ERR_CAPACITY for n_kp > 64. */
+int64_t stac_prep_donor_workspace(int64_t n_frames, int32_t n_kp);
+
+/* Fills the missing keypoints of kp [n_frames][3 n_kp] from the local frame of three other keypoints that are still
+ * tracked (csrc/stac_donor.hpp states the rule).  Missing, and the frames p (the last valid one
+ * before) and n (the first valid one after) of a missing keypoint k in frame t, are those of stac_prep_fill.
+ * don [n_kp][n_triples][3], DEVICE memory: row d of keypoint k is a donor triple (a, b, c); the list of k ends at the
+ * first row that is not three different indices in 0 .. n_kp - 1, all different from k (such a row is never used as an
+ * address).  The first usable triple of the list fills: the coordinates of k in the frame of (a, b, c) -- origin a, axes
+ * u = b - a, w = (c - a) less its part along u, m = u x w, not normalised -- are taken at p and at n, interpolated
+ * linearly in time (one neighbour only: held), and carried back by the frame of (a, b, c) at t, all in double with one
+ * rounding to float32.  A triple is usable iff a, b, c are not missing at t or at those of p, n that exist, the squared
+ * lengths of u, w, m are > 0 at each of them, and the three rounded values are finite.  Every test reads kp only.
+ * out [n_frames][3 n_kp]: the filled values; every other element is kp's bit for bit (what stays missing included).
+ * gap [n_frames][n_kp]: as stac_prep_fill writes it for the same kp.  src [n_frames][n_kp]: 0 observed, d + 1 filled by
+ * row d, 255 missing and left so (no usable triple, or a track without a valid frame).
+ * n_triples in 1 .. 8; n_kp <= 64 (STAC_ERR_CAPACITY above).  workspace: at least stac_prep_donor_workspace bytes, its
+ * contents do not matter; it may be reused once the call has finished on `stream`.  kp, don, out, gap 4-byte aligned,
+ * workspace 8-byte aligned; no two buffers may overlap -- in place is not possible.  A bad size, n_triples, pointer,
+ * workspace size, alignment or overlap is STAC_ERR_INVALID before anything is launched.
+ * Three launches on `stream`; no copy from or to the host, no synchronisation, no workgroup waits for another, no atomics:
+ * a second call gives the same bits, and the call can be captured. */
+int32_t stac_prep_donor(const float *kp, int64_t n_frames, int32_t n_kp, const int32_t *don, int32_t n_triples, float *out,
+                        int32_t *gap, uint8_t *src, void *workspace, int64_t workspace_bytes, void *stream);
 
 /* ---- Fit report: per-keypoint marker errors and exact quantiles (no stac_model needed; the current device is used) ----
  * DESIGN.md "Fit report".  The device counterpart of the reference's notebook graph_error.ipynb (per-frame summed squared

@@ -1,9 +1,7 @@
-"""The C ABI of ``libstac_hip.so`` (``include/stac_hip.h``) as ctypes sees it: the five structures, ONE table of the 31
-prototypes, ``declare`` that applies the table to a loaded library (``engine.load_library`` does, to whatever it loads), and the
-few helpers every caller of the library shares.  ``tests/test_host.py`` holds the table against the header and the structures against the compiler.
-A second table, ``PAIRWISE_PROTOTYPES``, holds the two functions of ``include/stac_hip_pairwise.h``; ``declare`` applies both.
-A third, ``SWAPS_PROTOTYPES``, holds the two of ``include/stac_hip_swaps.h`` in the same way, a fourth, ``DONOR_PROTOTYPES``, the two of
-``include/stac_hip_donor.h``, a fifth, ``RESAMPLE_PROTOTYPES``, the two of ``include/stac_hip_resample.h``.
+"""The C ABI of ``libstac_hip.so`` (``include/stac_hip.h``) as ctypes sees it: the five structures, ONE table of the 39
+prototypes in the header's order, ``declare`` that applies the table to a loaded library (``engine.load_library`` does, to whatever
+it loads), and the few helpers every caller of the library shares.  ``tests/test_host.py`` holds the table against the header and
+the structures against the compiler.
 """
 
 from __future__ import annotations
@@ -82,8 +80,8 @@ PROTOTYPES = {
     "stac_m_phase_partial": (i32, [vp, vp, vp, i32, vp, vp, vp]),
     "stac_m_phase_finish": (i32, [vp, vp, vp, vp, f32, vp, vp, vp]),
     "stac_render_scene_create": (vp, [vp, P(StacRenderTables)]),
-    "stac_render_scene_create_with_meshes": (vp, [vp, P(StacRenderTables), P(StacRenderMeshes)]),
     "stac_render_scene_destroy": (None, [vp]),
+    "stac_render_scene_create_with_meshes": (vp, [vp, P(StacRenderTables), P(StacRenderMeshes)]),
     "stac_render": (i32, [vp, i32, vp, vp, vp, vp, i32, vp, f32, i32, i32, vp, vp, vp, vp]),
     "stac_jpeg_header": (i64, [i32, i32, i32, i32, vp, i64]),
     "stac_jpeg_workspace_bytes": (i64, [i64, i32, i32, i32]),
@@ -92,37 +90,24 @@ PROTOTYPES = {
     "stac_post_stitch": (i32, [vp, i64, i32, i32, i32, P(f64), vp, i64, vp]),
     "stac_post_qvel": (i32, [vp, i64, i32, i32, f64, i32, f64, vp, vp]),
     "stac_post_smooth": (i32, [vp, i64, i32, i32, i32, _f32p, _i32p, i32, vp, vp, vp, vp]),
+    "stac_post_resample_rows": (i64, [i64, i32, i32]),
+    # the tap table of stac_post_resample is DEVICE memory, its quat_cols are HOST memory: an int32 pointer, not a device address
+    "stac_post_resample": (i32, [vp, i64, i32, i64, i32, i32, i32, vp, _i32p, i32, vp, vp, vp, i64, vp]),
     "stac_prep_fill_workspace": (i64, [i64, i32]),
     "stac_prep_fill": (i32, [vp, i64, i32, i32, vp, vp, vp, i64, vp]),
     "stac_prep_reject": (i32, [vp, i64, i32, i32, f64, f64, vp, vp, vp]),
+    "stac_prep_pairwise_workspace": (i64, [i64, i32]),
+    "stac_prep_pairwise": (i32, [vp, i64, i32, f64, f64, i32, vp, vp, vp, vp, vp, vp, i64, vp]),
+    "stac_prep_swaps_workspace": (i64, [i64, i32]),
+    # the candidate table of stac_prep_swaps is HOST memory: an int32 pointer, not a device address
+    "stac_prep_swaps": (i32, [vp, i64, i32, _i32p, i32, f64, f64, i32, vp, vp, vp, vp, vp, vp, i64, vp]),
+    "stac_prep_donor_workspace": (i64, [i64, i32]),
+    # the donor table of stac_prep_donor is DEVICE memory
+    "stac_prep_donor": (i32, [vp, i64, i32, vp, i32, vp, vp, vp, vp, i64, vp]),
     "stac_report_workspace": (i64, [i64, i32, i32]),
     "stac_report_errors": (i32, [P(StacReportParams)]),
 }  # fmt: skip
 ABI_SYMBOLS = tuple(PROTOTYPES)
-# every function include/stac_hip_pairwise.h declares (the second header: it does not count into the ABI version or ABI_SYMBOLS);
-# tests/test_pairwise_host.py holds this table against that header
-PAIRWISE_PROTOTYPES = {
-    "stac_prep_pairwise_workspace": (i64, [i64, i32]),
-    "stac_prep_pairwise": (i32, [vp, i64, i32, f64, f64, i32, vp, vp, vp, vp, vp, vp, i64, vp]),
-}  # fmt: skip
-# every function include/stac_hip_swaps.h declares (the third header, like the second); tests/test_swaps_host.py holds this table
-# against that header.  The candidate table of stac_prep_swaps is HOST memory: an int32 pointer, not a device address.
-SWAPS_PROTOTYPES = {
-    "stac_prep_swaps_workspace": (i64, [i64, i32]),
-    "stac_prep_swaps": (i32, [vp, i64, i32, _i32p, i32, f64, f64, i32, vp, vp, vp, vp, vp, vp, i64, vp]),
-}  # fmt: skip
-# every function include/stac_hip_donor.h declares (the fourth header, like the second); tests/test_donor_host.py holds this table
-# against that header.  The donor table of stac_prep_donor is DEVICE memory.
-DONOR_PROTOTYPES = {
-    "stac_prep_donor_workspace": (i64, [i64, i32]),
-    "stac_prep_donor": (i32, [vp, i64, i32, vp, i32, vp, vp, vp, vp, i64, vp]),
-}  # fmt: skip
-# every function include/stac_hip_resample.h declares (the fifth header, like the second); tests/test_resample_host.py holds this table
-# against that header.  The tap table of stac_post_resample is DEVICE memory, its quaternion columns are HOST memory.
-RESAMPLE_PROTOTYPES = {
-    "stac_post_resample_rows": (i64, [i64, i32, i32]),
-    "stac_post_resample": (i32, [vp, i64, i32, i64, i32, i32, i32, vp, _i32p, i32, vp, vp, vp, i64, vp]),
-}  # fmt: skip
 
 
 class StacHipError(RuntimeError):
@@ -130,9 +115,8 @@ class StacHipError(RuntimeError):
 
 
 def declare(lib):
-    """Declares ``restype`` and ``argtypes`` of every function of the five tables on ``lib`` (idempotent) -> ``lib``."""
-    for name, (restype, argtypes) in (*PROTOTYPES.items(), *PAIRWISE_PROTOTYPES.items(), *SWAPS_PROTOTYPES.items(), *DONOR_PROTOTYPES.items(),
-                                      *RESAMPLE_PROTOTYPES.items()):
+    """Declares ``restype`` and ``argtypes`` of every function of the table on ``lib`` (idempotent) -> ``lib``."""
+    for name, (restype, argtypes) in PROTOTYPES.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     return lib

@@ -13,11 +13,9 @@ from pathlib import Path
 
 CSRC = Path(__file__).resolve().parent / "csrc"
 LIB = CSRC / "libstac_hip.so"
-# every unit and every header of csrc: a new file cannot be missing from the build or from source_digest()
+# every unit and every header of csrc and of include/: a new file cannot be missing from the build or from source_digest()
 SOURCES = sorted(CSRC.glob("*.hip"))
-HEADERS = sorted(CSRC.glob("*.hpp")) + [CSRC.parents[1] / "include" / "stac_hip.h", CSRC.parents[1] / "include" / "stac_hip_pairwise.h",
-                                         CSRC.parents[1] / "include" / "stac_hip_swaps.h", CSRC.parents[1] / "include" / "stac_hip_donor.h",
-                                         CSRC.parents[1] / "include" / "stac_hip_resample.h"]
+HEADERS = sorted(CSRC.glob("*.hpp")) + sorted((CSRC.parents[1] / "include").glob("*.h"))
 # -amdgpu-opt-vgpr-liverange=false: SIOptimizeVGPRLiveRange is the pass behind round 3's stale-state defect (a latency-kernel
 # shape whose results depended on what the previous launch left in registers / scratch): with it off that shape is correct under
 # every poison pattern, with it on it is wrong on 36 of 36 models (profiles/r04/stale_spill_repro.txt, reproducer:

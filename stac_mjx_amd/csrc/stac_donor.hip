@@ -10,7 +10,6 @@
 // K <= 64: one chunk of the tile walk holds all keypoints.  Offsets are 64-bit element offsets; rows are 4-byte aligned only.
 #include <hip/hip_runtime.h>
 
-#include "../../include/stac_hip_donor.h"
 #include "stac_donor.hpp"
 #include "stac_host.hpp"
 #include "stac_prep_tile.hpp"
@@ -100,7 +99,7 @@ hipError_t launch_donor(const float *kp, int64_t T, int32_t K, const int32_t *do
 
 }  // namespace stac
 
-// ---- C ABI entry points (include/stac_hip_donor.h): every argument is checked before the device is touched --------------------------
+// ---- C ABI entry points (include/stac_hip.h): every argument is checked before the device is touched --------------------------
 extern "C" int64_t stac_prep_donor_workspace(int64_t n_frames, int32_t n_kp) {
     const int64_t b = prep_workspace_bytes(n_frames, n_kp);
     if (b < 0) return fail(STAC_ERR_INVALID, "stac_prep_donor_workspace: n_frames >= 1, n_kp >= 1 (and a workspace size within int64)");

@@ -35,8 +35,6 @@
 
 #include <cmath>
 
-#include "../../include/stac_hip_pairwise.h"
-#include "../../include/stac_hip_swaps.h"
 #include "stac_host.hpp"
 #include "stac_pairwise.hpp"
 #include "stac_swap.hpp"
@@ -395,7 +393,7 @@ static hipError_t launch_swaps(const float *kp, int64_t T, int32_t K, const Swap
 
 }  // namespace stac
 
-// ---- C ABI entry points (include/stac_hip_pairwise.h): every argument is checked before the device is touched ---------------------
+// ---- C ABI entry points of stac.reject_pairwise (include/stac_hip.h): every argument is checked before the device is touched -----
 extern "C" int64_t stac_prep_pairwise_workspace(int64_t n_frames, int32_t n_kp) {
     if (n_frames >= 1 && n_kp > kPairwiseMaxKp)
         return fail(STAC_ERR_CAPACITY, "stac_prep_pairwise_workspace: n_kp = " + std::to_string(n_kp) + " is above the " +
@@ -451,7 +449,7 @@ extern "C" int32_t stac_prep_pairwise(const float *kp, int64_t n_frames, int32_t
                                                                workspace, (hipStream_t)stream));
 }
 
-// ---- C ABI entry points (include/stac_hip_swaps.h) -------------------------------------------------------------------------------
+// ---- C ABI entry points of stac.repair_swaps (include/stac_hip.h) ----------------------------------------------------------------
 extern "C" int64_t stac_prep_swaps_workspace(int64_t n_frames, int32_t n_kp) {
     if (n_frames >= 1 && n_kp > kPairwiseMaxKp)
         return fail(STAC_ERR_CAPACITY, "stac_prep_swaps_workspace: n_kp = " + std::to_string(n_kp) + " is above the " +

@@ -21,7 +21,6 @@
 // 32 KiB, more than kernel arguments carry).
 #include <hip/hip_runtime.h>
 
-#include "../../include/stac_hip_resample.h"
 #include "stac_host.hpp"
 #include "stac_resample.hpp"
 
@@ -171,7 +170,7 @@ const char *bad_ratio(int64_t L, int32_t U, int32_t D) {
 
 }  // namespace stac
 
-// ---- C ABI entry points (include/stac_hip_resample.h): every argument is checked before the device is touched ------------------------
+// ---- C ABI entry points (include/stac_hip.h): every argument is checked before the device is touched ------------------------
 extern "C" int64_t stac_post_resample_rows(int64_t clip_len, int32_t up, int32_t down) {
     if (const char *bad = bad_ratio(clip_len, up, down)) return fail(STAC_ERR_INVALID, std::string("stac_post_resample_rows: ") + bad);
     return resample_rows(clip_len, up, down);

@@ -1,12 +1,10 @@
 """fill_donors, the parts that need no GPU: the rule of csrc/stac_donor.hpp as a stand-alone CPU program (under the address and
 undefined-behaviour sanitizers where the host compiler has them) that runs the staged scan serially with small tiles, against the
-numpy reference of tests/donor_cases.py; the config keys and the pre-flight refusal; the fourth prototype table against the fourth
-header; the argument checks of the entry points (they happen before the device is touched); ``prep.donor_table`` on hand-made
+numpy reference of tests/donor_cases.py; the config keys and the pre-flight refusal;
+the argument checks of the entry points (they happen before the device is touched); ``prep.donor_table`` on hand-made
 statistics; ``kp_gap`` through ``_prepare_series`` and the result files; and what the rule is worth, on the reference alone."""
 
 import ctypes as C
-import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -15,19 +13,13 @@ import pytest
 import donor_cases as dc
 import pairwise_cases as pw
 import prep_cases as pc
-from conftest import ROOT
-
-STAC_ERR_INVALID, STAC_ERR_CAPACITY = -1, -3
-HEADER = ROOT / "include" / "stac_hip_donor.h"
+import host_scaffold as hs
+from host_scaffold import STAC_ERR_INVALID, STAC_ERR_CAPACITY
 
 
 @pytest.fixture(scope="module")
 def lib():
-    from stac_mjx_amd.build import build_extension
-    from stac_mjx_amd.engine import load_library
-
-    build_extension()
-    return load_library()
+    return hs.loaded_library()
 
 
 # ---- the rule on the CPU, from the kernel's header, with any tile size -------------------------------------------------------------
@@ -129,16 +121,7 @@ int main(int argc, char **argv) {
 
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
-    cxx = next((c for c in (shutil.which("c++"), shutil.which("g++"), shutil.which("clang++")) if c), None)
-    assert cxx, "no host C++ compiler"
-    d = tmp_path_factory.mktemp("donor_host")
-    (d / "donor_cpu.cpp").write_text(_PROGRAM)
-    exe = d / "donor_cpu"
-    base = [cxx, "-O1", "-g", "-ffp-contract=off", "-std=c++17", f"-I{ROOT / 'stac_mjx_amd' / 'csrc'}", str(d / "donor_cpu.cpp"), "-o", str(exe)]
-    # with the address and undefined-behaviour sanitizers where the host compiler has their runtimes (a stand-alone CPU program)
-    if subprocess.run(base + ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"], capture_output=True, text=True).returncode != 0:
-        subprocess.run(base, check=True, capture_output=True, text=True)
-    return exe
+    return hs.build_cpu_program(tmp_path_factory, "donor", _PROGRAM, "-O1")
 
 
 @pytest.mark.parametrize("tile", [1, 2, 4, 7])
@@ -210,33 +193,23 @@ def test_the_cases_hold_what_they_are_meant_to():
 
 
 # ---- config and pre-flight ---------------------------------------------------------------------------------------------------------
-def _cfg(rodent_cfg, **over):
-    from stac_mjx_amd.config import validate_config
-
-    stac = dict(fit_offsets_path="fit.h5", ik_only_path="ik.h5", data_path="d.mat", continuous=False, n_fit_frames=4,
-                skip_fit_offsets=False, skip_ik_only=False, infer_qvels=False, n_frames_per_clip=2,
-                mujoco=dict(solver="newton", iterations=1, ls_iterations=4))
-    stac.update(over)
-    return validate_config({"model": dict(rodent_cfg), "stac": stac})
-
-
 def test_config_fill_donors_keys(rodent_cfg):
     from stac_mjx_amd.config import DONOR_DEFAULTS, DONORS_NEED_FILL, donor_options
     from stac_mjx_amd.main import _fill_donors_mode, _reject_pairwise_mode, _repair_swaps_mode
 
-    plain = _cfg(rodent_cfg)
+    plain = hs.stage_cfg(rodent_cfg)
     assert DONOR_DEFAULTS == {"fill_donors_triples": 4}
     assert donor_options(plain.stac) == ("off", 4) and _fill_donors_mode(plain) == ("off", 4) and "donors" not in plain.to_yaml()
-    off = _cfg(rodent_cfg, fill_donors=False)  # what YAML 1.1 makes of a bare `off`
+    off = hs.stage_cfg(rodent_cfg, fill_donors=False)  # what YAML 1.1 makes of a bare `off`
     assert off.stac.fill_donors == "off" and _fill_donors_mode(off) == ("off", 4)
-    assert _fill_donors_mode(_cfg(rodent_cfg, fill_donors="off", fill_donors_triples=8)) == ("off", 8)
+    assert _fill_donors_mode(hs.stage_cfg(rodent_cfg, fill_donors="off", fill_donors_triples=8)) == ("off", 8)
     for fill in ("linear", "hold"):
-        on = _cfg(rodent_cfg, fill_donors="auto", fill_missing=fill, fill_donors_triples=1)
+        on = hs.stage_cfg(rodent_cfg, fill_donors="auto", fill_missing=fill, fill_donors_triples=1)
         assert _fill_donors_mode(on) == ("auto", 1)
         assert _reject_pairwise_mode(on) == _reject_pairwise_mode(plain) and _repair_swaps_mode(on) == _repair_swaps_mode(plain)
     # auto without the fill: what no triple can fill would reach the solver as NaN
     for over in (dict(fill_donors="auto"), dict(fill_donors="auto", fill_missing="off")):
-        cfg = _cfg(rodent_cfg, **over)  # (the values are fine: the refusal is the pre-flight's)
+        cfg = hs.stage_cfg(rodent_cfg, **over)  # (the values are fine: the refusal is the pre-flight's)
         with pytest.raises(ValueError) as e:
             _fill_donors_mode(cfg)
         assert str(e.value) == DONORS_NEED_FILL
@@ -245,13 +218,13 @@ def test_config_fill_donors_keys(rodent_cfg):
            dict(fill_donors_triples=4.0), dict(fill_donors_triples="4"), dict(fill_donors_triples=True), dict(fill_donors_triples=None)]
     for over in bad:
         with pytest.raises(ValueError):
-            _cfg(rodent_cfg, fill_missing="linear", **over)
-        cfg = _cfg(rodent_cfg, fill_missing="linear")  # also when the key is set after validation: the run reads the caller's config
+            hs.stage_cfg(rodent_cfg, fill_missing="linear", **over)
+        cfg = hs.stage_cfg(rodent_cfg, fill_missing="linear")  # also when the key is set after validation: the run reads the caller's config
         cfg.stac.update(over)
         with pytest.raises(ValueError):
             _fill_donors_mode(cfg)
     with pytest.raises(ValueError):
-        _cfg(rodent_cfg, fill_donor="auto")  # an unknown key stays an error
+        hs.stage_cfg(rodent_cfg, fill_donor="auto")  # an unknown key stays an error
 
 
 def test_run_stac_refuses_donors_without_fill_before_any_work(tmp_path, rodent_cfg):
@@ -261,9 +234,9 @@ def test_run_stac_refuses_donors_without_fill_before_any_work(tmp_path, rodent_c
     names = list(rodent_cfg["KEYPOINT_MODEL_PAIRS"].keys())
     kp = np.zeros((4, 69), np.float32)
     with pytest.raises(ValueError) as e:  # before the model is even looked for: the path does not exist
-        run_stac(_cfg(rodent_cfg, fill_donors="auto"), kp, names, base_path=tmp_path / "nowhere")
+        run_stac(hs.stage_cfg(rodent_cfg, fill_donors="auto"), kp, names, base_path=tmp_path / "nowhere")
     assert str(e.value) == DONORS_NEED_FILL
-    cfg = _cfg(rodent_cfg, fill_missing="linear", fill_donors="auto")
+    cfg = hs.stage_cfg(rodent_cfg, fill_missing="linear", fill_donors="auto")
     cfg.stac.fill_donors_triples = 9  # a bad value set after validation
     with pytest.raises(ValueError, match="fill_donors_triples"):
         run_stac(cfg, kp, names, base_path=tmp_path / "nowhere")
@@ -271,65 +244,6 @@ def test_run_stac_refuses_donors_without_fill_before_any_work(tmp_path, rodent_c
 
 
 # ---- C ABI -------------------------------------------------------------------------------------------------------------------------
-def _c_class(ctype):
-    if "*" in ctype:
-        return "pointer"
-    base = ctype.replace("const", " ").split()
-    assert len(base) == 1 and base[0] in ("int32_t", "int64_t", "float", "double", "void"), ctype
-    return base[0]
-
-
-def _ctypes_class(t):
-    if t is None:
-        return "void"
-    if t in (C.c_void_p, C.c_char_p) or issubclass(t, C._Pointer):
-        return "pointer"
-    return {C.c_int32: "int32_t", C.c_int64: "int64_t", C.c_float: "float", C.c_double: "double"}[t]
-
-
-def _header_prototypes():
-    """Every ``ret stac_name(args);`` of include/stac_hip_donor.h -> name: (class of ret, [class of every argument])"""
-    text = re.sub(r"/\*.*?\*/", " ", HEADER.read_text(), flags=re.S)
-    text = "\n".join(ln for ln in text.splitlines() if not ln.lstrip().startswith("#"))
-    text = text.replace('extern "C" {', " ")
-    protos = {}
-    for stmt in text.split(";"):
-        stmt = " ".join(stmt.split())
-        if stmt in ("", "}"):
-            continue
-        m = re.fullmatch(r"(.*?)\b(stac_[a-z0-9_]+) ?\((.*)\)", stmt)
-        assert m, f"not a prototype: {stmt!r}"  # nothing of the header is passed over in silence
-        ret, name, args = m.groups()
-        protos[name] = (_c_class(ret), [_c_class(re.sub(r"\w+$", "", a.strip())) for a in args.split(",")])
-    return protos
-
-
-def test_fourth_abi_table_against_the_fourth_header(lib):
-    from stac_mjx_amd import abi, build
-
-    protos = _header_prototypes()
-    assert list(protos) == ["stac_prep_donor_workspace", "stac_prep_donor"] and set(protos) == set(abi.DONOR_PROTOTYPES)
-    for name, (ret, args) in protos.items():
-        restype, argtypes = abi.DONOR_PROTOTYPES[name]
-        assert len(argtypes) == len(args), name
-        assert [_ctypes_class(t) for t in argtypes] == args and _ctypes_class(restype) == ret, name
-        fn = getattr(lib, name)  # the library carries them, declared by abi.declare
-        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
-    assert len(abi.DONOR_PROTOTYPES["stac_prep_donor"][1]) == 11
-    # the four tables are disjoint; the other headers, their tables and the version are what they were
-    tables = (abi.PROTOTYPES, abi.PAIRWISE_PROTOTYPES, abi.SWAPS_PROTOTYPES, abi.DONOR_PROTOTYPES)
-    assert len(set().union(*tables)) == sum(len(t) for t in tables)
-    assert len(abi.PROTOTYPES) == 31 and len(abi.PAIRWISE_PROTOTYPES) == 2 and len(abi.SWAPS_PROTOTYPES) == 2
-    assert abi.ABI_SYMBOLS == tuple(abi.PROTOTYPES) and lib.stac_abi_version() == 3
-    for other in ("stac_hip.h", "stac_hip_pairwise.h", "stac_hip_swaps.h"):
-        assert "donor" not in (ROOT / "include" / other).read_text() and ROOT / "include" / other in build.HEADERS
-    assert HEADER in build.HEADERS and ROOT / "stac_mjx_amd" / "csrc" / "stac_donor.hip" in build.SOURCES
-    header = (ROOT / "stac_mjx_amd" / "csrc" / "stac_donor.hpp").read_text()
-    from stac_mjx_amd import prep
-
-    assert f"kDonorMaxTriples = {prep.DONOR_MAX_TRIPLES};" in header and f"kDonorMaxKp = {prep.PAIRWISE_MAX_KP};" in header
-
-
 def test_workspace_is_the_fill_workspace(lib):
     from stac_mjx_amd import prep
 
@@ -502,7 +416,7 @@ def test_kp_gap_of_a_run_is_the_gap_of_the_raw_series(tmp_path, rodent_cfg, rode
     raw_gap = pc.reference_fill(raw, "linear")[1]
 
     def prepare(**over):
-        cfg = _cfg(rodent_cfg, n_fit_frames=40, n_frames_per_clip=40, **over)
+        cfg = hs.stage_cfg(rodent_cfg, n_fit_frames=40, n_frames_per_clip=40, **over)
         pre = _Preflight(cfg, T, tmp_path / "fit.h5", kp_names=names)
         pre.check_config()
         pre.fill_mode = _fill_missing_mode(cfg)
@@ -564,7 +478,7 @@ def test_statistics_of_an_earlier_stage_are_taken_where_one_ran(tmp_path, rodent
             self.pair_stats = {"pair_n": pair_n, "pair_mad": pair_mad}
             return out, flag
 
-    cfg = _cfg(rodent_cfg, n_fit_frames=32, n_frames_per_clip=32, fill_missing="linear", fill_donors="auto", reject_pairwise="mad")
+    cfg = hs.stage_cfg(rodent_cfg, n_fit_frames=32, n_frames_per_clip=32, fill_missing="linear", fill_donors="auto", reject_pairwise="mad")
     pre = _Preflight(cfg, T, tmp_path / "fit.h5", kp_names=names)
     pre.check_config()
     pre.fill_mode = _fill_missing_mode(cfg)

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import host_scaffold as hs
 import donor_cases as dc
 import pairwise_cases as pw
 import prep_cases as pc
@@ -19,9 +20,7 @@ STAC_ERR_INVALID, STAC_ERR_CAPACITY = -1, -3
 
 
 def _lib():
-    from stac_mjx_amd.engine import load_library
-
-    return load_library()
+    return hs.loaded_library()
 
 
 class _Buffers:

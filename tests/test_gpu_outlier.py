@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import host_scaffold as hs
 import outlier_cases as oc
 import prep_cases as pc
 
@@ -16,9 +17,7 @@ PATTERN, FLAG_PATTERN, GUARD = -12345.0, 0xEE, 64
 
 
 def _lib():
-    from stac_mjx_amd.engine import load_library
-
-    return load_library()
+    return hs.loaded_library()
 
 
 def _tile():

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import host_scaffold as hs
 import post_cases as pc
 
 pytestmark = pytest.mark.gpu
@@ -15,9 +16,7 @@ PATTERN = -12345.0
 
 
 def _lib():
-    from stac_mjx_amd.engine import load_library
-
-    return load_library()
+    return hs.loaded_library()
 
 
 def _raw_stitch(lib, src, Cn, F, D, dst, rows, stream=None):

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import host_scaffold as hs
 import prep_cases as pc
 import report_cases as rc
 
@@ -21,9 +22,7 @@ WORK_PATTERN = 0x7FF8_DEAD_BEEF_0123
 
 
 def _lib():
-    from stac_mjx_amd.engine import load_library
-
-    return load_library()
+    return hs.loaded_library()
 
 
 def _tile():

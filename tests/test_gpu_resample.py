@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import host_scaffold as hs
 import resample_cases as rc
 
 pytestmark = pytest.mark.gpu
@@ -18,9 +19,7 @@ ULP1 = float(np.spacing(np.float32(1.0)))
 
 
 def _lib():
-    from stac_mjx_amd.engine import load_library
-
-    return load_library()
+    return hs.loaded_library()
 
 
 def _p(t):

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import host_scaffold as hs
 import post_cases as pc
 import smooth_cases as sc
 
@@ -18,9 +19,7 @@ STAC_ERR_INVALID = -1
 
 
 def _lib():
-    from stac_mjx_amd.engine import load_library
-
-    return load_library()
+    return hs.loaded_library()
 
 
 def _raw_smooth(lib, src, L, taps, cols, lb, ub, dst, stream=None):

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import host_scaffold as hs
 import swaps_cases as sc
 
 pytestmark = pytest.mark.gpu
@@ -16,9 +17,7 @@ STAC_ERR_INVALID, STAC_ERR_CAPACITY = -1, -3
 
 
 def _lib():
-    from stac_mjx_amd.engine import load_library
-
-    return load_library()
+    return hs.loaded_library()
 
 
 class _Buffers:

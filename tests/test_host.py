@@ -9,82 +9,52 @@ import pytest
 import torch
 import yaml
 
+import host_scaffold as hs
 from conftest import ROOT
 
 
 # ---- C ABI -----------------------------------------------------------------------------------------------
-_C_CLASSES = ("int32_t", "int64_t", "float", "double", "void")
-
-
-def _c_class(ctype: str) -> str:
-    """A C type of the header as one of: pointer, int32_t, int64_t, float, double, void."""
-    if "*" in ctype:
-        return "pointer"
-    base = ctype.replace("const", " ").split()
-    assert len(base) == 1 and base[0] in _C_CLASSES, ctype
-    return base[0]
-
-
-def _ctypes_class(t) -> str:
-    import ctypes as C
-
-    if t is None:
-        return "void"
-    if t in (C.c_void_p, C.c_char_p) or issubclass(t, C._Pointer):
-        return "pointer"
-    return {C.c_int32: "int32_t", C.c_int64: "int64_t", C.c_float: "float", C.c_double: "double"}[t]
-
-
-def _header_prototypes() -> dict:
-    """Every ``ret stac_name(args);`` of include/stac_hip.h -> name: (class of ret, [class of every argument])."""
-    text = re.sub(r"/\*.*?\*/", " ", (ROOT / "include" / "stac_hip.h").read_text(), flags=re.S)
-    text = re.sub(r"//[^\n]*", " ", text)
-    text = "\n".join(ln for ln in text.splitlines() if not ln.lstrip().startswith("#"))
-    text = text.replace('extern "C" {', " ")
-    text = re.sub(r"(typedef\s+struct\s+\w+|enum)\s*\{[^}]*\}\s*\w*\s*;", " ", text)  # struct and enum bodies
-    text = re.sub(r"typedef\s+struct\s+\w+\s+\w+\s*;", " ", text)  # opaque handles
-    protos = {}
-    for stmt in text.split(";"):
-        stmt = " ".join(stmt.split())
-        if stmt in ("", "}"):  # (the closing brace of extern "C")
-            continue
-        m = re.fullmatch(r"(.*?)\b(stac_[a-z0-9_]+) ?\((.*)\)", stmt)
-        assert m, f"not a prototype: {stmt!r}"  # nothing of the header is passed over in silence
-        ret, name, args = m.groups()
-        args = [] if args.strip() == "void" else [a.strip() for a in args.split(",")]
-        # an argument is its type followed by its name: what is left without the last identifier is the type
-        protos[name] = (_c_class(ret), [_c_class(re.sub(r"\w+$", "", a)) for a in args])
-    return protos
-
-
 def test_library_exports_every_declared_symbol():
-    """The ONE binding table (abi.PROTOTYPES) against the header: the same names, the same number of arguments, every argument and
-    return value of the same class; and the loaded library carries exactly the table."""
-    from stac_mjx_amd.build import build_extension
-    from stac_mjx_amd.engine import ABI_SYMBOLS, load_library
-    from stac_mjx_amd import abi
+    """The ONE binding table (abi.PROTOTYPES) against the ONE header: the same names in the same order, the same number of arguments,
+    every argument and return value of the same class; and the loaded library carries exactly the table."""
+    from stac_mjx_amd import abi, build, prep
+    from stac_mjx_amd.engine import ABI_SYMBOLS
 
-    build_extension()
-    header = (ROOT / "include" / "stac_hip.h").read_text()
-    declared = set(re.findall(r"\b(stac_[a-z0-9_]+)\s*\(", header))
+    lib = hs.loaded_library()
+    declared = set(re.findall(r"\b(stac_[a-z0-9_]+)\s*\(", hs.HEADER.read_text()))
     assert declared == set(ABI_SYMBOLS), declared ^ set(ABI_SYMBOLS)
-    protos = _header_prototypes()
-    assert len(protos) == 31 and set(protos) == declared and ABI_SYMBOLS == tuple(abi.PROTOTYPES)
+    protos, n_statements = hs.header_prototypes()
+    assert n_statements == len(protos) == 39  # (a name declared twice is one key and two statements)
+    assert set(protos) == declared and ABI_SYMBOLS == tuple(abi.PROTOTYPES) == tuple(protos)
+    order = list(protos)
+    at = order.index
+    # preparation entry points beside stac_prep_fill / stac_prep_reject, the resampler beside stac_post_smooth, sizes first
+    assert order[at("stac_prep_reject") + 1: at("stac_prep_reject") + 7] == [
+        "stac_prep_pairwise_workspace", "stac_prep_pairwise", "stac_prep_swaps_workspace", "stac_prep_swaps",
+        "stac_prep_donor_workspace", "stac_prep_donor"]
+    assert order[at("stac_post_smooth") + 1: at("stac_post_smooth") + 3] == ["stac_post_resample_rows", "stac_post_resample"]
     for name, (ret, args) in protos.items():
         assert name in abi.PROTOTYPES, name
         restype, argtypes = abi.PROTOTYPES[name]
         assert len(argtypes) == len(args), name
-        assert [_ctypes_class(t) for t in argtypes] == args, name
-        assert _ctypes_class(restype) == ret, name
+        assert [hs.ctypes_class(t) for t in argtypes] == [a[0] for a in args], name
+        assert hs.ctypes_class(restype) == ret, name
     assert not set(abi.PROTOTYPES) - set(protos)
     assert [n for n, (r, _) in abi.PROTOTYPES.items() if r is None] == ["stac_model_destroy", "stac_render_scene_destroy"]
-    lib = load_library()
+    assert len(abi.PROTOTYPES["stac_prep_swaps"][1]) == 16 and len(abi.PROTOTYPES["stac_prep_donor"][1]) == 11
+    assert [a[1] for a in protos["stac_post_resample"][1]] == ["x", "n_rows", "n_cols", "clip_len", "up", "down", "half", "taps_dev", "quat_cols",
+                                                               "n_quat", "lb", "ub", "out", "out_rows", "stream"]
     for s in declared:
         assert hasattr(lib, s), s
-        fn = getattr(lib, s)
+        fn = getattr(lib, s)  # the library carries them, declared by abi.declare
         assert fn.restype is abi.PROTOTYPES[s][0] and list(fn.argtypes) == list(abi.PROTOTYPES[s][1]), s
     assert lib.stac_abi_version() == 3
     assert lib.stac_device_count() >= 0
+    # one header, and every file of the library in the build and in source_digest()
+    assert list((ROOT / "include").glob("*.h")) == [hs.HEADER] and hs.HEADER in build.HEADERS
+    assert set(hs.CSRC.glob("*.hip")) == set(build.SOURCES) and set(hs.CSRC.glob("*.hpp")) | {hs.HEADER} == set(build.HEADERS)
+    header = (hs.CSRC / "stac_donor.hpp").read_text()  # the capacities Python states are the kernel's
+    assert f"kDonorMaxTriples = {prep.DONOR_MAX_TRIPLES};" in header and f"kDonorMaxKp = {prep.PAIRWISE_MAX_KP};" in header
 
 
 def test_ctypes_structures_have_the_compilers_layout(tmp_path):

@@ -3,16 +3,16 @@ reference of tests/outlier_cases.py, what the reference finds in a series with k
 ``stac_prep_reject`` (they happen before the device is touched) and ``kp_rejected`` through the result files."""
 
 import ctypes as C
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
 import outlier_cases as oc
+import host_scaffold as hs
 from conftest import ROOT
+from host_scaffold import STAC_ERR_INVALID
 
-STAC_ERR_INVALID = -1
 TILE = 64  # prep.TILE_FRAMES (asserted below)
 
 
@@ -76,16 +76,7 @@ int main(int argc, char **argv) {
 
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
-    cxx = next((c for c in (shutil.which("c++"), shutil.which("g++"), shutil.which("clang++")) if c), None)
-    assert cxx, "no host C++ compiler"
-    d = tmp_path_factory.mktemp("outlier_host")
-    (d / "outlier_cpu.cpp").write_text(_PROGRAM)
-    exe = d / "outlier_cpu"
-    base = [cxx, "-O2", "-g", "-ffp-contract=off", "-std=c++17", f"-I{ROOT / 'stac_mjx_amd' / 'csrc'}", str(d / "outlier_cpu.cpp"), "-o", str(exe)]
-    # with the address and undefined-behaviour sanitizers where the host compiler has their runtimes (a stand-alone CPU program)
-    if subprocess.run(base + ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"], capture_output=True, text=True).returncode != 0:
-        subprocess.run(base, check=True, capture_output=True, text=True)
-    return exe
+    return hs.build_cpu_program(tmp_path_factory, "outlier", _PROGRAM, "-O2")
 
 
 @pytest.mark.parametrize("h", oc.HS)
@@ -187,28 +178,18 @@ def test_recall_every_injected_spike_and_nothing_else():
 
 
 # ---- config -----------------------------------------------------------------------------------------------------------------------
-def _cfg(rodent_cfg, **over):
-    from stac_mjx_amd.config import validate_config
-
-    stac = dict(fit_offsets_path="fit.h5", ik_only_path="ik.h5", data_path="d.mat", continuous=False, n_fit_frames=4,
-                skip_fit_offsets=False, skip_ik_only=False, infer_qvels=False, n_frames_per_clip=2,
-                mujoco=dict(solver="newton", iterations=1, ls_iterations=4))
-    stac.update(over)
-    return validate_config({"model": dict(rodent_cfg), "stac": stac})
-
-
 def test_config_reject_outliers_keys(rodent_cfg):
     from stac_mjx_amd import prep
     from stac_mjx_amd.config import OUTLIER_MAX_WINDOW
     from stac_mjx_amd.main import _reject_outliers_mode
 
-    plain = _cfg(rodent_cfg)
+    plain = hs.stage_cfg(rodent_cfg)
     assert _reject_outliers_mode(plain)[0] == "off" and "outlier" not in plain.to_yaml()  # absent stays absent
-    assert _reject_outliers_mode(_cfg(rodent_cfg, reject_outliers="off"))[0] == "off"
-    assert _reject_outliers_mode(_cfg(rodent_cfg, reject_outliers=False))[0] == "off"  # what YAML 1.1 makes of a bare `off`
-    mode, args = _reject_outliers_mode(_cfg(rodent_cfg, reject_outliers="hampel", fill_missing="linear"))
+    assert _reject_outliers_mode(hs.stage_cfg(rodent_cfg, reject_outliers="off"))[0] == "off"
+    assert _reject_outliers_mode(hs.stage_cfg(rodent_cfg, reject_outliers=False))[0] == "off"  # what YAML 1.1 makes of a bare `off`
+    mode, args = _reject_outliers_mode(hs.stage_cfg(rodent_cfg, reject_outliers="hampel", fill_missing="linear"))
     assert mode == "hampel" and args == {"half_window": 5, "n_sigma": 3.0, "min_dev": 0.001}  # the defaults
-    mode, args = _reject_outliers_mode(_cfg(rodent_cfg, reject_outliers="hampel", fill_missing="hold", outlier_window=16,
+    mode, args = _reject_outliers_mode(hs.stage_cfg(rodent_cfg, reject_outliers="hampel", fill_missing="hold", outlier_window=16,
                                             outlier_nsigma=2, outlier_min_dev=0))
     assert mode == "hampel" and args == {"half_window": 16, "n_sigma": 2.0, "min_dev": 0.0}
     assert OUTLIER_MAX_WINDOW == prep.MAX_HALF_WINDOW == 16
@@ -220,22 +201,22 @@ def test_config_reject_outliers_keys(rodent_cfg):
            dict(outlier_nsigma="3"), dict(outlier_min_dev=-0.001), dict(outlier_min_dev=float("inf")), dict(outlier_min_dev=None)]
     for over in bad:
         with pytest.raises(ValueError):
-            _reject_outliers_mode(_cfg(rodent_cfg, fill_missing="linear", **over))
-        cfg = _cfg(rodent_cfg, fill_missing="linear")  # also when the key is set after validation: the run reads the caller's config
+            _reject_outliers_mode(hs.stage_cfg(rodent_cfg, fill_missing="linear", **over))
+        cfg = hs.stage_cfg(rodent_cfg, fill_missing="linear")  # also when the key is set after validation: the run reads the caller's config
         cfg.stac.update(over)
         with pytest.raises(ValueError):
             _reject_outliers_mode(cfg)
     with pytest.raises(ValueError):
-        _cfg(rodent_cfg, outlier_windw=5)  # an unknown key stays an error
+        hs.stage_cfg(rodent_cfg, outlier_windw=5)  # an unknown key stays an error
     for fill in ({}, dict(fill_missing="off")):  # the solver cannot take the NaNs
         with pytest.raises(ValueError, match="fill_missing"):
-            _reject_outliers_mode(_cfg(rodent_cfg, reject_outliers="hampel", **fill))
+            _reject_outliers_mode(hs.stage_cfg(rodent_cfg, reject_outliers="hampel", **fill))
 
 
 def test_run_stac_refuses_rejecting_without_filling_before_any_work(tmp_path, rodent_cfg):
     from stac_mjx_amd.main import run_stac
 
-    cfg = _cfg(rodent_cfg, reject_outliers="hampel")
+    cfg = hs.stage_cfg(rodent_cfg, reject_outliers="hampel")
     with pytest.raises(ValueError, match="fill_missing"):  # before the model is even looked for: the path does not exist
         run_stac(cfg, np.zeros((4, 6), np.float32), ["a", "b"], base_path=tmp_path / "nowhere")
     assert not list(tmp_path.iterdir())
@@ -244,11 +225,7 @@ def test_run_stac_refuses_rejecting_without_filling_before_any_work(tmp_path, ro
 # ---- C ABI and wrapper ------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def lib():
-    from stac_mjx_amd.build import build_extension
-    from stac_mjx_amd.engine import load_library
-
-    build_extension()
-    return load_library()
+    return hs.loaded_library()
 
 
 def test_reject_argument_errors_need_no_device(lib):
@@ -311,38 +288,22 @@ def _data(n, with_rejected, seed=0):
     return d
 
 
-def _suffixes():
-    from stac_mjx_amd import io
-
-    return [".npz"] + ([".h5"] if io.h5py is not None else [])
-
-
-def _dataset_names(path):
-    from stac_mjx_amd import io
-
-    if path.suffix == ".npz":
-        with np.load(path) as f:
-            return set(f.files)
-    with io.h5py.File(path, "r") as f:
-        return set(f.keys())
-
-
 TODAY = {"config", "kp_names", "names_qpos", "names_xpos", "kp_data", "marker_sites", "offsets", "qpos", "qvel", "xpos", "xquat"}
 
 
 def test_kp_rejected_round_trip_and_old_files(tmp_path, rodent_cfg):
     from stac_mjx_amd import io
 
-    cfg = _cfg(rodent_cfg)
+    cfg = hs.stage_cfg(rodent_cfg)
     assert io.StacData.__dataclass_fields__["kp_rejected"] is list(io.StacData.__dataclass_fields__.values())[-1]  # a trailing field
     assert "kp_rejected" not in _data(4, False).as_dict() and set(_data(4, True).as_dict()) - set(_data(4, False).as_dict()) == {"kp_gap", "kp_rejected"}
-    for suffix in _suffixes():
+    for suffix in hs.result_suffixes():
         for with_rejected in (False, True):
             d = _data(6, with_rejected)
             path = io.save_data_to_h5(config=cfg, file_path=tmp_path / f"r{int(with_rejected)}{suffix}", **d.as_dict())
             assert path.suffix == suffix
             # without the option: exactly today's datasets, which is also what a file from before this field looks like
-            assert _dataset_names(path) == (TODAY | {"kp_gap", "kp_rejected"} if with_rejected else TODAY)
+            assert hs.dataset_names(path) == (TODAY | {"kp_gap", "kp_rejected"} if with_rejected else TODAY)
             _, back = io.load_stac_data(path)
             if with_rejected:
                 assert back.kp_rejected.dtype == np.uint8 and back.kp_rejected.shape == (6, 3)
@@ -355,7 +316,7 @@ def test_kp_rejected_round_trip_and_old_files(tmp_path, rodent_cfg):
         d = _data(6, True)
         only_gap = {k: v for k, v in d.as_dict().items() if k != "kp_rejected"}
         path = io.save_data_to_h5(config=cfg, file_path=tmp_path / f"g{suffix}", **only_gap)
-        assert _dataset_names(path) == TODAY | {"kp_gap"}
+        assert hs.dataset_names(path) == TODAY | {"kp_gap"}
         back = io.load_stac_data(path)[1]
         assert back.kp_rejected.size == 0 and np.array_equal(back.kp_gap, d.kp_gap)
 
@@ -364,7 +325,7 @@ def test_kp_rejected_shard_concatenation(tmp_path, rodent_cfg):
     from stac_mjx_amd import io
     from stac_mjx_amd.dist import shard_range
 
-    cfg = _cfg(rodent_cfg)
+    cfg = hs.stage_cfg(rodent_cfg)
     F, world = 2, 3
     for with_rejected in (True, False):
         full = _data(5 * F, with_rejected, seed=3)

@@ -1,11 +1,9 @@
 """reject_pairwise, the parts that need no GPU: the rule of csrc/stac_pairwise.hpp as a stand-alone CPU program against the numpy
 reference of tests/pairwise_cases.py, what the reference finds in the golden recording with 40-frame left / right swaps (and what the
-Hampel identifier finds there), the config keys, the second ABI table against the second header, the argument checks of
+Hampel identifier finds there), the config keys, the argument checks of
 ``stac_prep_pairwise`` (they happen before the device is touched) and ``kp_rejected_pairwise`` through the result files."""
 
 import ctypes as C
-import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -13,10 +11,9 @@ import pytest
 
 import outlier_cases as oc
 import pairwise_cases as pc
+import host_scaffold as hs
 from conftest import ROOT
-
-STAC_ERR_INVALID, STAC_ERR_CAPACITY = -1, -3
-HEADER = ROOT / "include" / "stac_hip_pairwise.h"
+from host_scaffold import STAC_ERR_INVALID, STAC_ERR_CAPACITY
 
 
 # ---- the rule on the CPU, from the kernels' header ---------------------------------------------------------------------------------
@@ -132,16 +129,7 @@ int main(int argc, char **argv) {
 
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
-    cxx = next((c for c in (shutil.which("c++"), shutil.which("g++"), shutil.which("clang++")) if c), None)
-    assert cxx, "no host C++ compiler"
-    d = tmp_path_factory.mktemp("pairwise_host")
-    (d / "pairwise_cpu.cpp").write_text(_PROGRAM)
-    exe = d / "pairwise_cpu"
-    base = [cxx, "-O2", "-g", "-ffp-contract=off", "-std=c++17", f"-I{ROOT / 'stac_mjx_amd' / 'csrc'}", str(d / "pairwise_cpu.cpp"), "-o", str(exe)]
-    # with the address and undefined-behaviour sanitizers where the host compiler has their runtimes (a stand-alone CPU program)
-    if subprocess.run(base + ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"], capture_output=True, text=True).returncode != 0:
-        subprocess.run(base, check=True, capture_output=True, text=True)
-    return exe
+    return hs.build_cpu_program(tmp_path_factory, "pairwise", _PROGRAM, "-O2")
 
 
 @pytest.mark.parametrize("K", pc.KS)
@@ -274,34 +262,24 @@ def test_motivating_swaps_of_40_frames_in_the_golden_recording(rodent_mocap, rod
 
 
 # ---- config -----------------------------------------------------------------------------------------------------------------------
-def _cfg(rodent_cfg, **over):
-    from stac_mjx_amd.config import validate_config
-
-    stac = dict(fit_offsets_path="fit.h5", ik_only_path="ik.h5", data_path="d.mat", continuous=False, n_fit_frames=4,
-                skip_fit_offsets=False, skip_ik_only=False, infer_qvels=False, n_frames_per_clip=2,
-                mujoco=dict(solver="newton", iterations=1, ls_iterations=4))
-    stac.update(over)
-    return validate_config({"model": dict(rodent_cfg), "stac": stac})
-
-
 def test_config_reject_pairwise_keys(rodent_cfg):
     from stac_mjx_amd import prep
     from stac_mjx_amd.config import PAIRWISE_NEEDS_FILL, pairwise_options
     from stac_mjx_amd.main import _reject_outliers_mode, _reject_pairwise_mode
 
-    plain = _cfg(rodent_cfg)
+    plain = hs.stage_cfg(rodent_cfg)
     assert _reject_pairwise_mode(plain)[0] == "off" and "pairwise" not in plain.to_yaml()  # absent stays absent
     assert pairwise_options(plain.stac) == ("off", 6.0, 0.002, 2)
-    assert _reject_pairwise_mode(_cfg(rodent_cfg, reject_pairwise="off"))[0] == "off"
-    off = _cfg(rodent_cfg, reject_pairwise=False)  # what YAML 1.1 makes of a bare `off`
+    assert _reject_pairwise_mode(hs.stage_cfg(rodent_cfg, reject_pairwise="off"))[0] == "off"
+    off = hs.stage_cfg(rodent_cfg, reject_pairwise=False)  # what YAML 1.1 makes of a bare `off`
     assert _reject_pairwise_mode(off)[0] == "off" and off.stac.reject_pairwise == "off"
-    mode, args = _reject_pairwise_mode(_cfg(rodent_cfg, reject_pairwise="mad", fill_missing="linear"))
+    mode, args = _reject_pairwise_mode(hs.stage_cfg(rodent_cfg, reject_pairwise="mad", fill_missing="linear"))
     assert mode == "mad" and args == {"n_sigma": 6.0, "min_dev": 0.002, "votes": 2}  # the defaults
-    mode, args = _reject_pairwise_mode(_cfg(rodent_cfg, reject_pairwise="mad", fill_missing="hold", pairwise_nsigma=8, pairwise_min_dev=0,
+    mode, args = _reject_pairwise_mode(hs.stage_cfg(rodent_cfg, reject_pairwise="mad", fill_missing="hold", pairwise_nsigma=8, pairwise_min_dev=0,
                                             pairwise_votes=3))
     assert mode == "mad" and args == {"n_sigma": 8.0, "min_dev": 0.0, "votes": 3}
     # the sibling is untouched: same return value with and without the new keys
-    assert _reject_outliers_mode(_cfg(rodent_cfg, reject_pairwise="mad", fill_missing="linear")) == _reject_outliers_mode(plain)
+    assert _reject_outliers_mode(hs.stage_cfg(rodent_cfg, reject_pairwise="mad", fill_missing="linear")) == _reject_outliers_mode(plain)
     header = (ROOT / "stac_mjx_amd" / "csrc" / "stac_pairwise.hpp").read_text()
     assert f"kPairwiseMaxKp = {prep.PAIRWISE_MAX_KP};" in header and prep.PAIRWISE_MAX_KP == 64
     bad = [dict(reject_pairwise="on"), dict(reject_pairwise="MAD"), dict(reject_pairwise=True), dict(reject_pairwise=1),
@@ -311,16 +289,16 @@ def test_config_reject_pairwise_keys(rodent_cfg):
            dict(pairwise_votes=True), dict(pairwise_votes=None), dict(pairwise_votes=2**31)]
     for over in bad:
         with pytest.raises(ValueError):
-            _reject_pairwise_mode(_cfg(rodent_cfg, fill_missing="linear", **over))
-        cfg = _cfg(rodent_cfg, fill_missing="linear")  # also when the key is set after validation: the run reads the caller's config
+            _reject_pairwise_mode(hs.stage_cfg(rodent_cfg, fill_missing="linear", **over))
+        cfg = hs.stage_cfg(rodent_cfg, fill_missing="linear")  # also when the key is set after validation: the run reads the caller's config
         cfg.stac.update(over)
         with pytest.raises(ValueError):
             _reject_pairwise_mode(cfg)
     with pytest.raises(ValueError):
-        _cfg(rodent_cfg, pairwise_nsigm=5)  # an unknown key stays an error
+        hs.stage_cfg(rodent_cfg, pairwise_nsigm=5)  # an unknown key stays an error
     for fill in ({}, dict(fill_missing="off")):  # the solver cannot take the NaNs: one text
         with pytest.raises(ValueError) as err:
-            _reject_pairwise_mode(_cfg(rodent_cfg, reject_pairwise="mad", **fill))
+            _reject_pairwise_mode(hs.stage_cfg(rodent_cfg, reject_pairwise="mad", **fill))
         assert str(err.value) == PAIRWISE_NEEDS_FILL and "fill_missing" in PAIRWISE_NEEDS_FILL
 
 
@@ -328,7 +306,7 @@ def test_run_stac_refuses_pairwise_without_filling_before_any_work(tmp_path, rod
     from stac_mjx_amd.config import PAIRWISE_NEEDS_FILL
     from stac_mjx_amd.main import run_stac
 
-    cfg = _cfg(rodent_cfg, reject_pairwise="mad")
+    cfg = hs.stage_cfg(rodent_cfg, reject_pairwise="mad")
     with pytest.raises(ValueError) as err:  # before the model is even looked for: the path does not exist
         run_stac(cfg, np.zeros((4, 6), np.float32), ["a", "b"], base_path=tmp_path / "nowhere")
     assert str(err.value) == PAIRWISE_NEEDS_FILL
@@ -338,61 +316,7 @@ def test_run_stac_refuses_pairwise_without_filling_before_any_work(tmp_path, rod
 # ---- C ABI and wrapper ------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def lib():
-    from stac_mjx_amd.build import build_extension
-    from stac_mjx_amd.engine import load_library
-
-    build_extension()
-    return load_library()
-
-
-def _c_class(ctype):
-    if "*" in ctype:
-        return "pointer"
-    base = ctype.replace("const", " ").split()
-    assert len(base) == 1 and base[0] in ("int32_t", "int64_t", "float", "double", "void"), ctype
-    return base[0]
-
-
-def _ctypes_class(t):
-    if t is None:
-        return "void"
-    if t in (C.c_void_p, C.c_char_p) or issubclass(t, C._Pointer):
-        return "pointer"
-    return {C.c_int32: "int32_t", C.c_int64: "int64_t", C.c_float: "float", C.c_double: "double"}[t]
-
-
-def _header_prototypes():
-    """Every ``ret stac_name(args);`` of include/stac_hip_pairwise.h -> name: (class of ret, [class of every argument])"""
-    text = re.sub(r"/\*.*?\*/", " ", HEADER.read_text(), flags=re.S)
-    text = "\n".join(ln for ln in text.splitlines() if not ln.lstrip().startswith("#"))
-    text = text.replace('extern "C" {', " ")
-    protos = {}
-    for stmt in text.split(";"):
-        stmt = " ".join(stmt.split())
-        if stmt in ("", "}"):
-            continue
-        m = re.fullmatch(r"(.*?)\b(stac_[a-z0-9_]+) ?\((.*)\)", stmt)
-        assert m, f"not a prototype: {stmt!r}"  # nothing of the header is passed over in silence
-        ret, name, args = m.groups()
-        protos[name] = (_c_class(ret), [_c_class(re.sub(r"\w+$", "", a.strip())) for a in args.split(",")])
-    return protos
-
-
-def test_second_abi_table_against_the_second_header(lib):
-    from stac_mjx_amd import abi, build
-
-    protos = _header_prototypes()
-    assert list(protos) == ["stac_prep_pairwise_workspace", "stac_prep_pairwise"] and set(protos) == set(abi.PAIRWISE_PROTOTYPES)
-    for name, (ret, args) in protos.items():
-        restype, argtypes = abi.PAIRWISE_PROTOTYPES[name]
-        assert len(argtypes) == len(args), name
-        assert [_ctypes_class(t) for t in argtypes] == args and _ctypes_class(restype) == ret, name
-        fn = getattr(lib, name)  # the library carries them, declared by abi.declare
-        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
-    # the first header, its table and the version are what they were
-    assert not set(abi.PAIRWISE_PROTOTYPES) & set(abi.PROTOTYPES) and len(abi.PROTOTYPES) == 31 and abi.ABI_SYMBOLS == tuple(abi.PROTOTYPES)
-    assert "pairwise" not in (ROOT / "include" / "stac_hip.h").read_text() and lib.stac_abi_version() == 3
-    assert HEADER in build.HEADERS and ROOT / "include" / "stac_hip.h" in build.HEADERS
+    return hs.loaded_library()
 
 
 def test_workspace_arithmetic(lib):
@@ -479,7 +403,7 @@ def test_kp_rejected_pairwise_round_trip_and_old_files(tmp_path, rodent_cfg):
                     names_qpos=["a", "b"], names_xpos=["w", "v"], kp_names=["k0", "k1", "k2"])
     assert "kp_rejected_pairwise" not in d.as_dict()
     assert list(io.StacData.__dataclass_fields__)[-1] == "kp_rejected"  # (the trailing field stays the trailing field)
-    cfg = _cfg(rodent_cfg)
+    cfg = hs.stage_cfg(rodent_cfg)
     suffixes = [".npz"] + ([".h5"] if io.h5py is not None else [])
     for suffix in suffixes:
         plain = io.save_data_to_h5(config=cfg, file_path=tmp_path / f"plain{suffix}", **d.as_dict())

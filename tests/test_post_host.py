@@ -3,31 +3,17 @@ device is touched), the ``stac.postprocess`` config key, and a CPU build of the 
 ``utils.handle_edge_effects`` / ``utils.compute_velocity_from_kinematics`` on the cases of tests/test_gpu_post.py."""
 
 import ctypes as C
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import post_cases as pc
-from conftest import ROOT
-
-STAC_ERR_INVALID = -1
+import host_scaffold as hs
 
 
 @pytest.fixture(scope="module")
 def lib():
-    from stac_mjx_amd.build import build_extension
-    from stac_mjx_amd.engine import load_library
-
-    build_extension()
-    return load_library()
-
-
-def _invalid(lib, rc):
-    msg = lib.stac_last_error().decode()
-    assert rc == STAC_ERR_INVALID and lib.stac_last_error_code() == STAC_ERR_INVALID and msg, (rc, msg)
-    return msg
+    return hs.loaded_library()
 
 
 def test_stitch_rows_formula(lib):
@@ -38,7 +24,7 @@ def test_stitch_rows_formula(lib):
     assert lib.stac_post_stitch_rows(0, 5, 10) == 0
     assert lib.stac_post_stitch_rows(4, 7, 1) == 4 * 7 and lib.stac_post_stitch_rows(3, 40, 32) == 3 * 40
     for bad in ((3, 0, 10), (3, 5, 0), (3, 5, 33), (-1, 5, 10)):
-        _invalid(lib, lib.stac_post_stitch_rows(*bad))
+        hs.invalid(lib, lib.stac_post_stitch_rows(*bad))
 
 
 def test_stitch_argument_errors_need_no_device(lib):
@@ -47,30 +33,30 @@ def test_stitch_argument_errors_need_no_device(lib):
     src, dst = C.c_void_p(0x1000), C.c_void_p(0x2000)
     R = pc.stitch_rows(3, 12)
     call = lambda src=src, Cn=3, F=12, ov=10, D=7, m=m, dst=dst, rows=R: lib.stac_post_stitch(src, Cn, F, ov, D, m, dst, rows, None)
-    _invalid(lib, call(F=0))
-    _invalid(lib, call(ov=0, rows=3 * 12))
-    _invalid(lib, call(ov=33, rows=3 * 12))
-    _invalid(lib, call(D=0))
-    _invalid(lib, call(Cn=-1))
-    assert "36" in _invalid(lib, call(rows=R + 1))  # the message names the row count it expected
-    _invalid(lib, call(src=None))
-    _invalid(lib, call(dst=None))
-    _invalid(lib, call(m=None))
+    hs.invalid(lib, call(F=0))
+    hs.invalid(lib, call(ov=0, rows=3 * 12))
+    hs.invalid(lib, call(ov=33, rows=3 * 12))
+    hs.invalid(lib, call(D=0))
+    hs.invalid(lib, call(Cn=-1))
+    assert "36" in hs.invalid(lib, call(rows=R + 1))  # the message names the row count it expected
+    hs.invalid(lib, call(src=None))
+    hs.invalid(lib, call(dst=None))
+    hs.invalid(lib, call(m=None))
     assert call(Cn=0, rows=0, src=None, dst=None, m=None) == 0  # nothing to do
-    _invalid(lib, call(Cn=0, rows=1))
+    hs.invalid(lib, call(Cn=0, rows=1))
 
 
 def test_qvel_argument_errors_need_no_device(lib):
     q, v = C.c_void_p(0x1000), C.c_void_p(0x2000)
     call = lambda q=q, N=12, nq=74, F=4, dt=0.02, fj=1, mx=20.0, v=v: lib.stac_post_qvel(q, N, nq, F, dt, fj, mx, v, None)
-    _invalid(lib, call(F=0))
-    assert "13" in _invalid(lib, call(N=13))  # N % F != 0
-    _invalid(lib, call(nq=6))           # a free joint needs 7
-    _invalid(lib, call(nq=0, fj=0))
-    _invalid(lib, call(dt=0.0))
-    _invalid(lib, call(N=-4))
-    _invalid(lib, call(q=None))
-    _invalid(lib, call(v=None))
+    hs.invalid(lib, call(F=0))
+    assert "13" in hs.invalid(lib, call(N=13))  # N % F != 0
+    hs.invalid(lib, call(nq=6))           # a free joint needs 7
+    hs.invalid(lib, call(nq=0, fj=0))
+    hs.invalid(lib, call(dt=0.0))
+    hs.invalid(lib, call(N=-4))
+    hs.invalid(lib, call(q=None))
+    hs.invalid(lib, call(v=None))
     assert call(N=0, q=None, v=None) == 0  # nothing to do
     assert call(N=0, nq=6, fj=0, q=None, v=None) == 0
 
@@ -133,14 +119,7 @@ extern "C" void host_qvel(const float *qpos, int64_t N, int32_t nq, int32_t F, i
 
 @pytest.fixture(scope="module")
 def hostlib(tmp_path_factory):
-    cxx = next((c for c in (shutil.which("c++"), shutil.which("g++"), shutil.which("clang++")) if c), None)
-    assert cxx, "no host C++ compiler"
-    d = tmp_path_factory.mktemp("post_host")
-    (d / "driver.cpp").write_text(_DRIVER)
-    so = d / "libpost_host.so"
-    subprocess.run([cxx, "-O2", "-ffp-contract=off", "-std=c++17", "-shared", "-fPIC", f"-I{ROOT / 'stac_mjx_amd' / 'csrc'}",
-                    str(d / "driver.cpp"), "-o", str(so)], check=True, capture_output=True, text=True)
-    h = C.CDLL(str(so))
+    h = hs.build_cpu_library(tmp_path_factory, "post", _DRIVER)
     fp, dp = C.POINTER(C.c_float), C.POINTER(C.c_double)
     h.host_stitch.argtypes = [fp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, dp, fp, C.c_int64]
     h.host_stitch.restype = None
@@ -151,10 +130,6 @@ def hostlib(tmp_path_factory):
     return h
 
 
-def _fp(a):
-    return a.ctypes.data_as(C.POINTER(C.c_float))
-
-
 def _cpu_stitch(h, x, F):
     from stac_mjx_amd.post import crossfade_mask
 
@@ -162,7 +137,7 @@ def _cpu_stitch(h, x, F):
     R = int(h.host_stitch_rows(Cn, F, pc.OV))
     m = np.ascontiguousarray(crossfade_mask(pc.OV))
     out = np.full((R,) + x.shape[2:], -12345.0, np.float32)
-    h.host_stitch(_fp(x), Cn, F, pc.OV, D, m.ctypes.data_as(C.POINTER(C.c_double)), _fp(out), R)
+    h.host_stitch(hs.fp(x), Cn, F, pc.OV, D, m.ctypes.data_as(C.POINTER(C.c_double)), hs.fp(out), R)
     return out
 
 
@@ -191,7 +166,7 @@ def test_cpu_build_qvel_equals_compute_velocity_from_kinematics(hostlib, freejoi
             pc.assert_host_gyro_is_meaningful(q, F)
         want = pc.host_qvel(q, F, dt, freejoint)
         got = np.full_like(want, -12345.0)
-        hostlib.host_qvel(_fp(q), q.shape[0], nq, F, int(freejoint), dt, pc.MAX_QVEL, _fp(got))
+        hostlib.host_qvel(hs.fp(q), q.shape[0], nq, F, int(freejoint), dt, pc.MAX_QVEL, hs.fp(got))
         a, b = pc.check_qvel(got, want, freejoint, label=f"F={F} C={Cn} nq={nq} dt={dt:.4g}")
         differ, total = differ + a, total + b
         if freejoint and F >= 7:

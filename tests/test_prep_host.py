@@ -3,56 +3,34 @@ happen before the device is touched), the staged scan of csrc/stac_prep.hip stat
 tile sizes against the numpy reference of tests/prep_cases.py, ``kp_gap`` through the result files, and the mask of ``viz_stac``."""
 
 import ctypes as C
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
 import prep_cases as pc
+import host_scaffold as hs
 from conftest import ROOT
-
-STAC_ERR_INVALID = -1
 
 
 @pytest.fixture(scope="module")
 def lib():
-    from stac_mjx_amd.build import build_extension
-    from stac_mjx_amd.engine import load_library
-
-    build_extension()
-    return load_library()
-
-
-def _invalid(lib, rc):
-    msg = lib.stac_last_error().decode()
-    assert rc == STAC_ERR_INVALID and lib.stac_last_error_code() == STAC_ERR_INVALID and msg, (rc, msg)
-    return msg
+    return hs.loaded_library()
 
 
 # ---- config ------------------------------------------------------------------------------------------------------------------
-def _cfg(rodent_cfg, **over):
-    from stac_mjx_amd.config import validate_config
-
-    stac = dict(fit_offsets_path="fit.h5", ik_only_path="ik.h5", data_path="d.mat", continuous=False, n_fit_frames=4,
-                skip_fit_offsets=False, skip_ik_only=False, infer_qvels=False, n_frames_per_clip=2,
-                mujoco=dict(solver="newton", iterations=1, ls_iterations=4))
-    stac.update(over)
-    return validate_config({"model": dict(rodent_cfg), "stac": stac})
-
-
 def test_config_fill_missing_key(rodent_cfg):
     from stac_mjx_amd.config import ConfigError
     from stac_mjx_amd.main import _fill_missing_mode
 
-    plain = _cfg(rodent_cfg)
+    plain = hs.stage_cfg(rodent_cfg)
     assert _fill_missing_mode(plain) == "off" and "fill_missing" not in plain.to_yaml()  # absent stays absent
     for mode in ("off", "linear", "hold"):
-        assert _fill_missing_mode(_cfg(rodent_cfg, fill_missing=mode)) == mode
-    assert _fill_missing_mode(_cfg(rodent_cfg, fill_missing=False)) == "off"  # what YAML 1.1 makes of a bare `off`
+        assert _fill_missing_mode(hs.stage_cfg(rodent_cfg, fill_missing=mode)) == mode
+    assert _fill_missing_mode(hs.stage_cfg(rodent_cfg, fill_missing=False)) == "off"  # what YAML 1.1 makes of a bare `off`
     for bad in ("on", "Linear", "cubic", True, 1, 0, "", None):
         with pytest.raises(ConfigError):
-            _cfg(rodent_cfg, fill_missing=bad)
+            hs.stage_cfg(rodent_cfg, fill_missing=bad)
 
 
 # ---- C ABI -------------------------------------------------------------------------------------------------------------------
@@ -60,7 +38,7 @@ def test_workspace_query(lib):
     from stac_mjx_amd import prep
 
     for T, K in ((0, 23), (-5, 23), (10, 0), (10, -1)):
-        _invalid(lib, lib.stac_prep_fill_workspace(T, K))
+        hs.invalid(lib, lib.stac_prep_fill_workspace(T, K))
     tile = prep.TILE_FRAMES
     for K in (1, 23, 70):
         last = 0
@@ -70,7 +48,7 @@ def test_workspace_query(lib):
             last = b
             assert prep.workspace_bytes(T, K) == b
             assert lib.stac_prep_fill_workspace(T, K + 1) > b  # monotone in K as well
-    _invalid(lib, lib.stac_prep_fill_workspace(2**62, 2**30))  # beyond int64
+    hs.invalid(lib, lib.stac_prep_fill_workspace(2**62, 2**30))  # beyond int64
     header = (ROOT / "stac_mjx_amd" / "csrc" / "stac_prep.hpp").read_text()
     assert f"kPrepTileFrames = {prep.TILE_FRAMES};" in header and f"kPrepMaxBlocks = {prep.MAX_BLOCKS};" in header
 
@@ -87,27 +65,27 @@ def test_fill_argument_errors_need_no_device(lib):
                                   p(ws) if ws else None, nbytes, None)
 
     for null in ("kp", "out", "gap", "ws"):
-        _invalid(lib, call(**{null: 0}))
-    _invalid(lib, call(T=0))
-    _invalid(lib, call(T=-3))
-    _invalid(lib, call(K=0))
-    _invalid(lib, call(K=-1))
+        hs.invalid(lib, call(**{null: 0}))
+    hs.invalid(lib, call(T=0))
+    hs.invalid(lib, call(T=-3))
+    hs.invalid(lib, call(K=0))
+    hs.invalid(lib, call(K=-1))
     for mode in (-1, 2, 7):
-        assert str(mode) in _invalid(lib, call(mode=mode))
-    assert str(need) in _invalid(lib, call(nbytes=need - 1))  # the message names the size it needs
-    _invalid(lib, call(nbytes=0))
-    _invalid(lib, call(ws=ws + 4))   # 8-byte alignment of the workspace
-    _invalid(lib, call(kp=kp + 2))   # 4-byte alignment of the arrays
+        assert str(mode) in hs.invalid(lib, call(mode=mode))
+    assert str(need) in hs.invalid(lib, call(nbytes=need - 1))  # the message names the size it needs
+    hs.invalid(lib, call(nbytes=0))
+    hs.invalid(lib, call(ws=ws + 4))   # 8-byte alignment of the workspace
+    hs.invalid(lib, call(kp=kp + 2))   # 4-byte alignment of the arrays
     # aliased buffers: the same array, a partial overlap at either end, the workspace inside an output
     kp_bytes, gap_bytes = T * K * 12, T * K * 4
-    assert "overlap" in _invalid(lib, call(out=kp))
-    _invalid(lib, call(out=kp + kp_bytes - 4))
-    _invalid(lib, call(kp=out + kp_bytes - 4))
-    _invalid(lib, call(gap=kp))
-    _invalid(lib, call(gap=out + 8))
-    _invalid(lib, call(ws=gap + gap_bytes - 8))
-    _invalid(lib, call(ws=kp + 8))
-    _invalid(lib, call(out=ws - kp_bytes + 8))
+    assert "overlap" in hs.invalid(lib, call(out=kp))
+    hs.invalid(lib, call(out=kp + kp_bytes - 4))
+    hs.invalid(lib, call(kp=out + kp_bytes - 4))
+    hs.invalid(lib, call(gap=kp))
+    hs.invalid(lib, call(gap=out + 8))
+    hs.invalid(lib, call(ws=gap + gap_bytes - 8))
+    hs.invalid(lib, call(ws=kp + 8))
+    hs.invalid(lib, call(out=ws - kp_bytes + 8))
 
 
 def test_python_wrapper_refuses_what_it_cannot_run():
@@ -213,16 +191,7 @@ int main(int argc, char **argv) {
 
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
-    cxx = next((c for c in (shutil.which("c++"), shutil.which("g++"), shutil.which("clang++")) if c), None)
-    assert cxx, "no host C++ compiler"
-    d = tmp_path_factory.mktemp("prep_host")
-    (d / "prep_cpu.cpp").write_text(_PROGRAM)
-    exe = d / "prep_cpu"
-    base = [cxx, "-O1", "-g", "-ffp-contract=off", "-std=c++17", f"-I{ROOT / 'stac_mjx_amd' / 'csrc'}", str(d / "prep_cpu.cpp"), "-o", str(exe)]
-    # with the address and undefined-behaviour sanitizers where the host compiler has their runtimes (a stand-alone CPU program)
-    if subprocess.run(base + ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"], capture_output=True, text=True).returncode != 0:
-        subprocess.run(base, check=True, capture_output=True, text=True)
-    return exe
+    return hs.build_cpu_program(tmp_path_factory, "prep", _PROGRAM, "-O1")
 
 
 @pytest.mark.parametrize("tile", [1, 2, 4, 7])
@@ -299,36 +268,20 @@ def _data(n, with_gap, seed=0):
     return d
 
 
-def _suffixes():
-    from stac_mjx_amd import io
-
-    return [".npz"] + ([".h5"] if io.h5py is not None else [])
-
-
-def _dataset_names(path):
-    from stac_mjx_amd import io
-
-    if path.suffix == ".npz":
-        with np.load(path) as f:
-            return set(f.files)
-    with io.h5py.File(path, "r") as f:
-        return set(f.keys())
-
-
 TODAY = {"config", "kp_names", "names_qpos", "names_xpos", "kp_data", "marker_sites", "offsets", "qpos", "qvel", "xpos", "xquat"}
 
 
 def test_kp_gap_round_trip(tmp_path, rodent_cfg):
     from stac_mjx_amd import io
 
-    cfg = _cfg(rodent_cfg)
+    cfg = hs.stage_cfg(rodent_cfg)
     assert "kp_gap" not in _data(4, False).as_dict() and set(_data(4, True).as_dict()) - set(_data(4, False).as_dict()) == {"kp_gap"}
-    for suffix in _suffixes():
+    for suffix in hs.result_suffixes():
         for with_gap in (False, True):
             d = _data(6, with_gap)
             path = io.save_data_to_h5(config=cfg, file_path=tmp_path / f"r{int(with_gap)}{suffix}", **d.as_dict())
             assert path.suffix == suffix
-            assert _dataset_names(path) == (TODAY | {"kp_gap"} if with_gap else TODAY)  # without the option: exactly today's datasets
+            assert hs.dataset_names(path) == (TODAY | {"kp_gap"} if with_gap else TODAY)  # without the option: exactly today's datasets
             _, back = io.load_stac_data(path)
             if with_gap:
                 assert back.kp_gap.dtype == np.int32
@@ -342,7 +295,7 @@ def test_kp_gap_round_trip(tmp_path, rodent_cfg):
 def test_kp_gap_shard_concatenation(tmp_path, rodent_cfg):
     from stac_mjx_amd import io
 
-    cfg = _cfg(rodent_cfg)
+    cfg = hs.stage_cfg(rodent_cfg)
     F, world = 2, 3
     for with_gap in (True, False):
         full = _data(5 * F, with_gap, seed=3)
@@ -377,7 +330,7 @@ def test_viz_stac_masks_filled_keypoints(tmp_path, rodent_cfg, monkeypatch):
             return ["frame"]
 
     monkeypatch.setattr(stac_mod, "Stac", FakeStac)
-    cfg = _cfg(rodent_cfg)
+    cfg = hs.stage_cfg(rodent_cfg)
     d = _data(6, True, seed=5)
     d.kp_gap = np.zeros((6, 3), np.int32)
     d.kp_gap[1:3, 0] = 2

@@ -5,64 +5,42 @@ on the CPU from csrc/stac_report.hpp with small tile sizes against the numpy ref
 import ctypes as C
 import json
 import math
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
 import report_cases as rc
+import host_scaffold as hs
 from conftest import ROOT
-
-STAC_ERR_INVALID = -1
 
 
 @pytest.fixture(scope="module")
 def lib():
-    from stac_mjx_amd.build import build_extension
-    from stac_mjx_amd.engine import load_library
-
-    build_extension()
-    return load_library()
-
-
-def _invalid(lib, rc_):
-    msg = lib.stac_last_error().decode()
-    assert rc_ == STAC_ERR_INVALID and lib.stac_last_error_code() == STAC_ERR_INVALID and msg, (rc_, msg)
-    return msg
+    return hs.loaded_library()
 
 
 # ---- config ------------------------------------------------------------------------------------------------------------------
-def _cfg(rodent_cfg, **over):
-    from stac_mjx_amd.config import validate_config
-
-    stac = dict(fit_offsets_path="fit.h5", ik_only_path="ik.h5", data_path="d.mat", continuous=False, n_fit_frames=4,
-                skip_fit_offsets=False, skip_ik_only=False, infer_qvels=False, n_frames_per_clip=2,
-                mujoco=dict(solver="newton", iterations=1, ls_iterations=4))
-    stac.update(over)
-    return validate_config({"model": dict(rodent_cfg), "stac": stac})
-
-
 def test_config_report_keys(rodent_cfg):
     from stac_mjx_amd.config import ConfigError
     from stac_mjx_amd.main import _report_mode
 
-    plain = _cfg(rodent_cfg)
+    plain = hs.stage_cfg(rodent_cfg)
     assert _report_mode(plain) == (False, (500, 900, 990), 10)
     assert "report" not in plain.to_yaml()  # absent stays absent (the three keys all hold the word)
     for value, on in (("off", False), ("on", True), (False, False), (True, True)):  # the bools: what YAML 1.1 makes of a bare off / on
-        assert _report_mode(_cfg(rodent_cfg, report=value))[0] is on
-    assert _report_mode(_cfg(rodent_cfg, report="on", report_quantiles=[0, 1000], report_worst=0)) == (True, (0, 1000), 0)
-    assert _report_mode(_cfg(rodent_cfg, report_quantiles=list(range(8))))[1] == tuple(range(8))
+        assert _report_mode(hs.stage_cfg(rodent_cfg, report=value))[0] is on
+    assert _report_mode(hs.stage_cfg(rodent_cfg, report="on", report_quantiles=[0, 1000], report_worst=0)) == (True, (0, 1000), 0)
+    assert _report_mode(hs.stage_cfg(rodent_cfg, report_quantiles=list(range(8))))[1] == tuple(range(8))
     for bad in ("yes", "On", 1, 0, "", 2.0, ["on"]):
         with pytest.raises(ConfigError):
-            _cfg(rodent_cfg, report=bad)
+            hs.stage_cfg(rodent_cfg, report=bad)
     for bad in ([], list(range(9)), [500.0], [-1], [1001], [True], "500", 500, None, [[500]]):
         with pytest.raises(ConfigError):
-            _cfg(rodent_cfg, report_quantiles=bad)
+            hs.stage_cfg(rodent_cfg, report_quantiles=bad)
     for bad in (-1, 1.5, "3", True, None, [3]):
         with pytest.raises(ConfigError):
-            _cfg(rodent_cfg, report_worst=bad)
+            hs.stage_cfg(rodent_cfg, report_worst=bad)
 
 
 # ---- C ABI -------------------------------------------------------------------------------------------------------------------
@@ -70,7 +48,7 @@ def test_workspace_query(lib):
     from stac_mjx_amd import report
 
     for N, K, Q in ((0, 23, 3), (-5, 23, 3), (10, 0, 3), (10, -1, 3), (10, 23, 0), (10, 23, 9), (10, 23, -1)):
-        _invalid(lib, lib.stac_report_workspace(N, K, Q))
+        hs.invalid(lib, lib.stac_report_workspace(N, K, Q))
     tile = report.TILE_FRAMES
     for K in (1, 23, 70):
         for Q in (1, 3, 8):
@@ -84,7 +62,7 @@ def test_workspace_query(lib):
                 if Q < report.MAX_QUANT:
                     assert lib.stac_report_workspace(N, K, Q + 1) > b  # and in Q
             assert lib.stac_report_workspace(tile + 1, K, Q) > lib.stac_report_workspace(tile, K, Q)
-    _invalid(lib, lib.stac_report_workspace(2**62, 2**30, 3))  # beyond int64
+    hs.invalid(lib, lib.stac_report_workspace(2**62, 2**30, 3))  # beyond int64
     header = (ROOT / "stac_mjx_amd" / "csrc" / "stac_report.hpp").read_text()
     for name, value in (("kReportTileFrames", report.TILE_FRAMES), ("kReportMaxBlocks", report.MAX_BLOCKS), ("kReportSegFrames", report.SEG_FRAMES),
                         ("kReportMaxQuant", report.MAX_QUANT), ("kReportBins0", report.HIST_BINS)):
@@ -115,32 +93,32 @@ def test_report_argument_errors_need_no_device(lib):
                           **{k: (v or None) for k, v in a.items()})
         return lib.stac_report_errors(C.byref(p))
 
-    assert "stac_report_errors" in _invalid(lib, lib.stac_report_errors(None))
+    assert "stac_report_errors" in hs.invalid(lib, lib.stac_report_errors(None))
     for null in NAMES:
         if null != "gap":
-            assert "stac_report_errors" in _invalid(lib, call(**{null: 0}))
-    _invalid(lib, call(null_permille=True))
+            assert "stac_report_errors" in hs.invalid(lib, call(**{null: 0}))
+    hs.invalid(lib, call(null_permille=True))
     for kw in (dict(N=0), dict(N=-3), dict(K=0), dict(K=-1), dict(Q=0), dict(Q=9), dict(Q=-1)):
-        assert "stac_report_errors" in _invalid(lib, call(**kw))
+        assert "stac_report_errors" in hs.invalid(lib, call(**kw))
     for bad in ((500, 900, 1001), (-1, 900, 990), (500, 2**20, 990)):
-        assert "permille" in _invalid(lib, call(permille=bad))
-    assert str(need) in _invalid(lib, call(nbytes=need - 1))  # the message names the size it needs
-    _invalid(lib, call(nbytes=0))
-    _invalid(lib, call(workspace=base["workspace"] + 4))  # 8-byte alignment of the workspace
+        assert "permille" in hs.invalid(lib, call(permille=bad))
+    assert str(need) in hs.invalid(lib, call(nbytes=need - 1))  # the message names the size it needs
+    hs.invalid(lib, call(nbytes=0))
+    hs.invalid(lib, call(workspace=base["workspace"] + 4))  # 8-byte alignment of the workspace
     for name in ("markers", "kp", "gap", "sqerr", "frame_n", "max", "quant"):
-        assert name in _invalid(lib, call(**{name: base[name] + 2}))  # 4-byte alignment of the arrays
+        assert name in hs.invalid(lib, call(**{name: base[name] + 2}))  # 4-byte alignment of the arrays
     for name in ("frame_sse", "count", "sum", "argmax", "hist"):
-        assert name in _invalid(lib, call(**{name: base[name] + 4}))  # 8-byte alignment of the 64-bit outputs
+        assert name in hs.invalid(lib, call(**{name: base[name] + 4}))  # 8-byte alignment of the 64-bit outputs
     # any two buffers that overlap: the same array, a partial overlap at either end
     for a in NAMES:
         for b in NAMES:
             if a == b:
                 continue
-            msg = _invalid(lib, call(**{a: base[b]}))
+            msg = hs.invalid(lib, call(**{a: base[b]}))
             assert "overlap" in msg and a in msg and b in msg, (a, b, msg)
-            _invalid(lib, call(**{a: base[b] + size[b] - 8}))
+            hs.invalid(lib, call(**{a: base[b] + size[b] - 8}))
             if size[a] > 8:
-                _invalid(lib, call(**{a: base[b] - size[a] + 8}))
+                hs.invalid(lib, call(**{a: base[b] - size[a] + 8}))
 
 
 def test_python_wrapper_refuses_what_it_cannot_run():
@@ -339,16 +317,7 @@ int main(int argc, char **argv) {
 
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
-    cxx = next((c for c in (shutil.which("c++"), shutil.which("g++"), shutil.which("clang++")) if c), None)
-    assert cxx, "no host C++ compiler"
-    d = tmp_path_factory.mktemp("report_host")
-    (d / "report_cpu.cpp").write_text(_PROGRAM)
-    exe = d / "report_cpu"
-    base = [cxx, "-O1", "-g", "-ffp-contract=off", "-std=c++17", f"-I{ROOT / 'stac_mjx_amd' / 'csrc'}", str(d / "report_cpu.cpp"), "-o", str(exe)]
-    # with the address and undefined-behaviour sanitizers where the host compiler has their runtimes (a stand-alone CPU program)
-    if subprocess.run(base + ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"], capture_output=True, text=True).returncode != 0:
-        subprocess.run(base, check=True, capture_output=True, text=True)
-    return exe
+    return hs.build_cpu_program(tmp_path_factory, "report", _PROGRAM, "-O1")
 
 
 def _read_outputs(raw, pos, N, K, Q):

@@ -1,31 +1,24 @@
 """stac.resample, the parts that need no GPU: the tap table against ``scipy.signal.resample_poly``, the normalised rows, the index
-rules with Python integers (beyond int32 too), every refusal of the options, the pre-flight and the Python functions, the fifth
-prototype table against the fifth header, the argument checks of the entry point (they happen before the device is touched), and a
+rules with Python integers (beyond int32 too), every refusal of the options, the pre-flight and the Python functions,
+the argument checks of the entry point (they happen before the device is touched), and a
 CPU build of csrc/stac_resample.hpp against the numpy restatement of tests/resample_cases.py, bit for bit."""
 
 import ctypes as C
-import re
-import shutil
-import subprocess
+import functools
 
 import numpy as np
 import pytest
 
 import resample_cases as rc
-from conftest import ROOT
+import host_scaffold as hs
+from host_scaffold import STAC_ERR_INVALID
 
-STAC_ERR_INVALID = -1
-HEADER = ROOT / "include" / "stac_hip_resample.h"
 BIG = 2**31 + 5
 
 
 @pytest.fixture(scope="module")
 def lib():
-    from stac_mjx_amd.build import build_extension
-    from stac_mjx_amd.engine import load_library
-
-    build_extension()
-    return load_library()
+    return hs.loaded_library()
 
 
 # ---- the table -----------------------------------------------------------------------------------------------------------------------
@@ -116,14 +109,7 @@ extern "C" int32_t host_constant(int32_t i) {
 
 @pytest.fixture(scope="module")
 def hostlib(tmp_path_factory):
-    cxx = next((c for c in (shutil.which("c++"), shutil.which("g++"), shutil.which("clang++")) if c), None)
-    assert cxx, "no host C++ compiler"
-    d = tmp_path_factory.mktemp("resample_host")
-    (d / "driver.cpp").write_text(_DRIVER)
-    so = d / "libresample_host.so"
-    subprocess.run([cxx, "-O2", "-ffp-contract=off", "-std=c++17", "-shared", "-fPIC", f"-I{ROOT / 'stac_mjx_amd' / 'csrc'}",
-                    str(d / "driver.cpp"), "-o", str(so)], check=True, capture_output=True, text=True)
-    h = C.CDLL(str(so))
+    h = hs.build_cpu_library(tmp_path_factory, "resample", _DRIVER)
     fp, ip, i32, i64 = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.c_int32, C.c_int64
     for name, res, args in (("host_resample", None, [fp, i64, i32, i64, i32, i32, i32, fp, ip, i32, fp, fp, fp]), ("host_rows", i64, [i64, i32, i32]),
                             ("host_n", i64, [i64, i32, i32]), ("host_r", i32, [i64, i32, i32]), ("host_source_row", i64, [i64, i64, i32, i32]),
@@ -182,14 +168,7 @@ def test_tile_rule_of_header_and_python_agree(hostlib):
 
 
 # ---- options, pre-flight, Python arguments -----------------------------------------------------------------------------------------
-def _cfg(rodent_cfg, **stac_over):
-    from stac_mjx_amd.config import validate_config
-
-    stac = dict(fit_offsets_path="fit.h5", ik_only_path="ik.h5", data_path="d.mat", continuous=False, n_fit_frames=4,
-                skip_fit_offsets=False, skip_ik_only=False, infer_qvels=False, n_frames_per_clip=12,
-                mujoco=dict(solver="newton", iterations=1, ls_iterations=4))
-    stac.update(stac_over)
-    return validate_config({"model": dict(rodent_cfg), "stac": stac})
+_cfg = functools.partial(hs.stage_cfg, n_frames_per_clip=12)
 
 
 def test_resample_options_and_their_refusals(rodent_cfg):
@@ -282,62 +261,6 @@ def test_python_functions_refuse_bad_arguments():
 
 
 # ---- C ABI -------------------------------------------------------------------------------------------------------------------------
-def _c_class(ctype):
-    if "*" in ctype:
-        return "pointer"
-    base = ctype.replace("const", " ").split()
-    assert len(base) == 1 and base[0] in ("int32_t", "int64_t", "float", "double", "void"), ctype
-    return base[0]
-
-
-def _ctypes_class(t):
-    if t is None:
-        return "void"
-    if t in (C.c_void_p, C.c_char_p) or issubclass(t, C._Pointer):
-        return "pointer"
-    return {C.c_int32: "int32_t", C.c_int64: "int64_t", C.c_float: "float", C.c_double: "double"}[t]
-
-
-def _header_prototypes():
-    """Every ``ret stac_name(args);`` of include/stac_hip_resample.h -> name: (class of ret, [(class, name) of every argument])"""
-    text = re.sub(r"/\*.*?\*/", " ", HEADER.read_text(), flags=re.S)
-    text = "\n".join(ln for ln in text.splitlines() if not ln.lstrip().startswith("#"))
-    text = text.replace('extern "C" {', " ")
-    protos = {}
-    for stmt in text.split(";"):
-        stmt = " ".join(stmt.split())
-        if stmt in ("", "}"):
-            continue
-        m = re.fullmatch(r"(.*?)\b(stac_[a-z0-9_]+) ?\((.*)\)", stmt)
-        assert m, f"not a prototype: {stmt!r}"  # nothing of the header is passed over in silence
-        ret, name, args = m.groups()
-        protos[name] = (_c_class(ret), [(_c_class(re.sub(r"\w+$", "", a.strip())), re.search(r"\w+$", a.strip()).group()) for a in args.split(",")])
-    return protos
-
-
-def test_fifth_abi_table_against_the_fifth_header(lib):
-    from stac_mjx_amd import abi, build
-
-    protos = _header_prototypes()
-    assert list(protos) == ["stac_post_resample_rows", "stac_post_resample"] and set(protos) == set(abi.RESAMPLE_PROTOTYPES)
-    for name, (ret, args) in protos.items():
-        restype, argtypes = abi.RESAMPLE_PROTOTYPES[name]
-        assert [_ctypes_class(t) for t in argtypes] == [a[0] for a in args] and _ctypes_class(restype) == ret, name
-        fn = getattr(lib, name)  # the library carries them, declared by abi.declare
-        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
-    assert [a[1] for a in protos["stac_post_resample"][1]] == ["x", "n_rows", "n_cols", "clip_len", "up", "down", "half", "taps_dev", "quat_cols",
-                                                               "n_quat", "lb", "ub", "out", "out_rows", "stream"]
-    # the five tables are disjoint; the other headers, their tables and the version are what they were
-    tables = (abi.PROTOTYPES, abi.PAIRWISE_PROTOTYPES, abi.SWAPS_PROTOTYPES, abi.DONOR_PROTOTYPES, abi.RESAMPLE_PROTOTYPES)
-    assert len(set().union(*tables)) == sum(len(t) for t in tables)
-    assert len(abi.PROTOTYPES) == 31 and abi.ABI_SYMBOLS == tuple(abi.PROTOTYPES) and lib.stac_abi_version() == 3
-    for other in ("stac_hip.h", "stac_hip_pairwise.h", "stac_hip_swaps.h", "stac_hip_donor.h"):
-        assert "resample" not in (ROOT / "include" / other).read_text() and ROOT / "include" / other in build.HEADERS
-    csrc = ROOT / "stac_mjx_amd" / "csrc"
-    assert HEADER in build.HEADERS and csrc / "stac_resample.hpp" in build.HEADERS and csrc / "stac_resample.hip" in build.SOURCES
-    assert "do not count into\n * STAC_HIP_ABI_VERSION" in HEADER.read_text()
-
-
 def test_entry_point_refuses_bad_arguments_before_the_device(lib):
     """Made-up addresses: nothing may be read through them, every refusal comes from the arguments alone."""
     A = 1 << 20
@@ -391,16 +314,12 @@ def test_entry_point_refuses_bad_arguments_before_the_device(lib):
 
 
 # ---- the header against numpy --------------------------------------------------------------------------------------------------------
-def _fp(a):
-    return a.ctypes.data_as(C.POINTER(C.c_float)) if a is not None else None
-
-
 def cpu_resample(h, x, L, U, D, taps, cols, lb=None, ub=None):
     W = taps.shape[1]
     out = np.full(((x.shape[0] // L) * rc.rows(L, U, D), x.shape[1]), -12345.0, np.float32)
     qc = np.ascontiguousarray(cols, dtype=np.int32)
-    h.host_resample(_fp(x), x.shape[0], x.shape[1], L, U, D, (W // 2 - 1) * U, _fp(taps), qc.ctypes.data_as(C.POINTER(C.c_int32)), len(cols),
-                    _fp(lb), _fp(ub), _fp(out))
+    h.host_resample(hs.fp(x), x.shape[0], x.shape[1], L, U, D, (W // 2 - 1) * U, hs.fp(taps), qc.ctypes.data_as(C.POINTER(C.c_int32)), len(cols),
+                    hs.fp(lb), hs.fp(ub), hs.fp(out))
     return out
 
 

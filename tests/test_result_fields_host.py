@@ -5,14 +5,7 @@ import dataclasses
 
 import numpy as np
 
-
-def _cfg(rodent_cfg):
-    from stac_mjx_amd.config import validate_config
-
-    stac = dict(fit_offsets_path="fit.h5", ik_only_path="ik.h5", data_path="d.mat", continuous=False, n_fit_frames=4,
-                skip_fit_offsets=False, skip_ik_only=False, infer_qvels=False, n_frames_per_clip=2,
-                mujoco=dict(solver="newton", iterations=1, ls_iterations=4))
-    return validate_config({"model": dict(rodent_cfg), "stac": stac})
+import host_scaffold as hs
 
 
 def _result(rng, T=4, K=3, nq=5, nb=2):
@@ -50,7 +43,7 @@ def test_table_against_dataclass():
 def test_all_fields_through_shards(tmp_path, rodent_cfg):
     from stac_mjx_amd import io
 
-    cfg, whole = _cfg(rodent_cfg), _result(np.random.default_rng(1))
+    cfg, whole = hs.stage_cfg(rodent_cfg), _result(np.random.default_rng(1))
     names = [name for name, _ in io.OPTIONAL_FIELDS]
     per_frame = [f.name for f in dataclasses.fields(io.StacData) if f.name not in ("offsets", "names_qpos", "names_xpos", "kp_names")]
     assert set(names) < set(per_frame)

@@ -4,45 +4,32 @@ build of the kernel's arithmetic (csrc/stac_smooth.hpp) against the restatement 
 entry point (they happen before the device is touched) and the ``qpos_raw`` field of the result files."""
 
 import ctypes as C
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import smooth_cases as sc
-from conftest import ROOT
+import host_scaffold as hs
 
-STAC_ERR_INVALID = -1
 SAVGOL_CASES = [(1, 0), (1, 2), (2, 2), (3, 2), (3, 3), (5, 3), (16, 2), (16, 4)]
 
 
 # ---- configuration ------------------------------------------------------------------------------------------------------------
-def _cfg(rodent_cfg, **over):
-    from stac_mjx_amd.config import validate_config
-
-    stac = dict(fit_offsets_path="fit.h5", ik_only_path="ik.h5", data_path="d.mat", continuous=False, n_fit_frames=4,
-                skip_fit_offsets=False, skip_ik_only=False, infer_qvels=False, n_frames_per_clip=2,
-                mujoco=dict(solver="newton", iterations=1, ls_iterations=4))
-    stac.update(over)
-    return validate_config({"model": dict(rodent_cfg), "stac": stac})
-
-
 def test_config_smooth_keys(rodent_cfg):
     from stac_mjx_amd.config import ConfigError, smooth_options
     from stac_mjx_amd.main import _smooth_mode
 
-    assert smooth_options(_cfg(rodent_cfg).stac) == {"kind": "off", "half_window": 3, "order": None, "sigma": None}
-    assert _smooth_mode(_cfg(rodent_cfg)) is None
-    cfg = _cfg(rodent_cfg, smooth=False)  # a bare `off` in YAML 1.1 is the boolean
+    assert smooth_options(hs.stage_cfg(rodent_cfg).stac) == {"kind": "off", "half_window": 3, "order": None, "sigma": None}
+    assert _smooth_mode(hs.stage_cfg(rodent_cfg)) is None
+    cfg = hs.stage_cfg(rodent_cfg, smooth=False)  # a bare `off` in YAML 1.1 is the boolean
     assert cfg.stac.smooth == "off" and _smooth_mode(cfg) is None
-    assert _smooth_mode(_cfg(rodent_cfg, smooth="off", postprocess="host", reference_marker_order=True)) is None  # off asks for nothing
-    assert _smooth_mode(_cfg(rodent_cfg, smooth="savgol", postprocess="gpu")) == {"kind": "savgol", "half_window": 3, "order": 2, "sigma": None}
-    assert _smooth_mode(_cfg(rodent_cfg, smooth="gaussian", postprocess="gpu", smooth_window=4)) == \
+    assert _smooth_mode(hs.stage_cfg(rodent_cfg, smooth="off", postprocess="host", reference_marker_order=True)) is None  # off asks for nothing
+    assert _smooth_mode(hs.stage_cfg(rodent_cfg, smooth="savgol", postprocess="gpu")) == {"kind": "savgol", "half_window": 3, "order": 2, "sigma": None}
+    assert _smooth_mode(hs.stage_cfg(rodent_cfg, smooth="gaussian", postprocess="gpu", smooth_window=4)) == \
         {"kind": "gaussian", "half_window": 4, "order": None, "sigma": 2.0}
-    assert _smooth_mode(_cfg(rodent_cfg, smooth="gaussian", postprocess="gpu", smooth_sigma=1))["sigma"] == 1.0
-    assert _smooth_mode(_cfg(rodent_cfg, smooth="savgol", postprocess="gpu", smooth_window=16, smooth_order=32))["order"] == 32
-    assert _smooth_mode(_cfg(rodent_cfg, smooth="savgol", postprocess="gpu", smooth_window=1, smooth_order=0))["order"] == 0
+    assert _smooth_mode(hs.stage_cfg(rodent_cfg, smooth="gaussian", postprocess="gpu", smooth_sigma=1))["sigma"] == 1.0
+    assert _smooth_mode(hs.stage_cfg(rodent_cfg, smooth="savgol", postprocess="gpu", smooth_window=16, smooth_order=32))["order"] == 32
+    assert _smooth_mode(hs.stage_cfg(rodent_cfg, smooth="savgol", postprocess="gpu", smooth_window=1, smooth_order=0))["order"] == 0
     for bad in (dict(smooth="on"), dict(smooth=True), dict(smooth="SAVGOL"), dict(smooth=1),
                 dict(smooth_window=0), dict(smooth_window=17), dict(smooth_window=3.0), dict(smooth_window=True),
                 dict(smooth_order=-1), dict(smooth_order=1.0), dict(smooth_order=True),
@@ -50,15 +37,15 @@ def test_config_smooth_keys(rodent_cfg):
                 dict(smooth_sigma=0), dict(smooth_sigma=-1.0), dict(smooth_sigma=float("inf")), dict(smooth_sigma=float("nan")),
                 dict(smooth_sigma="1"), dict(smooth_sigma=True)):
         with pytest.raises(ConfigError):
-            _cfg(rodent_cfg, **bad)
+            hs.stage_cfg(rodent_cfg, **bad)
     # the two refused combinations, before any work is done (ValueError, like hampel without fill_missing)
     for kind in ("savgol", "gaussian"):
         with pytest.raises(ValueError, match="postprocess"):
-            _cfg(rodent_cfg, smooth=kind)
+            hs.stage_cfg(rodent_cfg, smooth=kind)
         with pytest.raises(ValueError, match="postprocess"):
-            _cfg(rodent_cfg, smooth=kind, postprocess="host")
+            hs.stage_cfg(rodent_cfg, smooth=kind, postprocess="host")
         with pytest.raises(ValueError, match="reference_marker_order"):
-            _cfg(rodent_cfg, smooth=kind, postprocess="gpu", reference_marker_order=True)
+            hs.stage_cfg(rodent_cfg, smooth=kind, postprocess="gpu", reference_marker_order=True)
 
 
 def test_config_yaml_boolean_and_overrides(reference_dir):
@@ -78,11 +65,11 @@ def test_run_stac_refuses_clips_shorter_than_the_window_before_any_work(rodent_c
 
     kp = np.zeros((24, 69), np.float32)
     names = list(rodent_cfg["KEYPOINT_MODEL_PAIRS"].keys())
-    cfg = _cfg(rodent_cfg, smooth="savgol", postprocess="gpu", smooth_window=3, n_frames_per_clip=6)
+    cfg = hs.stage_cfg(rodent_cfg, smooth="savgol", postprocess="gpu", smooth_window=3, n_frames_per_clip=6)
     with pytest.raises(ValueError, match=r"(?s)7.*6|6.*7"):  # names the window and the clip
         run_stac(cfg, kp, names, base_path=tmp_path)
     # continuous: the clip is the stitched run (24 rows of 2 windows of 12 + 10), shorter than a window of 33
-    cfg = _cfg(rodent_cfg, smooth="gaussian", postprocess="gpu", smooth_window=16, n_frames_per_clip=12, continuous=True)
+    cfg = hs.stage_cfg(rodent_cfg, smooth="gaussian", postprocess="gpu", smooth_window=16, n_frames_per_clip=12, continuous=True)
     with pytest.raises(ValueError, match=r"(?s)33.*24|24.*33"):
         run_stac(cfg, kp, names, base_path=tmp_path)
     assert not list(tmp_path.iterdir())
@@ -285,14 +272,7 @@ extern "C" int32_t host_max_quat() { return kSmoothMaxQuat; }
 
 @pytest.fixture(scope="module")
 def hostlib(tmp_path_factory):
-    cxx = next((c for c in (shutil.which("c++"), shutil.which("g++"), shutil.which("clang++")) if c), None)
-    assert cxx, "no host C++ compiler"
-    d = tmp_path_factory.mktemp("smooth_host")
-    (d / "driver.cpp").write_text(_DRIVER)
-    so = d / "libsmooth_host.so"
-    subprocess.run([cxx, "-O2", "-ffp-contract=off", "-std=c++17", "-shared", "-fPIC", f"-I{ROOT / 'stac_mjx_amd' / 'csrc'}",
-                    str(d / "driver.cpp"), "-o", str(so)], check=True, capture_output=True, text=True)
-    h = C.CDLL(str(so))
+    h = hs.build_cpu_library(tmp_path_factory, "smooth", _DRIVER)
     fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
     h.host_smooth.argtypes = [fp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, fp, ip, C.c_int32, fp, fp, fp]
     h.host_smooth.restype = None
@@ -302,15 +282,11 @@ def hostlib(tmp_path_factory):
     return h
 
 
-def _fp(a):
-    return a.ctypes.data_as(C.POINTER(C.c_float)) if a is not None else None
-
-
 def _cpu_smooth(h, x, L, taps, cols, lb=None, ub=None):
     out = np.full_like(x, -12345.0)
     qc = np.ascontiguousarray(cols, dtype=np.int32)
-    h.host_smooth(_fp(x), x.shape[0], x.shape[1], L, taps.shape[0] // 2, _fp(taps), qc.ctypes.data_as(C.POINTER(C.c_int32)), len(cols),
-                  _fp(lb), _fp(ub), _fp(out))
+    h.host_smooth(hs.fp(x), x.shape[0], x.shape[1], L, taps.shape[0] // 2, hs.fp(taps), qc.ctypes.data_as(C.POINTER(C.c_int32)), len(cols),
+                  hs.fp(lb), hs.fp(ub), hs.fp(out))
     return out
 
 
@@ -354,17 +330,7 @@ def test_cpu_build_equals_restatement(hostlib, name, H):
 # ---- the entry point's argument checks (before the device is touched) -------------------------------------------------------------
 @pytest.fixture(scope="module")
 def lib():
-    from stac_mjx_amd.build import build_extension
-    from stac_mjx_amd.engine import load_library
-
-    build_extension()
-    return load_library()
-
-
-def _invalid(lib, rc):
-    msg = lib.stac_last_error().decode()
-    assert rc == STAC_ERR_INVALID and lib.stac_last_error_code() == STAC_ERR_INVALID and msg, (rc, msg)
-    return msg
+    return hs.loaded_library()
 
 
 def test_smooth_argument_errors_need_no_device(lib):
@@ -377,30 +343,30 @@ def test_smooth_argument_errors_need_no_device(lib):
         qc = (C.c_int32 * max(len(cols), 1))(*cols) if cols is not None else None
         return lib.stac_post_smooth(q, N, nq, L, H, taps, qc, len(cols) if cols is not None else 1, lb, ub, out, None)
 
-    _invalid(lib, call(H=0))
-    assert "17" in _invalid(lib, call(H=17, L=40))
-    msg = _invalid(lib, call(L=5, N=40))  # clip_len < W: names both numbers
+    hs.invalid(lib, call(H=0))
+    assert "17" in hs.invalid(lib, call(H=17, L=40))
+    msg = hs.invalid(lib, call(L=5, N=40))  # clip_len < W: names both numbers
     assert "5" in msg and "7" in msg
-    assert "41" in _invalid(lib, call(N=41))  # N % clip_len != 0
-    _invalid(lib, call(N=-10))
-    _invalid(lib, call(nq=0, cols=()))
-    assert "overlap" in _invalid(lib, call(cols=(3, 6)))
-    assert "overlap" in _invalid(lib, call(cols=(9, 3, 9)))
-    assert "leaves" in _invalid(lib, call(cols=(3, 10)))  # 10 + 4 > 13
-    _invalid(lib, call(cols=(-1,)))
-    assert "64" in _invalid(lib, call(nq=400, cols=tuple(range(0, 260, 4))))  # 65 blocks
+    assert "41" in hs.invalid(lib, call(N=41))  # N % clip_len != 0
+    hs.invalid(lib, call(N=-10))
+    hs.invalid(lib, call(nq=0, cols=()))
+    assert "overlap" in hs.invalid(lib, call(cols=(3, 6)))
+    assert "overlap" in hs.invalid(lib, call(cols=(9, 3, 9)))
+    assert "leaves" in hs.invalid(lib, call(cols=(3, 10)))  # 10 + 4 > 13
+    hs.invalid(lib, call(cols=(-1,)))
+    assert "64" in hs.invalid(lib, call(nq=400, cols=tuple(range(0, 260, 4))))  # 65 blocks
     assert call(N=0, nq=400, cols=tuple(range(0, 256, 4)), q=None, out=None) == 0  # 64 are fine (and N == 0: nothing to do)
-    _invalid(lib, call(cols=None))
-    _invalid(lib, call(nq=450, H=16, L=40))  # no room for a window in LDS
-    _invalid(lib, call(taps=None))
-    _invalid(lib, call(lb=None))
-    _invalid(lib, call(ub=None))
-    _invalid(lib, call(q=None))
-    _invalid(lib, call(out=None))
-    _invalid(lib, call(q=C.c_void_p(0x100002)))
-    assert "overlap" in _invalid(lib, call(out=q))  # in place
-    assert "overlap" in _invalid(lib, call(out=C.c_void_p(0x100000 + 40 * 13 * 4 - 4)))
-    assert "overlap" in _invalid(lib, call(lb=C.c_void_p(0x900000 + 64)))
+    hs.invalid(lib, call(cols=None))
+    hs.invalid(lib, call(nq=450, H=16, L=40))  # no room for a window in LDS
+    hs.invalid(lib, call(taps=None))
+    hs.invalid(lib, call(lb=None))
+    hs.invalid(lib, call(ub=None))
+    hs.invalid(lib, call(q=None))
+    hs.invalid(lib, call(out=None))
+    hs.invalid(lib, call(q=C.c_void_p(0x100002)))
+    assert "overlap" in hs.invalid(lib, call(out=q))  # in place
+    assert "overlap" in hs.invalid(lib, call(out=C.c_void_p(0x100000 + 40 * 13 * 4 - 4)))
+    assert "overlap" in hs.invalid(lib, call(lb=C.c_void_p(0x900000 + 64)))
     assert call(N=0, q=None, out=None) == 0 and call(N=0, lb=None, ub=None, cols=(), q=None, out=None) == 0
 
 
@@ -417,14 +383,8 @@ def test_python_wrapper_refuses_before_the_library(lib):
 
 
 # ---- qpos_raw in the result files -------------------------------------------------------------------------------------------------
-def _suffixes():
-    from stac_mjx_amd import io
-
-    return [".npz"] + ([".h5"] if io.h5py is not None else [])  # (.h5 where h5py is installed; else the writer's .npz stand-in alone)
-
-
 def test_qpos_raw_round_trip(tmp_path, rodent_cfg):
-    for suffix in _suffixes():
+    for suffix in hs.result_suffixes():
         _qpos_raw_round_trip(tmp_path, rodent_cfg, suffix)
 
 
@@ -437,7 +397,7 @@ def _qpos_raw_round_trip(tmp_path, rodent_cfg, suffix):
                        offsets=rng.random((23, 3), dtype=np.float32), kp_data=rng.random((6, 69), dtype=np.float32),
                        names_qpos=[f"q{i}" for i in range(74)], names_xpos=[f"b{i}" for i in range(67)], kp_names=[f"k{i}" for i in range(23)])
     assert data.qpos_raw.size == 0 and "qpos_raw" not in data.as_dict()
-    cfg = _cfg(rodent_cfg)
+    cfg = hs.stage_cfg(rodent_cfg)
     plain = io.save_data_to_h5(config=cfg, file_path=tmp_path / f"plain{suffix}", **data.as_dict())
     back = io.load_stac_data(plain)[1]
     assert back.qpos_raw.size == 0 and "qpos_raw" not in back.as_dict()  # a file without it loads with the empty array
@@ -461,7 +421,7 @@ def test_qpos_raw_in_sharded_results(tmp_path, rodent_cfg):
     from stac_mjx_amd import io
 
     rng = np.random.default_rng(1)
-    cfg = _cfg(rodent_cfg)
+    cfg = hs.stage_cfg(rodent_cfg)
     raws = []
     for r in range(2):
         d = io.StacData(qpos=rng.random((4, 74), dtype=np.float32), xpos=rng.random((4, 67, 3), dtype=np.float32),

@@ -1,13 +1,11 @@
 """repair_swaps, the parts that need no GPU: the numpy reference of tests/swaps_cases.py against its vectorised statement and against
 the rule of csrc/stac_swap.hpp as a stand-alone CPU program (once more under the address and undefined-behaviour sanitizers), what the
 reference does with the 40-frame left / right swaps in the golden recording, the config keys and ``config.lr_pairs``, the pre-flight
-refusals of ``run_stac``, the third ABI table against the third header, the argument checks of ``stac_prep_swaps`` (they happen
+refusals of ``run_stac``, the argument checks of ``stac_prep_swaps`` (they happen
 before the device is touched) and ``kp_swapped`` through the result files."""
 
 import ctypes as C
 import json
-import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -15,10 +13,9 @@ import pytest
 
 import pairwise_cases as pc
 import swaps_cases as sc
+import host_scaffold as hs
 from conftest import GOLDEN, ROOT
-
-STAC_ERR_INVALID, STAC_ERR_CAPACITY = -1, -3
-HEADER = ROOT / "include" / "stac_hip_swaps.h"
+from host_scaffold import STAC_ERR_INVALID, STAC_ERR_CAPACITY
 
 
 # ---- the reference ------------------------------------------------------------------------------------------------------------------
@@ -222,8 +219,7 @@ int main(int argc, char **argv) {
 
 
 def _compile(tmp_path_factory, tag, extra):
-    cxx = next((c for c in (shutil.which("c++"), shutil.which("g++"), shutil.which("clang++")) if c), None)
-    assert cxx, "no host C++ compiler"
+    cxx = hs.host_cxx()
     d = tmp_path_factory.mktemp(tag)
     (d / "swaps_cpu.cpp").write_text(_PROGRAM)
     exe = d / "swaps_cpu"
@@ -337,32 +333,22 @@ def test_the_96_frames_of_the_end_to_end_run(rodent_mocap, rodent_cfg):
 
 
 # ---- config -----------------------------------------------------------------------------------------------------------------------
-def _cfg(rodent_cfg, **over):
-    from stac_mjx_amd.config import validate_config
-
-    stac = dict(fit_offsets_path="fit.h5", ik_only_path="ik.h5", data_path="d.mat", continuous=False, n_fit_frames=4,
-                skip_fit_offsets=False, skip_ik_only=False, infer_qvels=False, n_frames_per_clip=2,
-                mujoco=dict(solver="newton", iterations=1, ls_iterations=4))
-    stac.update(over)
-    return validate_config({"model": dict(rodent_cfg), "stac": stac})
-
-
 def test_config_repair_swaps_keys(rodent_cfg):
     from stac_mjx_amd.config import SWAPS_DEFAULTS, swaps_options
     from stac_mjx_amd.main import _reject_outliers_mode, _reject_pairwise_mode, _repair_swaps_mode
 
     names = list(rodent_cfg["KEYPOINT_MODEL_PAIRS"].keys())
-    plain = _cfg(rodent_cfg)
+    plain = hs.stage_cfg(rodent_cfg)
     assert SWAPS_DEFAULTS == {"swaps_nsigma": 6.0, "swaps_min_dev": 0.002, "swaps_min_bad": 3}
     assert swaps_options(plain.stac) == ("off", 6.0, 0.002, 3) and "swaps" not in plain.to_yaml()  # absent stays absent
     assert _repair_swaps_mode(plain, names) == ([], {"n_sigma": 6.0, "min_dev": 0.002, "min_bad": 3})
-    assert swaps_options(_cfg(rodent_cfg, repair_swaps="off").stac)[0] == "off"
-    off = _cfg(rodent_cfg, repair_swaps=False)  # what YAML 1.1 makes of a bare `off`
+    assert swaps_options(hs.stage_cfg(rodent_cfg, repair_swaps="off").stac)[0] == "off"
+    off = hs.stage_cfg(rodent_cfg, repair_swaps=False)  # what YAML 1.1 makes of a bare `off`
     assert swaps_options(off.stac)[0] == "off" and off.stac.repair_swaps == "off" and _repair_swaps_mode(off, names)[0] == []
-    lr = _cfg(rodent_cfg, repair_swaps="lr")  # needs no fill_missing: it makes no NaN
+    lr = hs.stage_cfg(rodent_cfg, repair_swaps="lr")  # needs no fill_missing: it makes no NaN
     pairs, args = _repair_swaps_mode(lr, names)
     assert pairs == pc.swap_pairs(names) and args == {"n_sigma": 6.0, "min_dev": 0.002, "min_bad": 3}
-    named = _cfg(rodent_cfg, repair_swaps=[["KneeR", "KneeL"], ["Snout", "TailBase"]], swaps_nsigma=8, swaps_min_dev=0, swaps_min_bad=5)
+    named = hs.stage_cfg(rodent_cfg, repair_swaps=[["KneeR", "KneeL"], ["Snout", "TailBase"]], swaps_nsigma=8, swaps_min_dev=0, swaps_min_bad=5)
     pairs, args = _repair_swaps_mode(named, names)
     assert pairs == [(names.index("KneeR"), names.index("KneeL")), (names.index("Snout"), names.index("TailBase"))]
     assert args == {"n_sigma": 8.0, "min_dev": 0.0, "min_bad": 5}
@@ -378,18 +364,18 @@ def test_config_repair_swaps_keys(rodent_cfg):
            dict(swaps_min_bad=True), dict(swaps_min_bad=None), dict(swaps_min_bad=2**31)]
     for over in bad:
         with pytest.raises(ValueError):
-            _cfg(rodent_cfg, **over)
-        cfg = _cfg(rodent_cfg)  # also when the key is set after validation: the run reads the caller's config
+            hs.stage_cfg(rodent_cfg, **over)
+        cfg = hs.stage_cfg(rodent_cfg)  # also when the key is set after validation: the run reads the caller's config
         cfg.stac.update(over)
         with pytest.raises(ValueError):
             _repair_swaps_mode(cfg, names)
     with pytest.raises(ValueError):
-        _cfg(rodent_cfg, swaps_nsigm=5)  # an unknown key stays an error
+        hs.stage_cfg(rodent_cfg, swaps_nsigm=5)  # an unknown key stays an error
     # what only the keypoint names can say
     for over in (dict(repair_swaps=[["KneeL", "Knee"]]), dict(repair_swaps=[["KneeL", "KneeL"]]),
                  dict(repair_swaps=[["KneeL", "KneeR"], ["HipL", "KneeR"]])):
         with pytest.raises(ValueError):
-            _repair_swaps_mode(_cfg(rodent_cfg, **over), names)
+            _repair_swaps_mode(hs.stage_cfg(rodent_cfg, **over), names)
     with pytest.raises(ValueError, match="left / right"):
         _repair_swaps_mode(lr, ["a", "b", "c"])
 
@@ -429,10 +415,10 @@ def test_run_stac_refuses_bad_candidates_before_any_work(tmp_path, rodent_cfg):
     for over, what in ((dict(repair_swaps=[["KneeL", "Elbow"]]), "Elbow"), (dict(repair_swaps=[["KneeL", "KneeR"], ["KneeR", "HipL"]]), "two pairs"),
                        (dict(repair_swaps=[["HipL", "HipL"]]), "twice")):
         with pytest.raises(ValueError, match=what):  # before the model is even looked for: the path does not exist
-            run_stac(_cfg(rodent_cfg, **over), kp, names, base_path=tmp_path / "nowhere")
+            run_stac(hs.stage_cfg(rodent_cfg, **over), kp, names, base_path=tmp_path / "nowhere")
     with pytest.raises(ValueError, match="left / right"):
-        run_stac(_cfg(rodent_cfg, repair_swaps="lr"), np.zeros((4, 6), np.float32), ["a", "b"], base_path=tmp_path / "nowhere")
-    cfg = _cfg(rodent_cfg)
+        run_stac(hs.stage_cfg(rodent_cfg, repair_swaps="lr"), np.zeros((4, 6), np.float32), ["a", "b"], base_path=tmp_path / "nowhere")
+    cfg = hs.stage_cfg(rodent_cfg)
     cfg.stac.swaps_min_bad = 0  # a bad value set after validation
     with pytest.raises(ValueError, match="swaps_min_bad"):
         run_stac(cfg, kp, names, base_path=tmp_path / "nowhere")
@@ -442,65 +428,7 @@ def test_run_stac_refuses_bad_candidates_before_any_work(tmp_path, rodent_cfg):
 # ---- C ABI and wrapper ------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def lib():
-    from stac_mjx_amd.build import build_extension
-    from stac_mjx_amd.engine import load_library
-
-    build_extension()
-    return load_library()
-
-
-def _c_class(ctype):
-    if "*" in ctype:
-        return "pointer"
-    base = ctype.replace("const", " ").split()
-    assert len(base) == 1 and base[0] in ("int32_t", "int64_t", "float", "double", "void"), ctype
-    return base[0]
-
-
-def _ctypes_class(t):
-    if t is None:
-        return "void"
-    if t in (C.c_void_p, C.c_char_p) or issubclass(t, C._Pointer):
-        return "pointer"
-    return {C.c_int32: "int32_t", C.c_int64: "int64_t", C.c_float: "float", C.c_double: "double"}[t]
-
-
-def _header_prototypes():
-    """Every ``ret stac_name(args);`` of include/stac_hip_swaps.h -> name: (class of ret, [class of every argument])"""
-    text = re.sub(r"/\*.*?\*/", " ", HEADER.read_text(), flags=re.S)
-    text = "\n".join(ln for ln in text.splitlines() if not ln.lstrip().startswith("#"))
-    text = text.replace('extern "C" {', " ")
-    protos = {}
-    for stmt in text.split(";"):
-        stmt = " ".join(stmt.split())
-        if stmt in ("", "}"):
-            continue
-        m = re.fullmatch(r"(.*?)\b(stac_[a-z0-9_]+) ?\((.*)\)", stmt)
-        assert m, f"not a prototype: {stmt!r}"  # nothing of the header is passed over in silence
-        ret, name, args = m.groups()
-        protos[name] = (_c_class(ret), [_c_class(re.sub(r"\w+$", "", a.strip())) for a in args.split(",")])
-    return protos
-
-
-def test_third_abi_table_against_the_third_header(lib):
-    from stac_mjx_amd import abi, build
-
-    protos = _header_prototypes()
-    assert list(protos) == ["stac_prep_swaps_workspace", "stac_prep_swaps"] and set(protos) == set(abi.SWAPS_PROTOTYPES)
-    for name, (ret, args) in protos.items():
-        restype, argtypes = abi.SWAPS_PROTOTYPES[name]
-        assert len(argtypes) == len(args), name
-        assert [_ctypes_class(t) for t in argtypes] == args and _ctypes_class(restype) == ret, name
-        fn = getattr(lib, name)  # the library carries them, declared by abi.declare
-        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
-    assert len(abi.SWAPS_PROTOTYPES["stac_prep_swaps"][1]) == 16
-    # the other headers, their tables and the version are what they were
-    tables = (abi.PROTOTYPES, abi.PAIRWISE_PROTOTYPES, abi.SWAPS_PROTOTYPES)
-    assert len(set().union(*tables)) == sum(len(t) for t in tables) and len(abi.PROTOTYPES) == 31 and len(abi.PAIRWISE_PROTOTYPES) == 2
-    assert abi.ABI_SYMBOLS == tuple(abi.PROTOTYPES) and lib.stac_abi_version() == 3
-    for other in ("stac_hip.h", "stac_hip_pairwise.h"):
-        assert "swaps" not in (ROOT / "include" / other).read_text() and ROOT / "include" / other in build.HEADERS
-    assert HEADER in build.HEADERS
+    return hs.loaded_library()
 
 
 def test_workspace_is_the_pairwise_workspace(lib):
@@ -598,7 +526,7 @@ def test_kp_swapped_round_trip_and_old_files(tmp_path, rodent_cfg):
                     names_qpos=["a", "b"], names_xpos=["w", "v"], kp_names=["k0", "k1", "k2"])
     assert d.kp_swapped.size == 0 and "kp_swapped" not in d.as_dict()
     assert list(io.StacData.__dataclass_fields__)[-1] == "kp_rejected"  # (the trailing field stays the trailing field)
-    cfg = _cfg(rodent_cfg)
+    cfg = hs.stage_cfg(rodent_cfg)
     suffixes = [".npz"] + ([".h5"] if io.h5py is not None else [])
     for suffix in suffixes:
         plain = io.save_data_to_h5(config=cfg, file_path=tmp_path / f"plain{suffix}", **d.as_dict())

@@ -108,15 +108,23 @@ PROTOTYPES = {
     "stac_report_errors": (i32, [P(StacReportParams)]),
 }  # fmt: skip
 ABI_SYMBOLS = tuple(PROTOTYPES)
+# every function csrc/select/stac_select.h declares (libstac_select.so, the companion library of stac.fit_frames), in its order
+SELECT_PROTOTYPES = {
+    "stac_select_last_error": (C.c_char_p, []),
+    "stac_select_last_error_code": (i32, []),
+    "stac_select_workspace": (i64, [i64, i32]),
+    "stac_select_diverse": (i32, [vp, i64, i32, vp, i64, vp, vp, vp, vp, i64, vp]),
+}
 
 
 class StacHipError(RuntimeError):
     pass
 
 
-def declare(lib):
-    """Declares ``restype`` and ``argtypes`` of every function of the table on ``lib`` (idempotent) -> ``lib``."""
-    for name, (restype, argtypes) in PROTOTYPES.items():
+def declare(lib, prototypes=None):
+    """Declares ``restype`` and ``argtypes`` of every function of the table (``prototypes`` None: ``PROTOTYPES``) on ``lib``
+    (idempotent) -> ``lib``."""
+    for name, (restype, argtypes) in (PROTOTYPES if prototypes is None else prototypes).items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     return lib

@@ -1,4 +1,5 @@
-"""Builds the HIP extension in-tree: ``stac_mjx_amd/csrc/libstac_hip.so`` (gfx950 only).
+"""Builds the HIP extension in-tree: ``stac_mjx_amd/csrc/libstac_hip.so`` and its companion
+``stac_mjx_amd/csrc/select/libstac_select.so`` (gfx950 only).
 
 ``hipcc`` cross-compiles without a GPU.  ``-ffp-contract=off -fno-fast-math`` is part of the
 arithmetic contract of the kernels (bit-identical to the CPU oracle), not a tuning choice.
@@ -36,6 +37,13 @@ def hipcc_path() -> str:
 
 
 STAMP = CSRC / "libstac_hip.so.stamp"
+# The companion library of stac.fit_frames (csrc/select/: its own C header, digest and stamp).  ABI v3 of libstac_hip.so stays as it
+# is; the directory is matched by neither glob above.  The rule header includes csrc/stac_pairwise.hpp, so HEADERS are in its digest.
+SELECT_DIR = CSRC / "select"
+SELECT_LIB = SELECT_DIR / "libstac_select.so"
+SELECT_STAMP = SELECT_DIR / "libstac_select.so.stamp"
+SELECT_SOURCES = sorted(SELECT_DIR.glob("*.hip"))
+SELECT_HEADERS = sorted(SELECT_DIR.glob("*.hpp")) + sorted(SELECT_DIR.glob("*.h"))
 
 
 def source_digest() -> str:
@@ -50,26 +58,48 @@ def source_digest() -> str:
     return h.hexdigest()
 
 
+def select_digest() -> str:
+    """``source_digest`` of ``libstac_select.so``."""
+    import hashlib
+
+    h = hashlib.sha256(" ".join(FLAGS).encode())
+    for p in SELECT_SOURCES + SELECT_HEADERS + HEADERS:
+        h.update(p.name.encode())
+        h.update(p.read_bytes())
+    return h.hexdigest()
+
+
 def is_stale() -> bool:
     if not LIB.exists() or not STAMP.exists():
         return True
     return STAMP.read_text().strip() != source_digest()
 
 
-def build_extension(force: bool = False, verbose: bool = False) -> Path:
-    if not force and not is_stale():
-        return LIB
+def select_is_stale() -> bool:
+    return not SELECT_LIB.exists() or not SELECT_STAMP.exists() or SELECT_STAMP.read_text().strip() != select_digest()
+
+
+def _compile(sources, lib, stamp, digest, verbose):
     import time
 
-    cmd = [hipcc_path(), *FLAGS, *map(str, SOURCES), "-o", str(LIB)]
+    cmd = [hipcc_path(), *FLAGS, *map(str, sources), "-o", str(lib)]
     t0 = time.perf_counter()
     res = subprocess.run(cmd, capture_output=True, text=True)
     if res.returncode != 0:
         raise RuntimeError("hipcc failed:\n" + res.stdout + res.stderr)
-    STAMP.write_text(source_digest() + "\n")
+    stamp.write_text(digest() + "\n")
     if verbose:
         print(res.stdout + res.stderr)
-        print(f"[stac build] {' '.join(cmd)}\n[stac build] compiled in {time.perf_counter() - t0:.0f} s, sources sha256 {source_digest()[:16]}")
+        print(f"[stac build] {' '.join(cmd)}\n[stac build] compiled in {time.perf_counter() - t0:.0f} s, sources sha256 {digest()[:16]}")
+
+
+def build_extension(force: bool = False, verbose: bool = False) -> Path:
+    """Builds what is stale (``force``: both libraries) -> the path of ``libstac_hip.so``; ``libstac_select.so`` stands beside it
+    in ``csrc/select``."""
+    if force or select_is_stale():
+        _compile(SELECT_SOURCES, SELECT_LIB, SELECT_STAMP, select_digest, verbose)
+    if force or is_stale():
+        _compile(SOURCES, LIB, STAMP, source_digest, verbose)
     return LIB
 
 

@@ -54,14 +54,19 @@ _MUJOCO_REQUIRED = ("solver", "iterations", "ls_iterations")
 # resample: off (default) | kaiser, with mocap_hz (the rate of the recording), resample_hz (the rate wanted), resample_lobes (zero
 # crossings of the sinc on each side, 1 .. 16, default 10) and resample_beta (the Kaiser window's, >= 0, default 5.0) -- the ik_only
 # result is resampled per clip on the GPU into a second file next to the first, which does not change; needs postprocess = gpu, read
-# from the caller's config)
+# from the caller's config;
+# fit_frames: first (default) | strided | diverse -- which n_fit_frames rows of the prepared series calibrate the offsets: the first
+# ones (the reference), every (candidates / n)-th candidate, or the frames whose pairwise keypoint distances differ most (greedy
+# farthest-point selection on the GPU); strided and diverse pass over every frame that a preparation stage marked, hand the rows
+# to fit_offsets in ascending time order and write <fit file>.frames.json next to the fit file, read from the caller's config)
 _STAC_EXTENSIONS = ("solver", "lanes_per_chain", "device", "time_indices", "fit_frames_per_clip", "reference_marker_order", "gather", "gather_max_bytes", "lm_maxiter", "postprocess", "fill_missing",
                     "reject_outliers", "outlier_window", "outlier_nsigma", "outlier_min_dev", "report", "report_quantiles", "report_worst",
                     "smooth", "smooth_window", "smooth_order", "smooth_sigma",
                     "reject_pairwise", "pairwise_nsigma", "pairwise_min_dev", "pairwise_votes",
                     "repair_swaps", "swaps_nsigma", "swaps_min_dev", "swaps_min_bad",
                     "fill_donors", "fill_donors_triples",
-                    "resample", "mocap_hz", "resample_hz", "resample_lobes", "resample_beta")
+                    "resample", "mocap_hz", "resample_hz", "resample_lobes", "resample_beta",
+                    "fit_frames")
 _MODEL_EXTENSIONS = ("KP_NAMES_LABEL3D_PATH",)
 
 
@@ -255,6 +260,19 @@ def donor_options(stac) -> tuple:
     n_triples = checked_int(stac.get("fill_donors_triples", DONOR_DEFAULTS["fill_donors_triples"]), "stac.fill_donors_triples", ConfigError,
                             1, DONOR_MAX_TRIPLES)
     return mode, n_triples
+
+
+FIT_FRAMES_MODES = ("first", "strided", "diverse")
+
+
+def fit_frames_options(stac) -> str:
+    """``stac.fit_frames`` out of a ``stac`` mapping -> "first" (default, also for a key without a value) | "strided" | "diverse";
+    ``ConfigError`` for anything else."""
+    mode = stac.get("fit_frames", "first")
+    mode = "first" if mode is None else mode
+    if not isinstance(mode, str) or mode not in FIT_FRAMES_MODES:
+        raise ConfigError(f"stac.fit_frames must be first, strided or diverse, not {mode!r}")
+    return mode
 
 
 REPORT_DEFAULTS = {"report_quantiles": (500, 900, 990), "report_worst": 10}
@@ -521,6 +539,7 @@ def validate_config(cfg: dict) -> ConfigNode:
         if isinstance(stac.get(key), bool):  # the file that is written with a result says off / on, not the boolean
             stac[key] = _switch(stac, key)
         options(stac)
+    fit_frames_options(stac)
     return _wrap({"model": model, "stac": stac})
 
 

@@ -16,7 +16,7 @@ import torch
 
 from .abi import (ABI_SYMBOLS, StacHipError, StacModelTables, StacQParams, _f32p, _i32p, _ptr, _u8p, check, declare,  # noqa: F401
                   hip_error, last_error, stream_ptr)
-from .build import LIB, STAMP, source_digest
+from .build import LIB, SELECT_LIB, SELECT_STAMP, STAMP, select_digest, source_digest
 
 ABI_VERSION = 3  # include/stac_hip.h: STAC_HIP_ABI_VERSION
 SOLVERS = {"pg": 0, "lm": 1}  # STAC_SOLVER_PG (the reference's algorithm, parity mode) / STAC_SOLVER_LM
@@ -47,6 +47,29 @@ def load_library(path: Path | None = None):
     declare(lib)
     if path is None:
         _LIB = lib
+    return lib
+
+
+_SELECT_LIB = None
+
+
+def load_select_library(path: Path | None = None):
+    """Load ``libstac_select.so`` (csrc/select: the frame selection of ``stac.fit_frames``) with every prototype of
+    ``abi.SELECT_PROTOTYPES`` declared; raises if it has not been built or was built from other sources, like ``load_library``."""
+    global _SELECT_LIB
+    if _SELECT_LIB is not None and path is None:
+        return _SELECT_LIB
+    p = Path(path) if path else SELECT_LIB
+    if not p.exists():
+        raise StacHipError(f"HIP extension not built: {p} is missing (run `python -m stac_mjx_amd.build`)")
+    if p == SELECT_LIB and SELECT_STAMP.exists() and SELECT_STAMP.read_text().strip() != select_digest():
+        raise StacHipError(f"{p} was built from other sources than the ones in this tree (stamp {SELECT_STAMP.name} differs): "
+                           "rebuild with `python -m stac_mjx_amd.build`")
+    from .abi import SELECT_PROTOTYPES
+
+    lib = declare(C.CDLL(str(p)), SELECT_PROTOTYPES)
+    if path is None:
+        _SELECT_LIB = lib
     return lib
 
 

@@ -10,7 +10,7 @@ import numpy as np
 
 from . import dist, io, utils
 from .config import (DONORS_NEED_FILL, GATHER_NONE_CONTINUOUS, PAIRWISE_NEEDS_FILL, POSTPROCESS_GPU_MARKER_ORDER, RESAMPLE_SHARDED, compose_config,
-                     donor_options, fill_missing_options, outlier_options, pairwise_options, postprocess_options, report_options, resample_options,
+                     donor_options, fill_missing_options, fit_frames_options, outlier_options, pairwise_options, postprocess_options, report_options, resample_options,
                      smooth_options, swaps_candidates, swaps_options)
 from .stac import Stac
 
@@ -53,6 +53,10 @@ def run_stac(cfg, kp_data, kp_names, base_path=None, *, setup=None, device=None)
     ``stac.resample: kaiser`` with ``stac.mocap_hz`` and ``stac.resample_hz`` (needs ``postprocess: gpu``) writes, after the ik_only
     file and without changing it, a second file next to it (``resampled_path``) that holds the result at the other rate, resampled per
     clip on the GPU by ``Stac.resample_result`` (DESIGN.md "Resampling fitted poses"); the two paths returned are those of today.
+    ``stac.fit_frames: strided | diverse`` calibrates the offsets on ``n_fit_frames`` rows chosen from the whole prepared series
+    instead of its first ones -- even steps, or the frames whose pairwise keypoint distances differ most, chosen on the GPU -- never
+    on a frame that a preparation stage marked, and writes the choice as ``<fit file>.frames.json`` (DESIGN.md "Choosing calibration
+    frames"); more ``n_fit_frames`` than frames, or than usable frames, is a ``ValueError``.
     """
     base_path = Path.cwd() if base_path is None else Path(base_path)
     kp_data = np.asarray(kp_data)
@@ -71,7 +75,7 @@ def run_stac(cfg, kp_data, kp_names, base_path=None, *, setup=None, device=None)
     pre.check_run(dist.world()[1])
     series = _prepare_series(stac, cfg, kp_data, pre)
     if not cfg.stac.skip_fit_offsets:
-        fit_offsets_path = _run_fit(stac, cfg, series, fit_offsets_path, pre.report)
+        fit_offsets_path = _run_fit(stac, cfg, series, fit_offsets_path, pre.report, pre.fit_frames)
     else:
         print("Skipping fit_offsets. To change this behavior, set cfg.stac.skip_fit_offsets to False.")
     if cfg.stac.skip_ik_only:
@@ -80,16 +84,66 @@ def run_stac(cfg, kp_data, kp_names, base_path=None, *, setup=None, device=None)
     return _run_ik(stac, series, fit_offsets_path, ik_only_path, pre, start)
 
 
-def _run_fit(stac, cfg, series, fit_offsets_path, report) -> Path:
-    """``fit_offsets`` on the first ``n_fit_frames`` of the series and the fit file -> the name the file really has."""
-    kps = series.kp_data[: cfg.stac.n_fit_frames]
+def _run_fit(stac, cfg, series, fit_offsets_path, report, fit_frames="first") -> Path:
+    """``fit_offsets`` on ``n_fit_frames`` rows of the series -- the first ones, or with ``stac.fit_frames`` those of
+    ``_select_fit_frames`` in ascending time order -- and the fit file -> the name the file really has."""
+    rows = info = None
+    if fit_frames == "first":
+        kps = series.kp_data[: cfg.stac.n_fit_frames]
+    else:
+        rows, info = _select_fit_frames(stac, cfg, series, fit_frames)
+        kps = series.kp_data[rows]
     print(f"Running fit. Mocap data shape: {kps.shape}")
     fit_data = stac.fit_offsets(kps)
-    series.attach(fit_data, 0, fit_data.kp_data.shape[0])  # (the rows of the fit file are the first rows of the series, in order)
+    if rows is None:
+        series.attach(fit_data, 0, fit_data.kp_data.shape[0])  # (the rows of the fit file are the first rows of the series, in order)
+    else:
+        series.attach_rows(fit_data, rows[: fit_data.kp_data.shape[0]])  # (fit_frames_per_clip drops a ragged tail)
     # multi-GPU: rank 0 holds the gathered result and writes it
-    fit_offsets_path = _write_result(stac, cfg, fit_data, fit_offsets_path, report, dist.world()[0] == 0)
+    writes = dist.world()[0] == 0
+    fit_offsets_path = _write_result(stac, cfg, fit_data, fit_offsets_path, report, writes)
+    if rows is not None and writes:
+        _write_frames(fit_offsets_path, rows, info)
     print(f"saved fit to {fit_offsets_path}", flush=True)
     return fit_offsets_path
+
+
+def _select_fit_frames(stac, cfg, series, mode):
+    """``stac.fit_frames: strided | diverse`` -> (the ``n_fit_frames`` chosen rows of the prepared series, ascending, and the ``info``
+    of ``Stac.select_frames``).  Every rank computes the selection itself: same bits.  A frame that carries a mark of any
+    preparation stage (``series.marks``) is no candidate: the offsets are calibrated on observed keypoints only."""
+    n, T = int(cfg.stac.n_fit_frames), series.kp_data.shape[0]
+    exclude = np.zeros(T, bool)
+    for mark in series.marks.values():
+        exclude |= (np.asarray(mark).reshape(T, -1) != 0).any(axis=1)
+    n_cand = int(T - np.count_nonzero(exclude))
+    if n_cand < n:
+        raise ValueError(f"stac.fit_frames = {mode}: n_fit_frames = {n}, but only {n_cand} of the {T} frames carry no mark of a "
+                         "preparation stage")
+    rows, info = stac.select_frames(series.kp_data, n, mode, exclude=exclude)
+    if info["n_selected"] < n:
+        raise ValueError(f"stac.fit_frames = {mode}: n_fit_frames = {n}, but the selection stopped after {info['n_selected']} frames: "
+                         "every other usable frame equals one of them (or has a coordinate that is not finite)")
+    return rows, info
+
+
+def frames_path(fit_offsets_path) -> Path:
+    """``fit.h5`` -> ``fit.h5.frames.json`` (of the name the fit file really has: ``io.resolve_output_path``)."""
+    p = io.resolve_output_path(fit_offsets_path)
+    return p.with_name(p.name + ".frames.json")
+
+
+def _write_frames(fit_offsets_path, rows, info) -> Path:
+    """What ``stac.fit_frames`` chose, as JSON next to the fit file: the mode, the rows of the series that are the rows of the fit
+    file (ascending), the same in selection order, and ``radius2`` (``diverse``; the first is infinite: written as null)."""
+    import json
+
+    path = frames_path(fit_offsets_path)
+    r2 = [None if not np.isfinite(v) else float(v) for v in info["radius2"]]
+    path.write_text(json.dumps({"mode": info["mode"], "indices": [int(i) for i in rows], "order": [int(i) for i in info["order"]],
+                                "radius2": r2}, indent=1) + "\n")
+    print(f"fit_frames: wrote {path}", flush=True)
+    return path
 
 
 def _run_ik(stac, series, fit_offsets_path, ik_only_path, pre, start):
@@ -214,6 +268,13 @@ class _Preflight:
         self.report = _report_mode(self.cfg)
         self.smooth = _smooth_mode(self.cfg)
         self.resample = _resample_mode(self.cfg)
+        self.fit_frames = fit_frames_options(stac)
+        if self.fit_frames != "first" and not stac.skip_fit_offsets:  # (first keeps the reference's slice, which takes what there is)
+            n = int(stac.n_fit_frames)
+            if n > self.n_frames:
+                raise ValueError(f"stac.fit_frames = {self.fit_frames}: n_fit_frames = {n} exceeds the {self.n_frames} frames of the recording")
+            if n < 1:
+                raise ValueError(f"stac.fit_frames = {self.fit_frames}: n_fit_frames must be at least 1, not {n}")
         if stac.skip_ik_only:  # (checked all the same; there is no ik_only file to resample)
             self.resample = None
         self.marker_order = not stac.skip_ik_only and bool(stac.get("reference_marker_order", False))
@@ -255,6 +316,11 @@ class _Series:
         """The rows ``lo:hi`` of every mark become the field of that name of ``data`` (a ``StacData`` of those rows of the series)."""
         for name, mark in self.marks.items():
             setattr(data, name, mark[lo:hi])
+
+    def attach_rows(self, data, rows):
+        """The index form: ``data`` holds the rows ``rows`` of the series, in that order."""
+        for name, mark in self.marks.items():
+            setattr(data, name, mark[rows])
 
 
 def _prepare_series(stac, cfg, kp_data, pre) -> _Series:

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import dist, prng, utils
-from .config import GATHER_NONE_CONTINUOUS, INT32_MAX, POSTPROCESS_GPU_MARKER_ORDER, report_options, smooth_marker_order_refusal
+from .config import GATHER_NONE_CONTINUOUS, INT32_MAX, POSTPROCESS_GPU_MARKER_ORDER, checked_int, report_options, smooth_marker_order_refusal
 from .engine import Engine
 from .fit_model import FitSetup, build_fit_setup
 from .io import StacData
@@ -187,6 +187,48 @@ class Stac:
         out, gap, src = prep.fill_donors(kp, don)
         out, _ = self._log_flagged(out, ((src > 0) & (src < 255)).to(torch.uint8), "fill_donors", self._kp_names, "filled from donors")
         return out, gap.cpu().numpy(), src.cpu().numpy()
+
+    # -- select_frames (engine extension; DESIGN.md "Choosing calibration frames") ---------------------------------------
+    def select_frames(self, kp_data, n, mode="diverse", exclude=None):
+        """``n`` calibration frames of the whole series ``kp_data`` [T, 3K] -> ``(indices [n_selected] int64 ascending, info)``.
+        ``mode``: "first" (the first ``n`` candidates), "strided" (``select.select_strided``: even steps through the candidates,
+        on the host) or "diverse" (``select.select_diverse``: greedy farthest-point selection over the frames' pairwise keypoint
+        distances, on the GPU).  ``exclude`` ([T], truthy = not a candidate; None: every frame is one).  ``info``: ``mode``,
+        ``order`` (the indices in selection order), ``radius2`` (float32, ``diverse`` only: the squared descriptor distance of every
+        pick to the picks before it, else empty) and ``n_selected`` (below ``n`` only where ``diverse`` stopped early).  Logs the
+        covering radius and how the picks spread over the ten tenths of the recording."""
+        from . import select
+
+        if mode not in select.MODES:
+            raise ValueError(f"select_frames: mode must be first, strided or diverse, not {mode!r}")
+        kp = np.asarray(kp_data)
+        if kp.ndim != 2 or kp.shape[1] != 3 * len(self._kp_names):
+            raise ValueError(f"select_frames: kp_data must be [frames, {3 * len(self._kp_names)}], got {kp.shape}")
+        T = int(kp.shape[0])
+        n = checked_int(n, "select_frames: n", ValueError, 1)
+        cand = None
+        if exclude is not None:
+            ex = np.asarray(exclude)
+            if ex.shape != (T,):
+                raise ValueError(f"select_frames: exclude must be [{T}], one entry per frame, got {ex.shape}")
+            cand = ex == 0
+        radius2 = np.zeros(0, np.float32)
+        if mode == "diverse":
+            sel, r2, n_sel = select.select_diverse(self._series_to_device(kp, "select_frames"), n, cand)
+            order, radius2 = sel.cpu().numpy()[:n_sel], r2.cpu().numpy()[:n_sel]
+        elif mode == "strided":
+            order = select.select_strided(T, n, cand)
+        else:
+            frames = np.arange(T, dtype=np.int64) if cand is None else np.flatnonzero(cand).astype(np.int64)
+            if frames.size < n:
+                raise ValueError(f"select_frames: {n} frames wanted, but only {frames.size} of the {T} frames are candidates")
+            order = frames[:n]
+        order = np.asarray(order, dtype=np.int64)
+        tenths = np.bincount(np.minimum(order * 10 // max(T, 1), 9), minlength=10) if order.size else np.zeros(10, np.int64)
+        cover = f", covering radius {float(np.sqrt(radius2[-1])):.6g} (descriptor units)" if radius2.size > 1 else ""
+        self._log(f"select_frames ({mode}): {order.size} of {T} frames{cover}; picks per tenth of the recording: "
+                  + " ".join(str(int(c)) for c in tenths))
+        return np.sort(order), {"mode": mode, "order": order, "radius2": radius2, "n_selected": int(order.size)}
 
     # -- fit_report (engine extension; DESIGN.md "Fit report") -----------------------------------------------------------
     def fit_report(self, data, permille=None, worst=None) -> dict:

@@ -101,12 +101,17 @@ __device__ __forceinline__ float row_shr1(float v) {
 // lane butterflies for the levels below G, then the registers.  Every lane of the group gets the sum.
 // (Round 6 tried gfx950's v_permlane16_swap / v_permlane32_swap for the two levels that cross a 16-lane row, instead of ds_swizzle /
 //  ds_bpermute: 3 % SLOWER on 250-frame clips, 13 % on the LM solver -- and not the xor-partner exchange this tree needs.  Dropped.)
-template <int G, int NQR>
+// ZPAD (lean throughput kernels, STAC_TRANS & 2): a padding register enters the register tree as the literal +0 instead of running
+// the lane butterfly on a zero -- (+0) + (+0) = +0 at every level, the same value; the compiler cannot fold a DPP move of a constant,
+// so without it a register is pinned to 0 across the trip loop and every sum spends six instructions on it.  The additions
+// "t + 0" of the register tree stay: they turn a -0 into +0.
+template <int G, int NQR, bool ZPAD = false>
 __device__ __forceinline__ float group_tree_sum(const float (&v)[NQR]) {
     constexpr int PR = NQR <= 1 ? 1 : NQR <= 2 ? 2 : NQR <= 4 ? 4 : NQR <= 8 ? 8 : NQR <= 16 ? 16 : 32;
     float t[PR];
 #pragma unroll
     for (int r = 0; r < PR; ++r) {
+        if (ZPAD && r >= NQR) { t[r] = 0.0f; continue; }
         float x = r < NQR ? v[r] : 0.0f;
         if constexpr (G >= 2) x = x + xor_partner<1>(x);
         if constexpr (G >= 4) x = x + xor_partner<2>(x);
@@ -279,6 +284,7 @@ constexpr int kProfSub = 8;
         psub[k] += pq_ - ps0;                                    \
         ps0 = pq_;                                               \
     } while (0)
+#define PROF_MARK(k)
 #define PROF_TRIP
 #ifdef STAC_PROFILE_SEL
 #define PROF_KEEP(isroot) ((isroot) == (STAC_PROFILE_SEL != 0))
@@ -307,6 +313,7 @@ constexpr int kProfSub = 8;
 #define PROF_LM_END
 #define PROF_TICK(i) asm volatile("; TICK " #i)
 #define PROF_SUB(k) asm volatile("; SUB " #k)
+#define PROF_MARK(k) asm volatile("; MARK " #k)  // (listing only: sub-marks of the solver transition, profiles/r11/transition.md)
 #define PROF_FLUSH(a)
 #define PROF_FLUSH_SUB(a)
 #else
@@ -316,6 +323,7 @@ constexpr int kProfSub = 8;
 #define PROF_LM_END
 #define PROF_TICK(i)
 #define PROF_SUB(k)
+#define PROF_MARK(k)
 #define PROF_FLUSH(a)
 #define PROF_FLUSH_SUB(a)
 #endif

@@ -510,6 +510,17 @@ void q_phase_kernel(const QArgs a_in) {
     constexpr bool kSbsSite = SITEPIN && LEAN && SPEC == 0 && G == 16 && (STAC_SBS & 4);  // (the rounds' records are the pinned ones)
     constexpr bool kSbsRoot = LEAN && SPEC == 0 && (STAC_SBS & 8);
     constexpr bool kSbsGnew = LEAN && SPEC == 0 && (STAC_SBS & 16);
+    // Lean throughput kernels: the solver transition without the work its result does not need (profiles/r11/NOTES.md).  STAC_TRANS
+    // selects the parts in experiment builds: 1 = a chain in ST_VG_X takes its stopping residual from the residual block of the fused
+    // chains, so the sums compute the line-search step alone; 2 = padding registers of the nq-sums are literal zeros; 4 = the accept
+    // takes the candidate that the sums computed (recomputed only where a step is taken without evaluation).  Same operations on the
+    // same operands in every part.  The latency and the generic kernels keep their code.
+#ifndef STAC_TRANS
+#define STAC_TRANS 7
+#endif
+    constexpr bool kTransVgx = LEAN && SPEC == 0 && (STAC_TRANS & 1);
+    constexpr bool kTransZpad = LEAN && SPEC == 0 && (STAC_TRANS & 2);
+    constexpr bool kTransCand = LEAN && SPEC == 0 && (STAC_TRANS & 4);
     enum : uint32_t { CW_ROOT_FAST = 0xFFu, CW_HAND = 1u << 8, CW_QUEUE = 1u << 9 };
     uint32_t ctl_word = 0;
     int32_t fk3r_pin = 0;
@@ -1032,7 +1043,7 @@ void q_phase_kernel(const QArgs a_in) {
                 term[r] = k < K ? site_term(k, kpr[r][0], kpr[r][1], kpr[r][2], ((kpw_bits >> r) & 1u) != 0, r) : 0.0f;
             }
             }
-            loss = group_tree_sum<G, NSR>(term);
+            loss = group_tree_sum<G, NSR, kTransZpad>(term);
             wave_sync();
             PROF_TICK(3);  // sites + loss
         } else {
@@ -1527,13 +1538,15 @@ void q_phase_kernel(const QArgs a_in) {
                 c_grad++;
                 st = ST_LS;
             }
-            float a0 = 0.0f, a1 = 0.0f;
+            const bool isx = kTransVgx && st_in == ST_VG_X;  // (its residual comes from the block of the fused chains below)
+            float a0 = 0.0f, a1 = 0.0f, c0 = 0.0f;
             if (in0) {
-                if (st_in == ST_VG_X) {
+                if (!kTransVgx && st_in == ST_VG_X) {
                     const float d = clipf(x[0] - gnew[0], LB(0, lg), UB(0, lg)) - x[0];
                     a0 = d * d;
                 } else if (st_in == ST_LS) {
-                    const float d = CAND(0, lg) - y[0];
+                    c0 = CAND(0, lg);
+                    const float d = c0 - y[0];
                     a0 = d * d;
                     a1 = d * g[0];
                 }
@@ -1555,7 +1568,14 @@ void q_phase_kernel(const QArgs a_in) {
                     if (nls >= a.maxls) accept = true;
                 }
                 if (accept) {
-                    const float cr = in0 ? CAND(0, lg) : x[0];
+                    float cr;
+                    if constexpr (kTransCand) {  // (the candidate of the sums, unless the step was halved behind them)
+                        float cc = c0;
+                        if (!evaluated_point_accepted) cc = CAND(0, lg);
+                        cr = in0 ? cc : x[0];
+                    } else {
+                        cr = in0 ? CAND(0, lg) : x[0];
+                    }
                     const float d = cr - x[0];
                     y[0] = FMA(spec_beta, d, cr);
                     x[0] = cr;
@@ -1563,7 +1583,7 @@ void q_phase_kernel(const QArgs a_in) {
                     fused = ls_with_grad && evaluated_point_accepted;
                 }
             }
-            if (__any(fused)) {
+            if (__any(fused || isx)) {
                 float f0 = 0.0f;
                 if (in0) {
                     const float d = clipf(x[0] - gnew[0], LB(0, lg), UB(0, lg)) - x[0];
@@ -1571,7 +1591,7 @@ void q_phase_kernel(const QArgs a_in) {
                 }
                 const float onef[1] = {f0};
                 const float e2 = group_tree_sum<G, 1>(onef) + 0.0f;
-                if (fused) sum0 = e2;
+                if (fused || isx) sum0 = e2;
             }
             if (st_in == ST_VG_X || fused) {
                 fx = loss;
@@ -1595,7 +1615,8 @@ void q_phase_kernel(const QArgs a_in) {
         }
         // nq-sums as pairwise trees over the striped registers (oracle: tree_sum); all groups compute
         // them every trip (a few dozen DPP adds), only the groups in the matching state use them.  Straight-line: the
-        // bounds come in one LDS round trip for the whole transition, both candidates of a term are computed and one is selected.
+        // bounds come in one LDS round trip for the whole transition; the generic and the latency kernels compute both candidates of a
+        // term and select one, the lean throughput kernels (kTransVgx) the line-search step alone.
         float lbs[NQR], ubs[NQR];
 #pragma unroll
         for (int r = 0; r < NQR; ++r) {
@@ -1603,22 +1624,32 @@ void q_phase_kernel(const QArgs a_in) {
             lbs[r] = LB(r, eb);
             ubs[r] = UB(r, eb);
         }
+        float cand[NQR];  // the line-search candidate of the sums (kTransCand: kept for the accept)
+        const bool isx = SPEC == 0 && st_in == ST_VG_X;
         {
             const float eta_s = (SPEC && st_in == ST_SPEC) ? eta * spec_pow : eta;
-            const bool isx = SPEC == 0 && st_in == ST_VG_X, isl = SPEC ? st_in == ST_SPEC : st_in == ST_LS;
+            const bool isl = SPEC ? st_in == ST_SPEC : st_in == ST_LS;
             float t0[NQR], t1[NQR];
 #pragma unroll
             for (int r = 0; r < NQR; ++r) {
                 const int e = r * G + lg;
-                const float dx = clipf(x[r] - gnew[r], lbs[r], ubs[r]) - x[r];
-                const float dl = clipf(FMA(-eta_s, g[r], y[r]), lbs[r], ubs[r]) - y[r];
-                const float d = isx ? dx : dl;
-                const bool on = e < nq && (isx || isl);
-                t0[r] = on ? d * d : 0.0f;
-                t1[r] = (on && isl) ? d * g[r] : 0.0f;
+                cand[r] = clipf(FMA(-eta_s, g[r], y[r]), lbs[r], ubs[r]);
+                const float dl = cand[r] - y[r];
+                if constexpr (kTransVgx) {  // (a chain in ST_VG_X rides the residual block below: one clip per register here)
+                    const bool on = e < nq && isl;
+                    t0[r] = on ? dl * dl : 0.0f;
+                    t1[r] = on ? dl * g[r] : 0.0f;
+                } else {
+                    const float dx = clipf(x[r] - gnew[r], lbs[r], ubs[r]) - x[r];
+                    const float d = isx ? dx : dl;
+                    const bool on = e < nq && (isx || isl);
+                    t0[r] = on ? d * d : 0.0f;
+                    t1[r] = (on && isl) ? d * g[r] : 0.0f;
+                }
             }
-            sum0 = group_tree_sum<G, NQR>(t0);
-            sum1 = group_tree_sum<G, NQR>(t1);
+            PROF_MARK(1);  // terms
+            sum0 = group_tree_sum<G, NQR, kTransZpad>(t0);
+            sum1 = group_tree_sum<G, NQR, kTransZpad>(t1);
         }
         PROF_TICK(7);  // transition terms + nq sums
         bool fused = false;  // accepted a candidate whose gradient is already in gnew
@@ -1635,10 +1666,23 @@ void q_phase_kernel(const QArgs a_in) {
             }
             if (accept) {
                 const float beta = spec_beta;  // (t - 1) / t_next of the running iteration
+                if constexpr (kTransCand) {
+                    // an evaluated point that is accepted is the candidate of the sums (eta, g and y are what they were there); only
+                    // a step taken without evaluation, at the halved eta, is computed here -- wave-uniform, rare
+                    if (__any(!evaluated_point_accepted)) {
+#pragma unroll
+                        for (int r = 0; r < NQR; ++r) {
+                            const float c2 = clipf(FMA(-eta, g[r], y[r]), lbs[r], ubs[r]);
+                            cand[r] = evaluated_point_accepted ? cand[r] : c2;
+                        }
+                    }
+                }
 #pragma unroll
                 for (int r = 0; r < NQR; ++r) {
                     const int e = r * G + lg;
-                    const float cr = e < nq ? clipf(FMA(-eta, g[r], y[r]), lbs[r], ubs[r]) : x[r];
+                    float cr;
+                    if constexpr (kTransCand) cr = e < nq ? cand[r] : x[r];
+                    else cr = e < nq ? clipf(FMA(-eta, g[r], y[r]), lbs[r], ubs[r]) : x[r];
                     const float d = cr - x[r];
                     y[r] = FMA(beta, d, cr);
                     x[r] = cr;
@@ -1647,9 +1691,12 @@ void q_phase_kernel(const QArgs a_in) {
                 fused = ls_with_grad && evaluated_point_accepted;
             }
         }
+        PROF_MARK(2);  // line-search test + accept
         // stopping residual of x_next: either this trip evaluated x (VG_X) or the accepted candidate
         // came with its gradient (fused)
-        if (SPEC == 0 && __any(fused)) {
+        // (kTransVgx: a chain in ST_VG_X has accepted nothing this trip, its x is the point that was evaluated: the same formula)
+        const bool resid = fused || (kTransVgx && isx);
+        if (SPEC == 0 && __any(resid)) {
             float t0[NQR];
 #pragma unroll
             for (int r = 0; r < NQR; ++r) {
@@ -1657,9 +1704,10 @@ void q_phase_kernel(const QArgs a_in) {
                 const float d = clipf(x[r] - gnew[r], lbs[r], ubs[r]) - x[r];
                 t0[r] = e < nq ? d * d : 0.0f;
             }
-            const float e2 = group_tree_sum<G, NQR>(t0);
-            if (fused) sum0 = e2;
+            const float e2 = group_tree_sum<G, NQR, kTransZpad>(t0);
+            if (resid) sum0 = e2;
         }
+        PROF_MARK(3);  // residual
         if (SPEC == 0 && (st_in == ST_VG_X || fused)) {
             fx = loss;
             error = __builtin_sqrtf(sum0);

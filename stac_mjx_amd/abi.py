@@ -115,6 +115,14 @@ SELECT_PROTOTYPES = {
     "stac_select_workspace": (i64, [i64, i32]),
     "stac_select_diverse": (i32, [vp, i64, i32, vp, i64, vp, vp, vp, vp, i64, vp]),
 }
+# every function csrc/mmask/stac_mmask.h declares (libstac_mmask.so, the companion library of stac.offset_mask), in its order
+MMASK_PROTOTYPES = {
+    "stac_mmask_last_error": (C.c_char_p, []),
+    "stac_mmask_last_error_code": (i32, []),
+    "stac_mmask_workspace": (i64, [i64, i32]),
+    "stac_mmask_partial": (i32, [vp, vp, vp, i32, vp, vp, i64, i32, vp, i64, vp, vp]),
+    "stac_mmask_finish": (i32, [vp, i32, vp, vp, f32, vp, vp, vp, vp]),
+}
 
 
 class StacHipError(RuntimeError):

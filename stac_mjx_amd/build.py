@@ -1,5 +1,5 @@
-"""Builds the HIP extension in-tree: ``stac_mjx_amd/csrc/libstac_hip.so`` and its companion
-``stac_mjx_amd/csrc/select/libstac_select.so`` (gfx950 only).
+"""Builds the HIP extension in-tree: ``stac_mjx_amd/csrc/libstac_hip.so`` and its companions
+``stac_mjx_amd/csrc/select/libstac_select.so`` and ``stac_mjx_amd/csrc/mmask/libstac_mmask.so`` (gfx950 only).
 
 ``hipcc`` cross-compiles without a GPU.  ``-ffp-contract=off -fno-fast-math`` is part of the
 arithmetic contract of the kernels (bit-identical to the CPU oracle), not a tuning choice.
@@ -44,6 +44,13 @@ SELECT_LIB = SELECT_DIR / "libstac_select.so"
 SELECT_STAMP = SELECT_DIR / "libstac_select.so.stamp"
 SELECT_SOURCES = sorted(SELECT_DIR.glob("*.hip"))
 SELECT_HEADERS = sorted(SELECT_DIR.glob("*.hpp")) + sorted(SELECT_DIR.glob("*.h"))
+# The companion library of stac.offset_mask (csrc/mmask/: the offset phase on observed keypoints only), built the same way.  Its C
+# header includes include/stac_hip.h for the status codes, so HEADERS are in its digest.
+MMASK_DIR = CSRC / "mmask"
+MMASK_LIB = MMASK_DIR / "libstac_mmask.so"
+MMASK_STAMP = MMASK_DIR / "libstac_mmask.so.stamp"
+MMASK_SOURCES = sorted(MMASK_DIR.glob("*.hip"))
+MMASK_HEADERS = sorted(MMASK_DIR.glob("*.hpp")) + sorted(MMASK_DIR.glob("*.h"))
 
 
 def source_digest() -> str:
@@ -69,6 +76,17 @@ def select_digest() -> str:
     return h.hexdigest()
 
 
+def mmask_digest() -> str:
+    """``source_digest`` of ``libstac_mmask.so``."""
+    import hashlib
+
+    h = hashlib.sha256(" ".join(FLAGS).encode())
+    for p in MMASK_SOURCES + MMASK_HEADERS + HEADERS:
+        h.update(p.name.encode())
+        h.update(p.read_bytes())
+    return h.hexdigest()
+
+
 def is_stale() -> bool:
     if not LIB.exists() or not STAMP.exists():
         return True
@@ -77,6 +95,10 @@ def is_stale() -> bool:
 
 def select_is_stale() -> bool:
     return not SELECT_LIB.exists() or not SELECT_STAMP.exists() or SELECT_STAMP.read_text().strip() != select_digest()
+
+
+def mmask_is_stale() -> bool:
+    return not MMASK_LIB.exists() or not MMASK_STAMP.exists() or MMASK_STAMP.read_text().strip() != mmask_digest()
 
 
 def _compile(sources, lib, stamp, digest, verbose):
@@ -94,8 +116,10 @@ def _compile(sources, lib, stamp, digest, verbose):
 
 
 def build_extension(force: bool = False, verbose: bool = False) -> Path:
-    """Builds what is stale (``force``: both libraries) -> the path of ``libstac_hip.so``; ``libstac_select.so`` stands beside it
-    in ``csrc/select``."""
+    """Builds what is stale (``force``: all three libraries) -> the path of ``libstac_hip.so``; ``libstac_select.so`` stands beside
+    it in ``csrc/select`` and ``libstac_mmask.so`` in ``csrc/mmask``."""
+    if force or mmask_is_stale():
+        _compile(MMASK_SOURCES, MMASK_LIB, MMASK_STAMP, mmask_digest, verbose)
     if force or select_is_stale():
         _compile(SELECT_SOURCES, SELECT_LIB, SELECT_STAMP, select_digest, verbose)
     if force or is_stale():

@@ -58,7 +58,11 @@ _MUJOCO_REQUIRED = ("solver", "iterations", "ls_iterations")
 # fit_frames: first (default) | strided | diverse -- which n_fit_frames rows of the prepared series calibrate the offsets: the first
 # ones (the reference), every (candidates / n)-th candidate, or the frames whose pairwise keypoint distances differ most (greedy
 # farthest-point selection on the GPU); strided and diverse pass over every frame that a preparation stage marked, hand the rows
-# to fit_offsets in ascending time order and write <fit file>.frames.json next to the fit file, read from the caller's config)
+# to fit_offsets in ascending time order and write <fit file>.frames.json next to the fit file, read from the caller's config;
+# offset_mask: off (default) | observed -- the offset phase of fit_offsets sums over the keypoints that were observed (kp_gap == 0)
+# and leaves filled values out, the pose phase still sees the filled series; needs fill_missing; writes <fit file>.offsets.json with
+# the observed count of every keypoint; with it fit_frames_min_observed (q in (0, 1], default 1.0 = today's rule) lets strided and
+# diverse take a frame of which at least ceil(q K) keypoints are observed; read from the caller's config)
 _STAC_EXTENSIONS = ("solver", "lanes_per_chain", "device", "time_indices", "fit_frames_per_clip", "reference_marker_order", "gather", "gather_max_bytes", "lm_maxiter", "postprocess", "fill_missing",
                     "reject_outliers", "outlier_window", "outlier_nsigma", "outlier_min_dev", "report", "report_quantiles", "report_worst",
                     "smooth", "smooth_window", "smooth_order", "smooth_sigma",
@@ -66,7 +70,7 @@ _STAC_EXTENSIONS = ("solver", "lanes_per_chain", "device", "time_indices", "fit_
                     "repair_swaps", "swaps_nsigma", "swaps_min_dev", "swaps_min_bad",
                     "fill_donors", "fill_donors_triples",
                     "resample", "mocap_hz", "resample_hz", "resample_lobes", "resample_beta",
-                    "fit_frames")
+                    "fit_frames", "offset_mask", "fit_frames_min_observed")
 _MODEL_EXTENSIONS = ("KP_NAMES_LABEL3D_PATH",)
 
 
@@ -273,6 +277,29 @@ def fit_frames_options(stac) -> str:
     if not isinstance(mode, str) or mode not in FIT_FRAMES_MODES:
         raise ConfigError(f"stac.fit_frames must be first, strided or diverse, not {mode!r}")
     return mode
+
+
+OFFSET_MASK_DEFAULTS = {"fit_frames_min_observed": 1.0}
+# the one text of run_stac's pre-flight and of main._offset_mask_mode
+OFFSET_MASK_NEEDS_FILL = ("stac.offset_mask = observed reads which keypoint values are observations from kp_gap, the mark of "
+                          "stac.fill_missing: set stac.fill_missing to linear or hold as well")
+
+
+def offset_mask_options(stac) -> tuple:
+    """``stac.offset_mask`` and ``stac.fit_frames_min_observed`` out of a ``stac`` mapping -> (mode, q), absent keys at their defaults.
+    ``ConfigError`` for anything else than off | observed (a bare YAML ``off`` arrives as False), for a q that is not a number in
+    (0, 1], and for a q other than 1.0 with the mask off: only the masked offset phase can take a frame with filled keypoints."""
+    mode = _switch(stac, "offset_mask")
+    if not isinstance(mode, str) or mode not in ("off", "observed"):
+        raise ConfigError(f"stac.offset_mask must be off or observed, not {mode!r}")
+    q = stac.get("fit_frames_min_observed", OFFSET_MASK_DEFAULTS["fit_frames_min_observed"])
+    q = OFFSET_MASK_DEFAULTS["fit_frames_min_observed"] if q is None else q
+    if isinstance(q, bool) or not isinstance(q, (int, float)) or not math.isfinite(q) or not 0 < q <= 1:
+        raise ConfigError(f"stac.fit_frames_min_observed must be a number in (0, 1], not {q!r}")
+    if mode == "off" and float(q) != 1.0:
+        raise ConfigError(f"stac.fit_frames_min_observed = {q!r} is honoured only with stac.offset_mask = observed: without the mask the "
+                          "offset phase fits filled keypoints like observed ones, so it must stay 1.0")
+    return mode, float(q)
 
 
 REPORT_DEFAULTS = {"report_quantiles": (500, 900, 990), "report_worst": 10}
@@ -535,7 +562,7 @@ def validate_config(cfg: dict) -> ConfigNode:
     postprocess_options(stac)
     for key, options in (("fill_missing", fill_missing_options), ("reject_outliers", outlier_options), ("report", report_options),
                          ("smooth", smooth_options), ("reject_pairwise", pairwise_options), ("repair_swaps", swaps_options),
-                         ("fill_donors", donor_options), ("resample", resample_options)):
+                         ("fill_donors", donor_options), ("resample", resample_options), ("offset_mask", offset_mask_options)):
         if isinstance(stac.get(key), bool):  # the file that is written with a result says off / on, not the boolean
             stac[key] = _switch(stac, key)
         options(stac)

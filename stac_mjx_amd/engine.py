@@ -16,7 +16,7 @@ import torch
 
 from .abi import (ABI_SYMBOLS, StacHipError, StacModelTables, StacQParams, _f32p, _i32p, _ptr, _u8p, check, declare,  # noqa: F401
                   hip_error, last_error, stream_ptr)
-from .build import LIB, SELECT_LIB, SELECT_STAMP, STAMP, select_digest, source_digest
+from .build import LIB, MMASK_LIB, MMASK_STAMP, SELECT_LIB, SELECT_STAMP, STAMP, mmask_digest, select_digest, source_digest
 
 ABI_VERSION = 3  # include/stac_hip.h: STAC_HIP_ABI_VERSION
 SOLVERS = {"pg": 0, "lm": 1}  # STAC_SOLVER_PG (the reference's algorithm, parity mode) / STAC_SOLVER_LM
@@ -73,6 +73,37 @@ def load_select_library(path: Path | None = None):
     return lib
 
 
+_MMASK_LIB = None
+
+
+def load_mmask_library(path: Path | None = None):
+    """Load ``libstac_mmask.so`` (csrc/mmask: the offset phase on observed keypoints only, ``stac.offset_mask``) with every
+    prototype of ``abi.MMASK_PROTOTYPES`` declared; raises if it has not been built or was built from other sources, like
+    ``load_library``."""
+    global _MMASK_LIB
+    if _MMASK_LIB is not None and path is None:
+        return _MMASK_LIB
+    p = Path(path) if path else MMASK_LIB
+    if not p.exists():
+        raise StacHipError(f"HIP extension not built: {p} is missing (run `python -m stac_mjx_amd.build`)")
+    if p == MMASK_LIB and MMASK_STAMP.exists() and MMASK_STAMP.read_text().strip() != mmask_digest():
+        raise StacHipError(f"{p} was built from other sources than the ones in this tree (stamp {MMASK_STAMP.name} differs): "
+                           "rebuild with `python -m stac_mjx_amd.build`")
+    from .abi import MMASK_PROTOTYPES
+
+    lib = declare(C.CDLL(str(p)), MMASK_PROTOTYPES)
+    if path is None:
+        _MMASK_LIB = lib
+    return lib
+
+
+def mmask_check(lib, what, rc):
+    """``rc`` of an entry point of ``libstac_mmask.so``, a status or a size: negative is an error, anything else is returned."""
+    if rc < 0:
+        raise StacHipError(f"{what}: libstac_mmask error {rc}: {lib.stac_mmask_last_error().decode('utf-8', 'replace')}")
+    return rc
+
+
 def _host_u8(a, n):
     a = np.ascontiguousarray(np.asarray(a).astype(np.uint8)).reshape(-1)
     if a.size != n:
@@ -103,6 +134,7 @@ class Engine:
         self.phase_params = StacQParams(float(tol), int(lm_maxiter if solver == "lm" else maxiter), int(maxls),
                                         int(lanes_per_chain), SOLVERS[solver], float(lm_lambda0))
         self.solver = solver
+        self._site_bodyid_host, self._site_bodyid = np.array(tables.site_bodyid, dtype=np.int32), None  # (m_partial_masked puts it on the device)
         t = StacModelTables()
         t.nbody, t.njnt, t.nq, t.nsite = tables.nbody, tables.njnt, tables.nq, tables.nsite
         keep = {}
@@ -263,3 +295,62 @@ class Engine:
 
     def m_opt(self, kp, q, initial_offsets, is_regularized, reg_coef):
         return self.m_finish(self.m_partial(kp, q), initial_offsets, is_regularized, reg_coef)
+
+    # -- the offset phase on observed keypoints only (csrc/mmask, DESIGN.md "Offsets from observed keypoints") -----------------
+    def m_partial_masked(self, kp, xpos, xquat, valid):
+        """``stac_mmask_partial``: kp [T, 3K], xpos [T, nbody, 3] and xquat [T, nbody, 4] (``fk`` of the frames' poses) and valid
+        [T, K] (non-zero = observed) -> partial [4K + 2]: s [K, 3], the observed counts n [K], z2 and T.  A keypoint value that
+        is not observed takes no part, whatever it holds."""
+        lib = load_mmask_library()
+        kp = self._dev(kp).reshape(-1, 3 * self.K)
+        T = kp.shape[0]
+        xpos = self._dev(xpos).reshape(-1, self.nbody, 3)
+        xquat = self._dev(xquat).reshape(-1, self.nbody, 4)
+        valid = valid if isinstance(valid, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(valid))
+        valid = (valid.to(self.device) != 0).to(torch.uint8).contiguous()
+        if xpos.shape[0] != T or xquat.shape[0] != T or tuple(valid.shape) != (T, self.K):
+            raise ValueError(f"m_partial_masked: kp has {T} frames of {self.K} keypoints, but xpos is {tuple(xpos.shape)}, xquat "
+                             f"{tuple(xquat.shape)} and valid {tuple(valid.shape)}")
+        if self._site_bodyid is None:
+            self._site_bodyid = torch.as_tensor(self._site_bodyid_host).to(self.device)
+        nbytes = int(mmask_check(lib, "stac_mmask_workspace", lib.stac_mmask_workspace(T, self.K)))
+        ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=self.device)
+        partial = torch.empty(4 * self.K + 2, dtype=torch.float32, device=self.device)
+        # the workspace is a temporary of torch's stream-ordered caching allocator (see set_site_pos): no host sync
+        with torch.cuda.device(self.device):
+            rc = lib.stac_mmask_partial(_ptr(kp), _ptr(xpos), _ptr(xquat), self.nbody, _ptr(self._site_bodyid), _ptr(valid), T, self.K,
+                                        _ptr(ws), nbytes, _ptr(partial), self._stream())
+        mmask_check(lib, "stac_mmask_partial", rc)
+        return partial
+
+    def m_finish_masked(self, partial, initial_offsets, is_regularized, reg_coef):
+        """``stac_mmask_finish`` of a (summed) partial [4K + 2] -> (offsets [K, 3], err [1], n [K] int32: the observed counts)."""
+        lib = load_mmask_library()
+        partial = self._dev(partial).reshape(-1)
+        if partial.shape[0] != 4 * self.K + 2:
+            raise ValueError(f"m_finish_masked: partial must have {4 * self.K + 2} words, got {partial.shape[0]}")
+        m0 = self._dev(initial_offsets).reshape(self.K, 3)
+        d = self._dev(is_regularized).reshape(self.K, 3)
+        out = torch.empty((self.K, 3), dtype=torch.float32, device=self.device)
+        err = torch.empty(1, dtype=torch.float32, device=self.device)
+        n = torch.empty(self.K, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = lib.stac_mmask_finish(_ptr(partial), self.K, _ptr(m0), _ptr(d), C.c_float(float(reg_coef)), _ptr(out), _ptr(err), _ptr(n),
+                                       self._stream())
+        mmask_check(lib, "stac_mmask_finish", rc)
+        return out, err, n
+
+    def fk_bodies(self, q):
+        """``(xpos [T, nbody, 3], xquat [T, nbody, 4])`` of the poses ``q`` [T, nq] for ``m_partial_masked`` (``stac_fk``).  No pose at all
+        (a rank of a sharded fit that owns no sampled frame) is two empty tensors: ``stac_fk`` takes no empty batch."""
+        q = self._dev(q).reshape(-1, self.nq)
+        if q.shape[0] == 0:
+            return (torch.empty((0, self.nbody, 3), dtype=torch.float32, device=self.device),
+                    torch.empty((0, self.nbody, 4), dtype=torch.float32, device=self.device))
+        fk = self.fk(q, want=("xpos", "xquat"))
+        return fk["xpos"], fk["xquat"]
+
+    def m_opt_masked(self, kp, q, valid, initial_offsets, is_regularized, reg_coef):
+        """``m_opt`` on observed keypoints only: the kinematics of ``q`` (``stac_fk``), the masked sums, the closed form."""
+        xpos, xquat = self.fk_bodies(q)
+        return self.m_finish_masked(self.m_partial_masked(kp, xpos, xquat, valid), initial_offsets, is_regularized, reg_coef)

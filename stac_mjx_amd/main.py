@@ -9,8 +9,8 @@ from pathlib import Path
 import numpy as np
 
 from . import dist, io, utils
-from .config import (DONORS_NEED_FILL, GATHER_NONE_CONTINUOUS, PAIRWISE_NEEDS_FILL, POSTPROCESS_GPU_MARKER_ORDER, RESAMPLE_SHARDED, compose_config,
-                     donor_options, fill_missing_options, fit_frames_options, outlier_options, pairwise_options, postprocess_options, report_options, resample_options,
+from .config import (DONORS_NEED_FILL, GATHER_NONE_CONTINUOUS, OFFSET_MASK_NEEDS_FILL, PAIRWISE_NEEDS_FILL, POSTPROCESS_GPU_MARKER_ORDER, RESAMPLE_SHARDED, compose_config,
+                     donor_options, fill_missing_options, fit_frames_options, offset_mask_options, outlier_options, pairwise_options, postprocess_options, report_options, resample_options,
                      smooth_options, swaps_candidates, swaps_options)
 from .stac import Stac
 
@@ -57,6 +57,11 @@ def run_stac(cfg, kp_data, kp_names, base_path=None, *, setup=None, device=None)
     instead of its first ones -- even steps, or the frames whose pairwise keypoint distances differ most, chosen on the GPU -- never
     on a frame that a preparation stage marked, and writes the choice as ``<fit file>.frames.json`` (DESIGN.md "Choosing calibration
     frames"); more ``n_fit_frames`` than frames, or than usable frames, is a ``ValueError``.
+    ``stac.offset_mask: observed`` (needs ``fill_missing``) fits the offsets to observed keypoints only: the offset phase of
+    ``fit_offsets`` leaves out every value with ``kp_gap > 0``, on the GPU, while the pose phase still sees the filled series, and
+    ``<fit file>.offsets.json`` lists how many sampled frames observed each keypoint (DESIGN.md "Offsets from observed keypoints").
+    With it ``stac.fit_frames_min_observed: q`` lets ``strided`` / ``diverse`` take a frame of which at least ``ceil(q K)`` keypoints
+    are observed (default 1.0: all of them).
     """
     base_path = Path.cwd() if base_path is None else Path(base_path)
     kp_data = np.asarray(kp_data)
@@ -75,7 +80,7 @@ def run_stac(cfg, kp_data, kp_names, base_path=None, *, setup=None, device=None)
     pre.check_run(dist.world()[1])
     series = _prepare_series(stac, cfg, kp_data, pre)
     if not cfg.stac.skip_fit_offsets:
-        fit_offsets_path = _run_fit(stac, cfg, series, fit_offsets_path, pre.report, pre.fit_frames)
+        fit_offsets_path = _run_fit(stac, cfg, series, fit_offsets_path, pre.report, pre.fit_frames, pre.offset_mask, pre.min_observed)
     else:
         print("Skipping fit_offsets. To change this behavior, set cfg.stac.skip_fit_offsets to False.")
     if cfg.stac.skip_ik_only:
@@ -84,17 +89,23 @@ def run_stac(cfg, kp_data, kp_names, base_path=None, *, setup=None, device=None)
     return _run_ik(stac, series, fit_offsets_path, ik_only_path, pre, start)
 
 
-def _run_fit(stac, cfg, series, fit_offsets_path, report, fit_frames="first") -> Path:
+def _run_fit(stac, cfg, series, fit_offsets_path, report, fit_frames="first", offset_mask="off", min_observed=1.0) -> Path:
     """``fit_offsets`` on ``n_fit_frames`` rows of the series -- the first ones, or with ``stac.fit_frames`` those of
-    ``_select_fit_frames`` in ascending time order -- and the fit file -> the name the file really has."""
+    ``_select_fit_frames`` in ascending time order -- and the fit file -> the name the file really has.  With ``stac.offset_mask:
+    observed`` the same rows of ``kp_gap == 0`` go along as the ``valid`` of the offset phase."""
     rows = info = None
+    masked = offset_mask == "observed"
     if fit_frames == "first":
         kps = series.kp_data[: cfg.stac.n_fit_frames]
     else:
-        rows, info = _select_fit_frames(stac, cfg, series, fit_frames)
+        rows, info = _select_fit_frames(stac, cfg, series, fit_frames, min_observed if masked else None)
         kps = series.kp_data[rows]
     print(f"Running fit. Mocap data shape: {kps.shape}")
-    fit_data = stac.fit_offsets(kps)
+    if masked:
+        gap = np.asarray(series.marks["kp_gap"])  # (the pre-flight refused the mask without fill_missing)
+        fit_data = stac.fit_offsets(kps, valid=(gap[: cfg.stac.n_fit_frames] if rows is None else gap[rows]) == 0)
+    else:
+        fit_data = stac.fit_offsets(kps)
     if rows is None:
         series.attach(fit_data, 0, fit_data.kp_data.shape[0])  # (the rows of the fit file are the first rows of the series, in order)
     else:
@@ -104,23 +115,54 @@ def _run_fit(stac, cfg, series, fit_offsets_path, report, fit_frames="first") ->
     fit_offsets_path = _write_result(stac, cfg, fit_data, fit_offsets_path, report, writes)
     if rows is not None and writes:
         _write_frames(fit_offsets_path, rows, info)
+    if masked and writes and stac.offset_counts is not None:  # (None: N_ITERS = 0, no offset phase ran)
+        _write_offset_counts(fit_offsets_path, stac._kp_names, stac.offset_counts)
     print(f"saved fit to {fit_offsets_path}", flush=True)
     return fit_offsets_path
 
 
-def _select_fit_frames(stac, cfg, series, mode):
+def min_observed_count(q: float, K: int) -> int:
+    """``ceil(q K)``: how many of a frame's K keypoints ``stac.fit_frames_min_observed: q`` wants observed (the product is rounded
+    to nine decimals first: 0.7 * 10 is 7, not the 7.000000000000001 of its float product)."""
+    import math
+
+    return int(math.ceil(round(float(q) * int(K), 9)))
+
+
+def fit_frame_exclude(kp_gap, kp_swapped, q: float) -> np.ndarray:
+    """The ``exclude`` [T] of ``Stac.select_frames`` under ``stac.offset_mask: observed``: a frame is a candidate iff at least
+    ``ceil(q K)`` of its keypoints have ``kp_gap == 0`` and it carries no ``kp_swapped`` mark (None: the stage was off)."""
+    gap = np.asarray(kp_gap)
+    T, K = gap.shape
+    exclude = np.count_nonzero(gap == 0, axis=1) < min_observed_count(q, K)
+    if kp_swapped is not None:
+        exclude |= (np.asarray(kp_swapped).reshape(T, -1) != 0).any(axis=1)
+    return exclude
+
+
+def _select_fit_frames(stac, cfg, series, mode, min_observed=None):
     """``stac.fit_frames: strided | diverse`` -> (the ``n_fit_frames`` chosen rows of the prepared series, ascending, and the ``info``
     of ``Stac.select_frames``).  Every rank computes the selection itself: same bits.  A frame that carries a mark of any
-    preparation stage (``series.marks``) is no candidate: the offsets are calibrated on observed keypoints only."""
+    preparation stage (``series.marks``) is no candidate: the offsets are calibrated on observed keypoints only.  ``min_observed``
+    (``stac.fit_frames_min_observed`` under ``stac.offset_mask: observed``, else None): the candidates are those of
+    ``fit_frame_exclude`` instead, since the masked offset phase leaves a frame's filled keypoints out itself."""
     n, T = int(cfg.stac.n_fit_frames), series.kp_data.shape[0]
-    exclude = np.zeros(T, bool)
-    for mark in series.marks.values():
-        exclude |= (np.asarray(mark).reshape(T, -1) != 0).any(axis=1)
+    if min_observed is None:
+        exclude = np.zeros(T, bool)
+        for mark in series.marks.values():
+            exclude |= (np.asarray(mark).reshape(T, -1) != 0).any(axis=1)
+        why = "carry no mark of a preparation stage"
+    else:
+        K = series.kp_data.shape[1] // 3
+        exclude = fit_frame_exclude(series.marks["kp_gap"], series.marks.get("kp_swapped"), min_observed)
+        why = (f"have at least {min_observed_count(min_observed, K)} of their {K} keypoints observed (stac.fit_frames_min_observed = "
+               f"{min_observed:g}) and no swap repaired")
     n_cand = int(T - np.count_nonzero(exclude))
     if n_cand < n:
-        raise ValueError(f"stac.fit_frames = {mode}: n_fit_frames = {n}, but only {n_cand} of the {T} frames carry no mark of a "
-                         "preparation stage")
+        raise ValueError(f"stac.fit_frames = {mode}: n_fit_frames = {n}, but only {n_cand} of the {T} frames {why}")
     rows, info = stac.select_frames(series.kp_data, n, mode, exclude=exclude)
+    if min_observed is not None:
+        info["min_observed"] = float(min_observed)
     if info["n_selected"] < n:
         raise ValueError(f"stac.fit_frames = {mode}: n_fit_frames = {n}, but the selection stopped after {info['n_selected']} frames: "
                          "every other usable frame equals one of them (or has a coordinate that is not finite)")
@@ -140,9 +182,31 @@ def _write_frames(fit_offsets_path, rows, info) -> Path:
 
     path = frames_path(fit_offsets_path)
     r2 = [None if not np.isfinite(v) else float(v) for v in info["radius2"]]
-    path.write_text(json.dumps({"mode": info["mode"], "indices": [int(i) for i in rows], "order": [int(i) for i in info["order"]],
-                                "radius2": r2}, indent=1) + "\n")
+    out = {"mode": info["mode"], "indices": [int(i) for i in rows], "order": [int(i) for i in info["order"]], "radius2": r2}
+    if "min_observed" in info:  # (stac.offset_mask: observed -- the fit_frames_min_observed that chose the candidates)
+        out["min_observed"] = float(info["min_observed"])
+    path.write_text(json.dumps(out, indent=1) + "\n")
     print(f"fit_frames: wrote {path}", flush=True)
+    return path
+
+
+def offset_counts_path(fit_offsets_path) -> Path:
+    """``fit.h5`` -> ``fit.h5.offsets.json`` (of the name the fit file really has: ``io.resolve_output_path``)."""
+    p = io.resolve_output_path(fit_offsets_path)
+    return p.with_name(p.name + ".offsets.json")
+
+
+def _write_offset_counts(fit_offsets_path, kp_names, counts) -> Path:
+    """What ``stac.offset_mask: observed`` fitted the offsets to, as JSON next to the fit file: the keypoint names, per keypoint the
+    number of sampled frames of the last calibration iteration that observed it, the number of sampled frames, and the keypoints
+    that none observed (their offsets follow the regularisation, or stay as they were where there is none)."""
+    import json
+
+    path = offset_counts_path(fit_offsets_path)
+    n = [int(v) for v in counts["n"]]
+    path.write_text(json.dumps({"kp_names": list(kp_names), "n": n, "n_sampled": int(counts["n_sampled"]),
+                                "never_observed": [str(kp_names[k]) for k, v in enumerate(n) if v == 0]}, indent=1) + "\n")
+    print(f"offset_mask: wrote {path}", flush=True)
     return path
 
 
@@ -269,6 +333,7 @@ class _Preflight:
         self.smooth = _smooth_mode(self.cfg)
         self.resample = _resample_mode(self.cfg)
         self.fit_frames = fit_frames_options(stac)
+        self.offset_mask, self.min_observed = _offset_mask_mode(self.cfg)
         if self.fit_frames != "first" and not stac.skip_fit_offsets:  # (first keeps the reference's slice, which takes what there is)
             n = int(stac.n_fit_frames)
             if n > self.n_frames:
@@ -491,6 +556,16 @@ def _fill_donors_mode(cfg) -> tuple:
     if mode != "off" and _fill_missing_mode(cfg) == "off":
         raise ValueError(DONORS_NEED_FILL)
     return mode, n_triples
+
+
+def _offset_mask_mode(cfg) -> tuple:
+    """``stac.offset_mask``: "off" (default) | "observed" -> (mode, ``stac.fit_frames_min_observed``).  ``ValueError`` for a bad value
+    of either key, for a ``fit_frames_min_observed`` other than 1.0 with the mask off, and for ``observed`` with ``fill_missing`` off:
+    ``kp_gap``, the mark of that stage, is what says which values are observations."""
+    mode, q = offset_mask_options(cfg.stac)
+    if mode != "off" and _fill_missing_mode(cfg) == "off":
+        raise ValueError(OFFSET_MASK_NEEDS_FILL)
+    return mode, q
 
 
 def _repair_swaps_mode(cfg, kp_names=None) -> tuple:

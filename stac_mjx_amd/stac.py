@@ -53,6 +53,7 @@ class Stac:
         self._timestep = s.tables.timestep
         self._renderer = None
         self.pair_stats = None  # the pairwise statistics of the last reject_pairwise / repair_swaps call (device tensors)
+        self.offset_counts = None  # fit_offsets(valid=...): the observed counts of the last calibration iteration
 
     # -- helpers ------------------------------------------------------------------------------------
     def _log(self, *a):
@@ -356,7 +357,7 @@ class Stac:
         return replace(data, qpos_raw=np.array([]), **host)
 
     # -- fit_offsets (stac.py:253-354) ------------------------------------------------------------------
-    def fit_offsets(self, kp_data, time_indices=None) -> StacData:
+    def fit_offsets(self, kp_data, time_indices=None, valid=None) -> StacData:
         """Alternate pose and offset optimisation.
 
         Default (the reference, ``stac.py:298-341``): ONE warm-started chain over all frames, carried across the
@@ -367,21 +368,38 @@ class Stac:
         iterations), the clips are sharded over the ranks and the offset phase all-reduces its 3K + 2 partial sums.
 
         ``time_indices`` (optional) overrides the PRNGKey(0) frame sample of the offset phase.
+
+        ``valid`` (optional, bool [T, K]; engine extension, DESIGN.md "Offsets from observed keypoints"): which keypoint values
+        are observations.  The offset phase of every calibration iteration then sums over the observed keypoints of the sampled
+        rows only (``Engine.m_partial_masked`` / ``m_finish_masked``; under ``fit_frames_per_clip`` the all-reduce carries their
+        4K + 2 partial sums), logs the keypoints that no sampled row observed, and leaves the counts of the last iteration in
+        ``self.offset_counts`` (``n`` [K] and ``n_sampled``).  The pose phase sees ``kp_data`` as it is, filled values included.
         """
         cfgm = self.cfg.model
         eng = self.engine
         fpc = int(self.cfg.stac.get("fit_frames_per_clip", 0) or 0)
         kp_np = np.asarray(kp_data, dtype=np.float32)
+        valid_np = None
+        if valid is not None:
+            valid_np = np.asarray(valid)
+            if valid_np.dtype != np.bool_ or valid_np.shape != (kp_np.shape[0], len(self._kp_names)):
+                raise ValueError(f"fit_offsets: valid must be a bool array [{kp_np.shape[0]}, {len(self._kp_names)}], one entry per frame "
+                                 f"and keypoint, got {valid_np.dtype} {valid_np.shape}")
         if fpc > 0:
             kp_np = utils.batch_kp_data(kp_np, fpc, continuous=False)  # [C, F, 3K]; a ragged tail is dropped
             if kp_np.shape[0] == 0:
                 raise ValueError(f"fit_frames_per_clip = {fpc} exceeds the {len(kp_data)} fit frames")
+            if valid_np is not None:  # (the rows that batch_kp_data kept, cut the same way)
+                valid_np = valid_np[: kp_np.shape[0] * fpc].reshape(kp_np.shape[0], fpc, -1)
         else:
             kp_np = kp_np[None]
+            valid_np = None if valid_np is None else valid_np[None]
         n_clips, n_per = kp_np.shape[0], kp_np.shape[1]
         n = n_clips * n_per
         lo, hi = dist.shard_range(n_clips) if fpc > 0 else (0, 1)
         kp = torch.as_tensor(kp_np[lo:hi]).to(eng.device)
+        valid_dev = None if valid_np is None else torch.as_tensor(np.ascontiguousarray(valid_np[lo:hi])).to(eng.device).reshape(-1, valid_np.shape[-1])
+        self.offset_counts = None
         self._offsets = eng.get_site_pos().clone()
         do_root = self.setup.do_root_opt
         if self._root_kp_idx == -1:
@@ -410,10 +428,22 @@ class Stac:
                 break
             # offset phase (compute_stac.py:107-167): regularised toward the PREVIOUS iterate (stac.py:317-328)
             nq = self.setup.tables.nq
-            partial = eng.m_partial(kp.reshape(-1, kp.shape[-1])[idx], res["qpos"].reshape(-1, nq)[idx])
+            kp_s, q_s = kp.reshape(-1, kp.shape[-1])[idx], res["qpos"].reshape(-1, nq)[idx]
+            if valid_dev is None:
+                partial = eng.m_partial(kp_s, q_s)
+            else:  # observed keypoints only: the kinematics of the sampled poses, then the masked sums
+                xpos_s, xquat_s = eng.fk_bodies(q_s)
+                partial = eng.m_partial_masked(kp_s, xpos_s, xquat_s, valid_dev[idx])
             if fpc > 0:
-                partial = dist.all_reduce_partial(partial)  # the one data-path collective: 3K + 2 floats
-            new_off, err = eng.m_finish(partial, self._offsets, is_reg, float(cfgm.M_REG_COEF))
+                partial = dist.all_reduce_partial(partial)  # the one data-path collective: 3K + 2 floats (4K + 2 with valid)
+            if valid_dev is None:
+                new_off, err = eng.m_finish(partial, self._offsets, is_reg, float(cfgm.M_REG_COEF))
+            else:
+                new_off, err, n_obs = eng.m_finish_masked(partial, self._offsets, is_reg, float(cfgm.M_REG_COEF))
+                self.offset_counts = {"n": n_obs.cpu().numpy(), "n_sampled": int(tix.size)}
+                never = [self._kp_names[k] for k in np.flatnonzero(self.offset_counts["n"] == 0)]
+                self._log(f"offset phase on observed keypoints: {len(never)} of {len(self._kp_names)} keypoints were observed in none of the "
+                          f"{tix.size} sampled frames" + (": " + ", ".join(never) + " (their offsets follow the regularisation alone)" if never else ""))
             self._log(f"Final residual error of {float(err)}")
             eng.set_site_pos(new_off)
             self._offsets = new_off

@@ -105,7 +105,11 @@ class StacCore:
                      ls_evals=int(c[1]), grad_evals=int(c[2]))
         return mjx_data, OptStep(params=params[0], state=st)
 
-    def m_opt(self, mjx_model, mjx_data, keypoints, q, initial_offsets, is_regularized, reg_coef, site_idxs=None):
-        """``StacCore.m_opt`` (``stac_core.py:237-275``)."""
+    def m_opt(self, mjx_model, mjx_data, keypoints, q, initial_offsets, is_regularized, reg_coef, site_idxs=None, valid=None):
+        """``StacCore.m_opt`` (``stac_core.py:237-275``).  ``valid`` ([T, K], engine extension): the offsets are fitted to the
+        keypoint values that it marks as observed alone (``Engine.m_opt_masked``); None = the reference's, every value."""
+        if valid is not None:
+            off, err, _ = self.engine.m_opt_masked(keypoints, q, valid, initial_offsets, is_regularized, float(reg_coef))
+            return MOptResult(params=off, error=err[0])
         off, err = self.engine.m_opt(keypoints, q, initial_offsets, is_regularized, float(reg_coef))
         return MOptResult(params=off, error=err[0])

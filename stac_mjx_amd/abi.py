@@ -123,6 +123,13 @@ MMASK_PROTOTYPES = {
     "stac_mmask_partial": (i32, [vp, vp, vp, i32, vp, vp, i64, i32, vp, i64, vp, vp]),
     "stac_mmask_finish": (i32, [vp, i32, vp, vp, f32, vp, vp, vp, vp]),
 }
+# every function csrc/seam/stac_seam.h declares (libstac_seam.so, the companion library of stac.seam_report), in its order; the
+# quat_cols of stac_seam_steps are HOST memory: an int32 pointer, not a device address
+SEAM_PROTOTYPES = {
+    "stac_seam_last_error": (C.c_char_p, []),
+    "stac_seam_last_error_code": (i32, []),
+    "stac_seam_steps": (i32, [vp, i64, i32, i64, _i32p, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+}
 
 
 class StacHipError(RuntimeError):

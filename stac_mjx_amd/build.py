@@ -1,5 +1,6 @@
 """Builds the HIP extension in-tree: ``stac_mjx_amd/csrc/libstac_hip.so`` and its companions
-``stac_mjx_amd/csrc/select/libstac_select.so`` and ``stac_mjx_amd/csrc/mmask/libstac_mmask.so`` (gfx950 only).
+``stac_mjx_amd/csrc/select/libstac_select.so``, ``stac_mjx_amd/csrc/mmask/libstac_mmask.so`` and
+``stac_mjx_amd/csrc/seam/libstac_seam.so`` (gfx950 only).
 
 ``hipcc`` cross-compiles without a GPU.  ``-ffp-contract=off -fno-fast-math`` is part of the
 arithmetic contract of the kernels (bit-identical to the CPU oracle), not a tuning choice.
@@ -51,6 +52,12 @@ MMASK_LIB = MMASK_DIR / "libstac_mmask.so"
 MMASK_STAMP = MMASK_DIR / "libstac_mmask.so.stamp"
 MMASK_SOURCES = sorted(MMASK_DIR.glob("*.hip"))
 MMASK_HEADERS = sorted(MMASK_DIR.glob("*.hpp")) + sorted(MMASK_DIR.glob("*.h"))
+# The companion library of stac.seam_report (csrc/seam/: the pose steps of a fitted series), built the same way.
+SEAM_DIR = CSRC / "seam"
+SEAM_LIB = SEAM_DIR / "libstac_seam.so"
+SEAM_STAMP = SEAM_DIR / "libstac_seam.so.stamp"
+SEAM_SOURCES = sorted(SEAM_DIR.glob("*.hip"))
+SEAM_HEADERS = sorted(SEAM_DIR.glob("*.hpp")) + sorted(SEAM_DIR.glob("*.h"))
 
 
 def source_digest() -> str:
@@ -87,6 +94,17 @@ def mmask_digest() -> str:
     return h.hexdigest()
 
 
+def seam_digest() -> str:
+    """``source_digest`` of ``libstac_seam.so``."""
+    import hashlib
+
+    h = hashlib.sha256(" ".join(FLAGS).encode())
+    for p in SEAM_SOURCES + SEAM_HEADERS + HEADERS:
+        h.update(p.name.encode())
+        h.update(p.read_bytes())
+    return h.hexdigest()
+
+
 def is_stale() -> bool:
     if not LIB.exists() or not STAMP.exists():
         return True
@@ -99,6 +117,10 @@ def select_is_stale() -> bool:
 
 def mmask_is_stale() -> bool:
     return not MMASK_LIB.exists() or not MMASK_STAMP.exists() or MMASK_STAMP.read_text().strip() != mmask_digest()
+
+
+def seam_is_stale() -> bool:
+    return not SEAM_LIB.exists() or not SEAM_STAMP.exists() or SEAM_STAMP.read_text().strip() != seam_digest()
 
 
 def _compile(sources, lib, stamp, digest, verbose):
@@ -116,8 +138,10 @@ def _compile(sources, lib, stamp, digest, verbose):
 
 
 def build_extension(force: bool = False, verbose: bool = False) -> Path:
-    """Builds what is stale (``force``: all three libraries) -> the path of ``libstac_hip.so``; ``libstac_select.so`` stands beside
-    it in ``csrc/select`` and ``libstac_mmask.so`` in ``csrc/mmask``."""
+    """Builds what is stale (``force``: all four libraries) -> the path of ``libstac_hip.so``; ``libstac_select.so`` stands beside
+    it in ``csrc/select``, ``libstac_mmask.so`` in ``csrc/mmask`` and ``libstac_seam.so`` in ``csrc/seam``."""
+    if force or seam_is_stale():
+        _compile(SEAM_SOURCES, SEAM_LIB, SEAM_STAMP, seam_digest, verbose)
     if force or mmask_is_stale():
         _compile(MMASK_SOURCES, MMASK_LIB, MMASK_STAMP, mmask_digest, verbose)
     if force or select_is_stale():

@@ -62,7 +62,10 @@ _MUJOCO_REQUIRED = ("solver", "iterations", "ls_iterations")
 # offset_mask: off (default) | observed -- the offset phase of fit_offsets sums over the keypoints that were observed (kp_gap == 0)
 # and leaves filled values out, the pose phase still sees the filled series; needs fill_missing; writes <fit file>.offsets.json with
 # the observed count of every keypoint; with it fit_frames_min_observed (q in (0, 1], default 1.0 = today's rule) lets strided and
-# diverse take a frame of which at least ceil(q K) keypoints are observed; read from the caller's config)
+# diverse take a frame of which at least ceil(q K) keypoints are observed; read from the caller's config;
+# seam_passes: 1 (default) .. 8 -- ik_only solves the clips behind the first again, P - 1 times, each warm-started from the pose
+# that the clip in front of it ended in, without root optimisation; seam_report: off (default) | on -- a <ik file>.seams.json with
+# the pose steps across and within the clips, measured on the GPU; both read from the caller's config)
 _STAC_EXTENSIONS = ("solver", "lanes_per_chain", "device", "time_indices", "fit_frames_per_clip", "reference_marker_order", "gather", "gather_max_bytes", "lm_maxiter", "postprocess", "fill_missing",
                     "reject_outliers", "outlier_window", "outlier_nsigma", "outlier_min_dev", "report", "report_quantiles", "report_worst",
                     "smooth", "smooth_window", "smooth_order", "smooth_sigma",
@@ -70,7 +73,8 @@ _STAC_EXTENSIONS = ("solver", "lanes_per_chain", "device", "time_indices", "fit_
                     "repair_swaps", "swaps_nsigma", "swaps_min_dev", "swaps_min_bad",
                     "fill_donors", "fill_donors_triples",
                     "resample", "mocap_hz", "resample_hz", "resample_lobes", "resample_beta",
-                    "fit_frames", "offset_mask", "fit_frames_min_observed")
+                    "fit_frames", "offset_mask", "fit_frames_min_observed",
+                    "seam_passes", "seam_report")
 _MODEL_EXTENSIONS = ("KP_NAMES_LABEL3D_PATH",)
 
 
@@ -300,6 +304,22 @@ def offset_mask_options(stac) -> tuple:
         raise ConfigError(f"stac.fit_frames_min_observed = {q!r} is honoured only with stac.offset_mask = observed: without the mask the "
                           "offset phase fits filled keypoints like observed ones, so it must stay 1.0")
     return mode, float(q)
+
+
+SEAM_MAX_PASSES = 8
+
+
+def seam_options(stac) -> tuple:
+    """``stac.seam_passes`` and ``stac.seam_report`` out of a ``stac`` mapping -> (passes, report on), absent keys (and keys without
+    a value) at their defaults 1 and off.  ``ConfigError`` for passes that are not an integer in 1 .. 8 and for anything else than
+    off | on (or the bool that a bare YAML off / on arrives as)."""
+    p = stac.get("seam_passes", 1)
+    p = checked_int(1 if p is None else p, "stac.seam_passes", ConfigError, 1, SEAM_MAX_PASSES)
+    mode = stac.get("seam_report", "off")
+    mode = "off" if mode is None or mode is False else ("on" if mode is True else mode)
+    if not isinstance(mode, str) or mode not in ("off", "on"):
+        raise ConfigError(f"stac.seam_report must be off or on, not {mode!r}")
+    return p, mode == "on"
 
 
 REPORT_DEFAULTS = {"report_quantiles": (500, 900, 990), "report_worst": 10}
@@ -567,6 +587,9 @@ def validate_config(cfg: dict) -> ConfigNode:
             stac[key] = _switch(stac, key)
         options(stac)
     fit_frames_options(stac)
+    if isinstance(stac.get("seam_report"), bool):  # (as above: the stored file says off / on)
+        stac["seam_report"] = "on" if stac["seam_report"] else "off"
+    seam_options(stac)
     return _wrap({"model": model, "stac": stac})
 
 

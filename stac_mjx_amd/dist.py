@@ -94,6 +94,33 @@ def gather_clips(local: torch.Tensor, n_total: int, dst: int = 0):
     return torch.cat([b[: hi - lo] for b, (lo, hi) in zip(bufs, sizes)], dim=0)
 
 
+def seam_neighbour(has_clips, rank: int) -> int:
+    """The rank whose last clip stands in front of ``rank``'s first one: the nearest earlier rank that owns a clip, -1 if there is
+    none (``rank`` then owns clip 0, or nothing).  ``has_clips``: one truth value per rank."""
+    for r in range(int(rank) - 1, -1, -1):
+        if has_clips[r]:
+            return r
+    return -1
+
+
+def exchange_seam_rows(last_row, nq: int, device) -> torch.Tensor | None:
+    """The one collective of a warm pass of ``Stac.ik_only`` (``stac.seam_passes``): every rank contributes the pose that its last
+    clip ended in (``last_row`` [nq] float32, None for a rank without clips) and a flag that says whether it has one, as ONE
+    all-gather of nq + 1 floats; -> the row of ``seam_neighbour``, bit for bit as its owner holds it, or None (no such rank, or no
+    process group)."""
+    if not is_dist():
+        return None
+    r, w = world()
+    mine = torch.zeros(nq + 1, dtype=torch.float32, device=device)
+    if last_row is not None:
+        mine[:nq] = last_row.reshape(nq)
+        mine[nq] = 1.0
+    parts = [torch.empty_like(mine) for _ in range(w)]
+    tdist.all_gather(parts, mine)
+    src = seam_neighbour((torch.stack(parts)[:, nq] != 0).cpu().tolist(), r)
+    return None if src < 0 else parts[src][:nq].clone()
+
+
 # ---- launcher helpers (bench.py --gpus N outside torchrun) ---------------------------------------------------------------------
 def visible_gpu_count(sysfs_root: str = "/sys/class/kfd/kfd/topology/nodes", environ=None) -> int:
     """GPUs this process would see, WITHOUT touching the HIP runtime (a launcher parent must never initialise the GPU:

@@ -11,7 +11,7 @@ import numpy as np
 from . import dist, io, utils
 from .config import (DONORS_NEED_FILL, GATHER_NONE_CONTINUOUS, OFFSET_MASK_NEEDS_FILL, PAIRWISE_NEEDS_FILL, POSTPROCESS_GPU_MARKER_ORDER, RESAMPLE_SHARDED, compose_config,
                      donor_options, fill_missing_options, fit_frames_options, offset_mask_options, outlier_options, pairwise_options, postprocess_options, report_options, resample_options,
-                     smooth_options, swaps_candidates, swaps_options)
+                     seam_options, smooth_options, swaps_candidates, swaps_options)
 from .stac import Stac
 
 
@@ -62,6 +62,10 @@ def run_stac(cfg, kp_data, kp_names, base_path=None, *, setup=None, device=None)
     ``<fit file>.offsets.json`` lists how many sampled frames observed each keypoint (DESIGN.md "Offsets from observed keypoints").
     With it ``stac.fit_frames_min_observed: q`` lets ``strided`` / ``diverse`` take a frame of which at least ``ceil(q K)`` keypoints
     are observed (default 1.0: all of them).
+    ``stac.seam_passes: P`` (1 .. 8, default 1) lets ``ik_only`` solve the clips behind the first ``P - 1`` times more, each
+    warm-started from the pose that the clip in front of it ended in, so that the clip borders stop carrying the jump of a cold start;
+    ``stac.seam_report: on`` measures the pose steps of the ik_only result on the GPU and writes them as ``<ik file>.seams.json``
+    (DESIGN.md "Warm-started clips and pose steps"); the ik_only file's stored config carries both keys.
     """
     base_path = Path.cwd() if base_path is None else Path(base_path)
     kp_data = np.asarray(kp_data)
@@ -239,7 +243,16 @@ def _run_ik(stac, series, fit_offsets_path, ik_only_path, pre, start):
     if pre.smooth is not None:  # (postprocess = gpu: _smooth_mode)
         _check_smooth_clip(pre.smooth, _smooth_clip_len(cfg, kp_data.shape[0]))
         post["smooth"] = pre.smooth
-    ik_data = stac.ik_only(kp_data, fit_data.offsets, gather=mode, **({"post": post} if pre.post_gpu else {}))
+    if seam_options(cfg.stac) != (pre.seam_passes, pre.seam_report):  # the ik_only file records what this run did at its clip borders
+        from .config import validate_config
+
+        stored = cfg.to_dict()
+        stored["stac"].update({"seam_passes": pre.seam_passes, "seam_report": "on" if pre.seam_report else "off"})
+        cfg = validate_config(stored)
+    extra = {"post": post} if pre.post_gpu else {}
+    if pre.seam_passes != 1:
+        extra["passes"] = pre.seam_passes
+    ik_data = stac.ik_only(kp_data, fit_data.offsets, gather=mode, **extra)
     if rank != 0 and not sharded and mode != "all":
         dist.barrier()  # this rank holds its own shard only: rank 0 post-processes and writes the gathered result
         if pre.resample is not None:
@@ -259,6 +272,8 @@ def _run_ik(stac, series, fit_offsets_path, ik_only_path, pre, start):
         # every rank writes ITS clips under a shard name (never a partial result under the full-run name; its report is of these
         # clips, shard reports are not merged); rank 0 adds the manifest that io.load_stac_result() reads the run back through
         shard = _write_result(stac, cfg, ik_data, io.shard_path(ik_only_path, rank, world_size), pre.report, True)
+        if pre.seam_report:  # (of this rank's clips, like its report)
+            _write_seams(stac, ik_data, shard, F)
         manifest = io.manifest_path(ik_only_path)
         if rank == 0:
             io.write_manifest(manifest, ik_only_path, world_size, n_clips, F)
@@ -267,10 +282,33 @@ def _run_ik(stac, series, fit_offsets_path, ik_only_path, pre, start):
               f"Finished in {(time.time() - start) / 60:.2f} minutes")
         return fit_offsets_path, manifest
     ik_only_path = _write_result(stac, cfg, ik_data, ik_only_path, pre.report, rank == 0)
+    if pre.seam_report and rank == 0:
+        _write_seams(stac, ik_data, ik_only_path, F)
     if pre.resample is not None:
         _write_resampled(stac, cfg, ik_data, ik_only_path, pre, rank == 0)
     print(f"Saved ik_only to {ik_only_path}. Finished in {(time.time() - start) / 60:.2f} minutes")
     return fit_offsets_path, ik_only_path
+
+
+def seams_path(ik_only_path) -> Path:
+    """``ik_only.h5`` -> ``ik_only.h5.seams.json`` (of the name the result file really has: ``io.resolve_output_path``)."""
+    p = io.resolve_output_path(ik_only_path)
+    return p.with_name(p.name + ".seams.json")
+
+
+def _write_seams(stac, ik_data, ik_only_path, clip_len) -> Path:
+    """``stac.seam_report: on``: the summary of ``Stac.seam_steps`` of the packaged ik_only result (clips of ``clip_len`` rows: a
+    continuous run is stitched by now) as JSON next to the result file, which does not change."""
+    import json
+
+    path = seams_path(ik_only_path)
+    if np.asarray(ik_data.qpos).shape[0] == 0:  # (a rank of a sharded run that owns no clip)
+        return path
+    summary = stac.seam_steps(ik_data, clip_len=clip_len)["summary"]
+    path.write_text(json.dumps(summary, indent=1) + "\n")
+    print(f"seam_report: {summary['n_seams']} seams, mean / max step across a clip border {summary['seam_mean']} / {summary['seam_max']}; "
+          f"wrote {path}", flush=True)
+    return path
 
 
 def resampled_path(ik_only_path, to_hz) -> Path:
@@ -334,6 +372,7 @@ class _Preflight:
         self.resample = _resample_mode(self.cfg)
         self.fit_frames = fit_frames_options(stac)
         self.offset_mask, self.min_observed = _offset_mask_mode(self.cfg)
+        self.seam_passes, self.seam_report = seam_options(stac)
         if self.fit_frames != "first" and not stac.skip_fit_offsets:  # (first keeps the reference's slice, which takes what there is)
             n = int(stac.n_fit_frames)
             if n > self.n_frames:

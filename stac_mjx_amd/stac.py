@@ -14,7 +14,8 @@ import numpy as np
 import torch
 
 from . import dist, prng, utils
-from .config import GATHER_NONE_CONTINUOUS, INT32_MAX, POSTPROCESS_GPU_MARKER_ORDER, checked_int, report_options, smooth_marker_order_refusal
+from .config import (GATHER_NONE_CONTINUOUS, INT32_MAX, POSTPROCESS_GPU_MARKER_ORDER, SEAM_MAX_PASSES, checked_int, report_options, seam_options,
+                     smooth_marker_order_refusal)
 from .engine import Engine
 from .fit_model import FitSetup, build_fit_setup
 from .io import StacData
@@ -70,12 +71,12 @@ class Stac:
             return e, 0.0, 0.0
         return e, float(np.mean(e)), float(np.std(e))
 
-    def _q_phase(self, kp, *, do_root_opt, q_init=None, want_outputs=True):
+    def _q_phase(self, kp, *, do_root_opt, q_init=None, want_outputs=True, out=None):
         s = self.setup
         return self.engine.q_phase(
             kp, part_masks=s.part_masks, trunk_kps=s.trunk_kps, root_kp_idx=max(s.root_kp_idx, 0),
             root_dims=s.root_dims, do_root_opt=do_root_opt, q_init=q_init, want_bodies=want_outputs,
-            want_markers=want_outputs)
+            want_markers=want_outputs, out=out)
 
     def _series_to_device(self, kp_data, what):
         """The whole series ``kp_data`` [T, 3K] as a float32 tensor on the engine's device."""
@@ -452,9 +453,13 @@ class Stac:
         return self._package_data(res, kp_np.reshape(kp_np.shape[0] * n_per, kp_np.shape[-1]), batched=fpc > 0)
 
     # -- ik_only (stac.py:356-454) --------------------------------------------------------------------------
-    def ik_only(self, kp_data, offsets, gather=None, *, post=None) -> StacData:
+    def ik_only(self, kp_data, offsets, gather=None, *, post=None, passes=None) -> StacData:
         """Inverse kinematics with fixed offsets; clips are independent chains, sharded over ranks.  ``gather`` (multi-GPU
         result placement: "rank0" | "all" | "none") overrides ``stac.gather`` for this call (run_stac resolves "auto").
+
+        ``passes`` (``stac.seam_passes``, engine extension, 1 .. 8; None: the config's, default 1 = every clip starts cold): the
+        clips behind the first are solved ``passes - 1`` times more, each warm-started from the pose that the clip in front of it
+        ended in (``_seam_passes``); every output is the last pass's.
 
         ``post`` (``stac.postprocess: gpu``, engine extension): ``{"continuous", "n_frames_per_clip", "infer_qvels"}`` as the fit
         file's config decided them.  The cross-fade stitch of ``utils.handle_edge_effects`` and the ``qvel`` of
@@ -463,6 +468,7 @@ class Stac:
         An optional ``post["smooth"]`` (``stac.smooth``: ``{"kind", "half_window", "order", "sigma"}``) smooths ``qpos`` per clip
         between the two; the ``StacData`` then carries ``qpos_raw`` and the kinematics of the smoothed pose."""
         eng = self.engine
+        passes = seam_options(self.cfg.stac)[0] if passes is None else checked_int(passes, "ik_only: passes", ValueError, 1, SEAM_MAX_PASSES)
         if post is not None:
             post = self._check_post(post, gather)
         tick = self._tick
@@ -478,6 +484,9 @@ class Stac:
             self._log("Missing or invalid ROOT_OPTIMIZATION_KEYPOINT, skipping root_optimization()")
         res = self._q_phase(kp, do_root_opt=self.setup.do_root_opt)
         tick("q_phase_and_fk_kernels_s")
+        if passes > 1:
+            self._seam_passes(res, kp, n_clips, lo, passes)
+            tick("seam_passes_s")
         if dist.is_dist():
             res, batched = self._gather(res, batched, n_clips, lo, hi, mode=gather)
             tick("gather_s")
@@ -492,6 +501,89 @@ class Stac:
         data = self._package_data(res, batched, batched=True, post=extra)
         tick("d2h_and_packing_s")
         return data
+
+    def _seam_passes(self, res, kp, n_clips, lo, passes):
+        """``stac.seam_passes``: pass p = 2 .. ``passes`` solves every clip but clip 0 again through ``Engine.q_phase``, without root
+        optimisation, from the pose that the clip in front of it ended in under pass p - 1: row F - 1 of that clip's ``qpos`` (F =
+        ``n_frames_per_clip``; the window of a continuous run has F + 10 rows and row F - 1 is still the frame in front of the next
+        window's first).  The warm starts are a copy taken before the launch, and the launch writes into the slices of ``res`` (the
+        outputs of pass 1, this rank's clips ``lo ..``) behind clip 0, which keeps its pass-1 result.  Multi-GPU: the clip in front of
+        a rank's first one lives on an earlier rank, ``dist.exchange_seam_rows`` brings its row (one all-gather per pass).  With one
+        clip there is nothing to do."""
+        if n_clips <= 1:
+            self._log(f"seam_passes = {passes}: the run is one clip, there is no clip border to warm-start across")
+            return
+        nq, F = self.setup.tables.nq, int(self.cfg.stac.n_frames_per_clip)
+        if not 1 <= F <= kp.shape[1]:
+            raise ValueError(f"seam_passes: n_frames_per_clip = {F}, but the clips have {kp.shape[1]} rows")
+        n_local = int(kp.shape[0])
+        start = 1 if lo == 0 else 0  # (clip 0 is never solved again)
+        names = ("qpos", "frame_error", "counters", "carry_qpos", "xpos", "xquat", "marker_sites")
+        scalar = None
+        if self.verbose:
+            from .seam import scalar_columns
+
+            scalar = torch.as_tensor(scalar_columns(nq, self._quat_cols(), 3 if self._freejoint else 0), device=self.engine.device)
+
+        def seam_mean():  # of this rank's own clip borders, over the hinge and slide columns
+            if scalar is None or n_local < 2 or scalar.numel() == 0:
+                return float("nan")
+            q = res["qpos"]
+            return float((q[1:, 0][:, scalar] - q[:-1, F - 1][:, scalar]).abs().amax(dim=1).mean())
+
+        for p in range(2, passes + 1):
+            before = seam_mean()
+            last = res["qpos"][:, F - 1, :]  # [n_local, nq]: the pose every clip of this rank ended in
+            rows = [last[:-1]] if n_local else []
+            if dist.is_dist():
+                incoming = dist.exchange_seam_rows(last[-1] if n_local else None, nq, self.engine.device)
+                if start == 0 and n_local:
+                    if incoming is None:
+                        raise RuntimeError(f"seam_passes: no earlier rank holds the clip in front of clip {lo}")
+                    rows.insert(0, incoming.reshape(1, nq))
+            if n_local - start < 1:
+                continue  # (a rank without a clip behind clip 0 only takes part in the exchange)
+            q_init = torch.cat(rows, dim=0).clone() if start == 0 else last[:-1].clone()
+            out = {k: res[k][start:] for k in names if res.get(k) is not None}
+            self._q_phase(kp[start:], do_root_opt=False, q_init=q_init, out=out)
+            self._log(f"seam_passes: pass {p} of {passes}: {n_local - start} clips warm-started; mean seam jump {before:.4f} -> "
+                      f"{seam_mean():.4f} rad over this rank's {max(n_local - 1, 0)} borders")
+
+    # -- seam_steps (engine extension; DESIGN.md "Warm-started clips and pose steps") --------------------------------------
+    def seam_steps(self, data, clip_len=None) -> dict:
+        """The pose steps of a result, on the GPU (``seam.seam_steps``): per row how far the pose moved since the row before it --
+        ``step_joint`` (the largest hinge or slide step, rad or m), ``step_col`` (its column), ``step_rot`` (1 - |<a, b>| of the
+        quaternions) and ``step_lin2`` (the squared step of the free joint's translation) as numpy arrays -- per column the largest
+        step within the clips and across their borders (``col_max_in`` / ``col_max_seam``), and ``summary`` (``seam.summarize``:
+        per seam, seam mean / max, the p50 / p99 within the clips, and the marker error of the first frames of the clips against
+        the whole run's).  ``data``: a ``StacData``, with this object's config, or the path of a result file (a ``*.manifest.json``
+        reads a sharded run), whose stored config decides the clips: ``n_frames_per_clip`` rows, also for a continuous run once it
+        is stitched (an unstitched one has windows of ``n_frames_per_clip + 10`` rows).  ``clip_len`` overrides it."""
+        from . import io, seam
+
+        cfg = self.cfg
+        if not isinstance(data, StacData):
+            cfg, data = io.load_stac_result(data)
+        qpos = np.asarray(data.qpos, dtype=np.float32)
+        nq = self.setup.tables.nq
+        if qpos.ndim != 2 or qpos.shape[1] != nq or qpos.shape[0] < 1:
+            raise ValueError(f"seam_steps: qpos must be [frames, {nq}] with at least one frame, got {qpos.shape}")
+        N, F, ov = qpos.shape[0], int(cfg.stac.n_frames_per_clip), utils.CONTINUOUS_BATCH_OVERLAP
+        if clip_len is None:
+            clip_len = F + ov if bool(cfg.stac.continuous) and N % F != 0 and N % (F + ov) == 0 else F
+        clip_len = checked_int(clip_len, "seam_steps: clip_len", ValueError, 1)
+        if N % clip_len != 0:
+            raise ValueError(f"seam_steps: cannot cut {N} rows into clips of {clip_len} frames")
+        res = seam.seam_steps(torch.as_tensor(np.array(qpos)).to(self.engine.device), clip_len, self._quat_cols(), 3 if self._freejoint else 0)
+        markers, kp = np.asarray(data.marker_sites), np.asarray(data.kp_data)
+        paired = markers.ndim == 3 and markers.shape[0] == N and kp.ndim == 2 and kp.shape == (N, 3 * markers.shape[1])
+        summary = seam.summarize(res, clip_len, data.names_qpos, markers if paired else None, kp if paired else None)
+        w = summary["within"]
+        self._log(f"seam_steps: {summary['n_seams']} seams of {N} rows (clips of {clip_len}): seam mean / max {summary['seam_mean']} / "
+                  f"{summary['seam_max']}; within clips p50 / p99 / max {w['p50']} / {w['p99']} / {w['max']}")
+        out = {k: v.cpu().numpy() for k, v in res.items()}
+        out["summary"] = summary
+        return out
 
     def _check_post(self, post, gather):
         """The ``post`` argument of ik_only, checked before any work is done."""

@@ -130,6 +130,13 @@ SEAM_PROTOTYPES = {
     "stac_seam_last_error_code": (i32, []),
     "stac_seam_steps": (i32, [vp, i64, i32, i64, _i32p, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
 }
+# every function csrc/ground/stac_ground.h declares (libstac_ground.so, the companion library of stac.ground), in its order; the
+# geom_meta_host of stac_ground_clearance is HOST memory: an int32 pointer, not a device address
+GROUND_PROTOTYPES = {
+    "stac_ground_last_error": (C.c_char_p, []),
+    "stac_ground_last_error_code": (i32, []),
+    "stac_ground_clearance": (i32, [vp, vp, i64, i32, _i32p, vp, vp, i32, vp, i32, i32, f32, vp, vp, vp, vp, vp, vp]),
+}
 
 
 class StacHipError(RuntimeError):

@@ -1,6 +1,6 @@
 """Builds the HIP extension in-tree: ``stac_mjx_amd/csrc/libstac_hip.so`` and its companions
-``stac_mjx_amd/csrc/select/libstac_select.so``, ``stac_mjx_amd/csrc/mmask/libstac_mmask.so`` and
-``stac_mjx_amd/csrc/seam/libstac_seam.so`` (gfx950 only).
+``stac_mjx_amd/csrc/select/libstac_select.so``, ``stac_mjx_amd/csrc/mmask/libstac_mmask.so``,
+``stac_mjx_amd/csrc/seam/libstac_seam.so`` and ``stac_mjx_amd/csrc/ground/libstac_ground.so`` (gfx950 only).
 
 ``hipcc`` cross-compiles without a GPU.  ``-ffp-contract=off -fno-fast-math`` is part of the
 arithmetic contract of the kernels (bit-identical to the CPU oracle), not a tuning choice.
@@ -58,6 +58,12 @@ SEAM_LIB = SEAM_DIR / "libstac_seam.so"
 SEAM_STAMP = SEAM_DIR / "libstac_seam.so.stamp"
 SEAM_SOURCES = sorted(SEAM_DIR.glob("*.hip"))
 SEAM_HEADERS = sorted(SEAM_DIR.glob("*.hpp")) + sorted(SEAM_DIR.glob("*.h"))
+# The companion library of stac.ground (csrc/ground/: the ground clearance of fitted poses), built the same way.
+GROUND_DIR = CSRC / "ground"
+GROUND_LIB = GROUND_DIR / "libstac_ground.so"
+GROUND_STAMP = GROUND_DIR / "libstac_ground.so.stamp"
+GROUND_SOURCES = sorted(GROUND_DIR.glob("*.hip"))
+GROUND_HEADERS = sorted(GROUND_DIR.glob("*.hpp")) + sorted(GROUND_DIR.glob("*.h"))
 
 
 def source_digest() -> str:
@@ -105,6 +111,17 @@ def seam_digest() -> str:
     return h.hexdigest()
 
 
+def ground_digest() -> str:
+    """``source_digest`` of ``libstac_ground.so``."""
+    import hashlib
+
+    h = hashlib.sha256(" ".join(FLAGS).encode())
+    for p in GROUND_SOURCES + GROUND_HEADERS + HEADERS:
+        h.update(p.name.encode())
+        h.update(p.read_bytes())
+    return h.hexdigest()
+
+
 def is_stale() -> bool:
     if not LIB.exists() or not STAMP.exists():
         return True
@@ -123,6 +140,10 @@ def seam_is_stale() -> bool:
     return not SEAM_LIB.exists() or not SEAM_STAMP.exists() or SEAM_STAMP.read_text().strip() != seam_digest()
 
 
+def ground_is_stale() -> bool:
+    return not GROUND_LIB.exists() or not GROUND_STAMP.exists() or GROUND_STAMP.read_text().strip() != ground_digest()
+
+
 def _compile(sources, lib, stamp, digest, verbose):
     import time
 
@@ -138,8 +159,11 @@ def _compile(sources, lib, stamp, digest, verbose):
 
 
 def build_extension(force: bool = False, verbose: bool = False) -> Path:
-    """Builds what is stale (``force``: all four libraries) -> the path of ``libstac_hip.so``; ``libstac_select.so`` stands beside
-    it in ``csrc/select``, ``libstac_mmask.so`` in ``csrc/mmask`` and ``libstac_seam.so`` in ``csrc/seam``."""
+    """Builds what is stale (``force``: all five libraries) -> the path of ``libstac_hip.so``; ``libstac_select.so`` stands beside
+    it in ``csrc/select``, ``libstac_mmask.so`` in ``csrc/mmask``, ``libstac_seam.so`` in ``csrc/seam`` and ``libstac_ground.so`` in
+    ``csrc/ground``."""
+    if force or ground_is_stale():
+        _compile(GROUND_SOURCES, GROUND_LIB, GROUND_STAMP, ground_digest, verbose)
     if force or seam_is_stale():
         _compile(SEAM_SOURCES, SEAM_LIB, SEAM_STAMP, seam_digest, verbose)
     if force or mmask_is_stale():

@@ -65,7 +65,14 @@ _MUJOCO_REQUIRED = ("solver", "iterations", "ls_iterations")
 # diverse take a frame of which at least ceil(q K) keypoints are observed; read from the caller's config;
 # seam_passes: 1 (default) .. 8 -- ik_only solves the clips behind the first again, P - 1 times, each warm-started from the pose
 # that the clip in front of it ended in, without root optimisation; seam_report: off (default) | on -- a <ik file>.seams.json with
-# the pose steps across and within the clips, measured on the GPU; both read from the caller's config)
+# the pose steps across and within the clips, measured on the GPU; both read from the caller's config;
+# ground: off (default) | report | level -- the ground clearance of the ik_only result, measured on the GPU: report writes
+# <ik file>.ground.json (per frame the lowest geom, per geom its lowest z and the frames it spends under ground_z, the floor of the
+# recording as the ground_permille quantile of the per-frame lowest z, per ground_track body the share of frames within
+# ground_contact of it); level (free-root models) also subtracts that floor from the z of the packaged result; ground_geoms: fitted
+# (default: the geoms of the bodies the fit can move) | all | a list of geom or body names; ground_geom_groups: the geom groups that
+# enter (default all); ground_floor_z: written by a level run into the stored config, the floor it subtracted; read from the
+# caller's config)
 _STAC_EXTENSIONS = ("solver", "lanes_per_chain", "device", "time_indices", "fit_frames_per_clip", "reference_marker_order", "gather", "gather_max_bytes", "lm_maxiter", "postprocess", "fill_missing",
                     "reject_outliers", "outlier_window", "outlier_nsigma", "outlier_min_dev", "report", "report_quantiles", "report_worst",
                     "smooth", "smooth_window", "smooth_order", "smooth_sigma",
@@ -74,7 +81,8 @@ _STAC_EXTENSIONS = ("solver", "lanes_per_chain", "device", "time_indices", "fit_
                     "fill_donors", "fill_donors_triples",
                     "resample", "mocap_hz", "resample_hz", "resample_lobes", "resample_beta",
                     "fit_frames", "offset_mask", "fit_frames_min_observed",
-                    "seam_passes", "seam_report")
+                    "seam_passes", "seam_report",
+                    "ground", "ground_geoms", "ground_geom_groups", "ground_track", "ground_z", "ground_permille", "ground_contact", "ground_floor_z")
 _MODEL_EXTENSIONS = ("KP_NAMES_LABEL3D_PATH",)
 
 
@@ -320,6 +328,56 @@ def seam_options(stac) -> tuple:
     if not isinstance(mode, str) or mode not in ("off", "on"):
         raise ConfigError(f"stac.seam_report must be off or on, not {mode!r}")
     return p, mode == "on"
+
+
+GROUND_MODES = ("off", "report", "level")
+GROUND_DEFAULTS = {"ground_geoms": "fitted", "ground_track": (), "ground_z": 0.0, "ground_permille": 50, "ground_contact": 0.002}
+GROUND_MAX_TRACK = 32  # csrc/ground/stac_ground.hpp: kGroundMaxSlots
+
+
+def _name_list(v, name) -> list:
+    if not isinstance(v, (list, tuple)) or not all(isinstance(n, str) and n for n in v):
+        raise ConfigError(f"{name} must be a list of names, not {v!r}")
+    return [str(n) for n in v]
+
+
+def ground_options(stac) -> dict:
+    """``stac.ground`` and its six parameters out of a ``stac`` mapping -> ``{"mode", "geoms", "geom_groups", "track", "z_ref",
+    "permille", "contact"}``, absent keys (and keys without a value) at their defaults.  ``ConfigError`` for anything else than off |
+    report | level (a bare YAML ``off`` arrives as False), ``ground_geoms`` that is not fitted, all or a non-empty list of names,
+    ``ground_geom_groups`` that is not a list of integers >= 0, ``ground_track`` that is not a list of at most 32 distinct names, a
+    ``ground_z`` that is not a finite number, a ``ground_permille`` outside 1 .. 1000 and a ``ground_contact`` that is not a finite
+    number >= 0, and a ``ground_floor_z`` (the floor that a ``level`` run records in the config its result file stores; it is written,
+    never read) that is not a finite number or comes without ``level``.  Whether the names exist is for ``ground.ground_table``, which knows the model."""
+    mode = _switch(stac, "ground")
+    if not isinstance(mode, str) or mode not in GROUND_MODES:
+        raise ConfigError(f"stac.ground must be off, report or level, not {mode!r}")
+    get = lambda key: GROUND_DEFAULTS[key] if stac.get(key) is None else stac.get(key)  # noqa: E731
+    geoms = get("ground_geoms")
+    if not (isinstance(geoms, str) and geoms in ("fitted", "all")):
+        if isinstance(geoms, str) or not geoms:
+            raise ConfigError(f"stac.ground_geoms must be fitted, all or a list of geom or body names, not {geoms!r}")
+        geoms = _name_list(geoms, "stac.ground_geoms")
+    groups = stac.get("ground_geom_groups")
+    if groups is not None:
+        if not isinstance(groups, (list, tuple)) or not groups or any(isinstance(g, bool) or not isinstance(g, int) or g < 0 for g in groups):
+            raise ConfigError(f"stac.ground_geom_groups must be a list of geom groups (integers >= 0), not {groups!r}")
+        groups = [int(g) for g in groups]
+    track = _name_list(get("ground_track"), "stac.ground_track")
+    if len(track) > GROUND_MAX_TRACK or len(set(track)) != len(track):
+        raise ConfigError(f"stac.ground_track must be a list of at most {GROUND_MAX_TRACK} distinct body names, not {track!r}")
+    z = get("ground_z")
+    if isinstance(z, bool) or not isinstance(z, (int, float)) or not math.isfinite(z):
+        raise ConfigError(f"stac.ground_z must be a finite number, not {z!r}")
+    permille = checked_int(get("ground_permille"), "stac.ground_permille", ConfigError, 1, 1000)
+    contact = checked_number(get("ground_contact"), "stac.ground_contact", ConfigError)
+    floor = stac.get("ground_floor_z")  # (written by a level run into the config that its result file stores; never read back)
+    if floor is not None:
+        if isinstance(floor, bool) or not isinstance(floor, (int, float)) or not math.isfinite(floor):
+            raise ConfigError(f"stac.ground_floor_z must be a finite number, not {floor!r}")
+        if mode != "level":
+            raise ConfigError(f"stac.ground_floor_z = {floor!r} is what a run with stac.ground = level records in its result file: it goes with level only")
+    return {"mode": mode, "geoms": geoms, "geom_groups": groups, "track": track, "z_ref": float(z), "permille": permille, "contact": contact}
 
 
 REPORT_DEFAULTS = {"report_quantiles": (500, 900, 990), "report_worst": 10}
@@ -590,6 +648,9 @@ def validate_config(cfg: dict) -> ConfigNode:
     if isinstance(stac.get("seam_report"), bool):  # (as above: the stored file says off / on)
         stac["seam_report"] = "on" if stac["seam_report"] else "off"
     seam_options(stac)
+    if isinstance(stac.get("ground"), bool):
+        stac["ground"] = _switch(stac, "ground")
+    ground_options(stac)
     return _wrap({"model": model, "stac": stac})
 
 

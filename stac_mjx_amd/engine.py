@@ -16,8 +16,8 @@ import torch
 
 from .abi import (ABI_SYMBOLS, StacHipError, StacModelTables, StacQParams, _f32p, _i32p, _ptr, _u8p, check, declare,  # noqa: F401
                   hip_error, last_error, stream_ptr)
-from .build import (LIB, MMASK_LIB, MMASK_STAMP, SEAM_LIB, SEAM_STAMP, SELECT_LIB, SELECT_STAMP, STAMP, mmask_digest, seam_digest, select_digest,
-                    source_digest)
+from .build import (GROUND_LIB, GROUND_STAMP, LIB, MMASK_LIB, MMASK_STAMP, SEAM_LIB, SEAM_STAMP, SELECT_LIB, SELECT_STAMP, STAMP, ground_digest,
+                    mmask_digest, seam_digest, select_digest, source_digest)
 
 ABI_VERSION = 3  # include/stac_hip.h: STAC_HIP_ABI_VERSION
 SOLVERS = {"pg": 0, "lm": 1}  # STAC_SOLVER_PG (the reference's algorithm, parity mode) / STAC_SOLVER_LM
@@ -118,6 +118,29 @@ def load_seam_library(path: Path | None = None):
     lib = declare(C.CDLL(str(p)), SEAM_PROTOTYPES)
     if path is None:
         _SEAM_LIB = lib
+    return lib
+
+
+_GROUND_LIB = None
+
+
+def load_ground_library(path: Path | None = None):
+    """Load ``libstac_ground.so`` (csrc/ground: the ground clearance of fitted poses, ``stac.ground``) with every prototype of
+    ``abi.GROUND_PROTOTYPES`` declared; raises if it has not been built or was built from other sources, like ``load_library``."""
+    global _GROUND_LIB
+    if _GROUND_LIB is not None and path is None:
+        return _GROUND_LIB
+    p = Path(path) if path else GROUND_LIB
+    if not p.exists():
+        raise StacHipError(f"HIP extension not built: {p} is missing (run `python -m stac_mjx_amd.build`)")
+    if p == GROUND_LIB and GROUND_STAMP.exists() and GROUND_STAMP.read_text().strip() != ground_digest():
+        raise StacHipError(f"{p} was built from other sources than the ones in this tree (stamp {GROUND_STAMP.name} differs): "
+                           "rebuild with `python -m stac_mjx_amd.build`")
+    from .abi import GROUND_PROTOTYPES
+
+    lib = declare(C.CDLL(str(p)), GROUND_PROTOTYPES)
+    if path is None:
+        _GROUND_LIB = lib
     return lib
 
 

@@ -10,7 +10,7 @@ import numpy as np
 
 from . import dist, io, utils
 from .config import (DONORS_NEED_FILL, GATHER_NONE_CONTINUOUS, OFFSET_MASK_NEEDS_FILL, PAIRWISE_NEEDS_FILL, POSTPROCESS_GPU_MARKER_ORDER, RESAMPLE_SHARDED, compose_config,
-                     donor_options, fill_missing_options, fit_frames_options, offset_mask_options, outlier_options, pairwise_options, postprocess_options, report_options, resample_options,
+                     donor_options, fill_missing_options, fit_frames_options, ground_options, offset_mask_options, outlier_options, pairwise_options, postprocess_options, report_options, resample_options,
                      seam_options, smooth_options, swaps_candidates, swaps_options)
 from .stac import Stac
 
@@ -66,6 +66,11 @@ def run_stac(cfg, kp_data, kp_names, base_path=None, *, setup=None, device=None)
     warm-started from the pose that the clip in front of it ended in, so that the clip borders stop carrying the jump of a cold start;
     ``stac.seam_report: on`` measures the pose steps of the ik_only result on the GPU and writes them as ``<ik file>.seams.json``
     (DESIGN.md "Warm-started clips and pose steps"); the ik_only file's stored config carries both keys.
+    ``stac.ground: report`` measures on the GPU how far the geoms of the ik_only result are from the floor and writes
+    ``<ik file>.ground.json`` (DESIGN.md "Ground clearance"); the result does not change.  ``stac.ground: level`` (models with a free
+    root that the fit places) also subtracts ``floor_z``, the ``stac.ground_permille`` quantile of the per-frame lowest z, from ``qpos[:, 2]`` and from the
+    z of ``xpos``, ``marker_sites`` and ``kp_data`` of the ik_only file, and records it in the sidecar and in the stored config; the
+    fit file and the offsets are not touched.  Unknown geom or body names are a ``ValueError`` before any work.
     """
     base_path = Path.cwd() if base_path is None else Path(base_path)
     kp_data = np.asarray(kp_data)
@@ -82,6 +87,7 @@ def run_stac(cfg, kp_data, kp_names, base_path=None, *, setup=None, device=None)
     pre.check_config()
     stac = Stac(base_path / cfg.model.MJCF_PATH, cfg, kp_names, setup=setup, device=device)
     pre.check_run(dist.world()[1])
+    _check_ground_model(pre.ground, stac)
     series = _prepare_series(stac, cfg, kp_data, pre)
     if not cfg.stac.skip_fit_offsets:
         fit_offsets_path = _run_fit(stac, cfg, series, fit_offsets_path, pre.report, pre.fit_frames, pre.offset_mask, pre.min_observed)
@@ -252,6 +258,8 @@ def _run_ik(stac, series, fit_offsets_path, ik_only_path, pre, start):
     extra = {"post": post} if pre.post_gpu else {}
     if pre.seam_passes != 1:
         extra["passes"] = pre.seam_passes
+    if pre.ground["mode"] == "level" and sharded:  # (gather = auto that resolved to none by the size of the output)
+        raise ValueError(GROUND_LEVEL_SHARDED)
     ik_data = stac.ik_only(kp_data, fit_data.offsets, gather=mode, **extra)
     if rank != 0 and not sharded and mode != "all":
         dist.barrier()  # this rank holds its own shard only: rank 0 post-processes and writes the gathered result
@@ -268,12 +276,18 @@ def _run_ik(stac, series, fit_offsets_path, ik_only_path, pre, start):
     lo, hi = dist.shard_range(n_clips) if sharded else (0, n_clips)
     # (rows of the input series, not passed through the cross-fade; a shard file carries the rows of its clips)
     series.attach(ik_data, lo * F, hi * F)
+    ground = None
+    if pre.ground["mode"] != "off" and (sharded or rank == 0) and np.asarray(ik_data.xpos).shape[0]:
+        ground = _ground_stage(stac, ik_data, pre.ground)  # (level: ik_data is levelled from here on; resample inherits it)
+        cfg = _ground_config(cfg, pre.ground, ground)
     if sharded:
         # every rank writes ITS clips under a shard name (never a partial result under the full-run name; its report is of these
         # clips, shard reports are not merged); rank 0 adds the manifest that io.load_stac_result() reads the run back through
         shard = _write_result(stac, cfg, ik_data, io.shard_path(ik_only_path, rank, world_size), pre.report, True)
         if pre.seam_report:  # (of this rank's clips, like its report)
             _write_seams(stac, ik_data, shard, F)
+        if ground is not None:
+            _write_ground(shard, ground)
         manifest = io.manifest_path(ik_only_path)
         if rank == 0:
             io.write_manifest(manifest, ik_only_path, world_size, n_clips, F)
@@ -284,6 +298,8 @@ def _run_ik(stac, series, fit_offsets_path, ik_only_path, pre, start):
     ik_only_path = _write_result(stac, cfg, ik_data, ik_only_path, pre.report, rank == 0)
     if pre.seam_report and rank == 0:
         _write_seams(stac, ik_data, ik_only_path, F)
+    if ground is not None:
+        _write_ground(ik_only_path, ground)
     if pre.resample is not None:
         _write_resampled(stac, cfg, ik_data, ik_only_path, pre, rank == 0)
     print(f"Saved ik_only to {ik_only_path}. Finished in {(time.time() - start) / 60:.2f} minutes")
@@ -308,6 +324,90 @@ def _write_seams(stac, ik_data, ik_only_path, clip_len) -> Path:
     path.write_text(json.dumps(summary, indent=1) + "\n")
     print(f"seam_report: {summary['n_seams']} seams, mean / max step across a clip border {summary['seam_mean']} / {summary['seam_max']}; "
           f"wrote {path}", flush=True)
+    return path
+
+
+GROUND_LEVEL_SHARDED = ("stac.ground = level takes the floor from the whole ik_only result on rank 0, but this run writes per-rank shards "
+                        "(stac.gather resolves to none): use gather = rank0, or stac.ground = report")
+GROUND_LEVEL_FIXED_ROOT = ("stac.ground = level moves the model along z through a free root joint that the fit places (root optimisation), "
+                           "which this model does not have: use stac.ground = report")
+
+
+def ground_path(ik_only_path) -> Path:
+    """``ik_only.h5`` -> ``ik_only.h5.ground.json`` (of the name the result file really has: ``io.resolve_output_path``)."""
+    p = io.resolve_output_path(ik_only_path)
+    return p.with_name(p.name + ".ground.json")
+
+
+def _ground_mode(cfg) -> dict:
+    """``stac.ground``: "off" (default) | "report" | "level" -> the options of ``config.ground_options``.  ``ValueError`` for a bad
+    value of any of the seven keys.  What needs the model is for ``_check_ground_model``."""
+    return ground_options(cfg.stac)
+
+
+def check_ground_level(mode: str, setup):
+    """``level`` shifts the pose along z through the free joint's translation: refused for a model without one, and for one whose
+    root the fit leaves where the model has it (a tethered animal: no ``ROOT_OPTIMIZATION_KEYPOINT``)."""
+    if mode == "level" and not (setup.freejoint and setup.do_root_opt):
+        raise ValueError(GROUND_LEVEL_FIXED_ROOT)
+
+
+def _check_ground_model(opt, stac):
+    """What ``stac.ground`` asks of the model, once it is known and before any work: a free root for ``level``, and geom and body
+    names (``ground_geoms``, ``ground_track``) that the model has."""
+    if opt["mode"] == "off":
+        return
+    check_ground_level(opt["mode"], stac.setup)
+    stac.ground_table(opt["geoms"], opt["geom_groups"], opt["track"])
+
+
+def _ground_stage(stac, ik_data, opt) -> dict:
+    """``stac.ground``: the summary of ``Stac.ground_clearance`` of the packaged ik_only result.  ``level``: ``floor_z`` of that
+    summary is subtracted in float32 from ``qpos[:, 2]`` and from the z of ``xpos``, ``marker_sites`` and ``kp_data`` of ``ik_data``
+    (in place), and ``summary["level"]`` says per geom how many frames it spends below the new floor: a second call on the unshifted
+    arrays with ``z_ref = floor_z``."""
+    args = dict(geoms=opt["geoms"], track=opt["track"], permille=opt["permille"], contact=opt["contact"])
+    summary = stac.ground_clearance(ik_data, z_ref=opt["z_ref"], **args)["summary"]
+    summary["mode"] = opt["mode"]
+    if opt["mode"] != "level":
+        return summary
+    if summary["floor_z"] is None:
+        raise ValueError("stac.ground = level: no frame of the result has a finite lowest z, so there is no floor to subtract")
+    floor = np.float32(summary["floor_z"])
+    again = stac.ground_clearance(ik_data, z_ref=float(floor), **args)["summary"]
+    summary["level"] = {"floor_z": float(floor), "geoms": [{"name": g["name"], "frames_below": g["frames_below"]} for g in again["geoms"]],
+                        "unfitted_below": again["unfitted_below"]}
+    for name, index in (("qpos", (slice(None), 2)), ("xpos", (Ellipsis, 2)), ("marker_sites", (Ellipsis, 2)), ("kp_data", (slice(None), slice(2, None, 3)))):
+        a = np.array(getattr(ik_data, name), dtype=np.float32)
+        a[index] = a[index] - floor
+        setattr(ik_data, name, a)
+    return summary
+
+
+def _ground_config(cfg, opt, summary):
+    """The config that the ik_only file stores: the ``stac.ground*`` keys of this run and, for ``level``, the floor it subtracted."""
+    from .config import validate_config
+
+    stored = cfg.to_dict()
+    stored["stac"].update({"ground": opt["mode"], "ground_geoms": opt["geoms"], "ground_track": list(opt["track"]), "ground_z": opt["z_ref"],
+                           "ground_permille": opt["permille"], "ground_contact": opt["contact"]})
+    if opt["geom_groups"] is not None:
+        stored["stac"]["ground_geom_groups"] = list(opt["geom_groups"])
+    if opt["mode"] == "level":
+        stored["stac"]["ground_floor_z"] = summary["level"]["floor_z"]
+    else:
+        stored["stac"].pop("ground_floor_z", None)
+    return validate_config(stored)
+
+
+def _write_ground(ik_only_path, summary) -> Path:
+    """The summary of ``_ground_stage`` as JSON next to the result file, and one line of it to the log."""
+    import json
+
+    path = ground_path(ik_only_path)
+    path.write_text(json.dumps(summary, indent=1) + "\n")
+    print(f"ground: floor_z {summary['floor_z']}, {len(summary['unfitted_below'])} geoms outside the fit below z = {summary['z_ref']:g} in most frames"
+          + (f"; levelled by {summary['level']['floor_z']}" if "level" in summary else "") + f"; wrote {path}", flush=True)
     return path
 
 
@@ -373,6 +473,7 @@ class _Preflight:
         self.fit_frames = fit_frames_options(stac)
         self.offset_mask, self.min_observed = _offset_mask_mode(self.cfg)
         self.seam_passes, self.seam_report = seam_options(stac)
+        self.ground = _ground_mode(self.cfg)
         if self.fit_frames != "first" and not stac.skip_fit_offsets:  # (first keeps the reference's slice, which takes what there is)
             n = int(stac.n_fit_frames)
             if n > self.n_frames:
@@ -400,6 +501,8 @@ class _Preflight:
                 raise ValueError(GATHER_NONE_CONTINUOUS)
             if self.resample is not None:
                 raise ValueError(RESAMPLE_SHARDED)
+            if self.ground["mode"] == "level":
+                raise ValueError(GROUND_LEVEL_SHARDED)
         # stac.postprocess (engine extension, read from the caller's config like gather): "host" (default) = the numpy functions
         # of utils.py; "gpu" = ik_only stitches and infers qvel on the device (post.py) and the two host steps are skipped
         self.post_gpu = _postprocess_mode(self.cfg) == "gpu"

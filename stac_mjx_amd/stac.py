@@ -585,6 +585,62 @@ class Stac:
         out["summary"] = summary
         return out
 
+    # -- ground_clearance (engine extension; DESIGN.md "Ground clearance") ------------------------------------------------------
+    def ground_table(self, geoms="fitted", geom_groups=None, track=()):
+        """``ground.ground_table`` of this model: the scene is compiled as ``render`` compiles it (the same ``SCALE_FACTOR``), once per
+        choice of ``geoms`` / ``geom_groups`` / ``track``.  ``ValueError`` for unknown names and for a ``Stac`` without an MJCF file."""
+        from . import ground
+
+        key = (geoms if isinstance(geoms, str) else tuple(geoms), None if geom_groups is None else tuple(int(g) for g in geom_groups), tuple(track))
+        tables = getattr(self, "_ground_tables", None)
+        if tables is None:
+            tables = self._ground_tables = {}
+        if key not in tables:
+            if getattr(self, "_ground_scene", None) is None:
+                if self._xml_path is None:
+                    raise ValueError("Stac.ground_clearance needs the model's MJCF file: this Stac was built from `setup=` without an xml_path")
+                from .mjcf import compile_render_scene
+
+                self._ground_scene = compile_render_scene(self._xml_path, scale=float(self.cfg.model.SCALE_FACTOR), log=self._log)
+            tables[key] = ground.ground_table(self._ground_scene, self.setup.tables, geoms, geom_groups, track)
+        return tables[key]
+
+    def ground_clearance(self, data, geoms=None, track=None, z_ref=None, permille=None, contact=None) -> dict:
+        """How far the fitted body is from the floor, on the GPU (``ground.ground_clearance``): per frame ``low_z``, the lowest world z
+        of the included geoms, and ``low_geom``, the table index of the geom that has it; ``track_z`` [N, S], the lowest z of the geoms
+        of each tracked body; per geom ``geom_min`` and ``geom_below`` (the frames it spends below ``z_ref``), as numpy arrays;
+        ``names`` (the geoms of the table) and ``summary`` (``ground.summarize``: ``floor_z``, the ``permille`` quantile of ``low_z``;
+        its minimum, median and maximum; every geom; the geoms that are not included and lie below ``z_ref`` in most frames; per track
+        the share of frames within ``contact`` of the floor).  ``data``: a ``StacData`` or the path of a result file (a
+        ``*.manifest.json`` reads a sharded run).  Arguments left None come from ``stac.ground_*`` of this object's config."""
+        from . import ground, io
+        from .config import ground_options
+
+        opt = ground_options(self.cfg.stac)
+        geoms = opt["geoms"] if geoms is None else geoms
+        track = opt["track"] if track is None else list(track)
+        z_ref = opt["z_ref"] if z_ref is None else float(z_ref)
+        permille = opt["permille"] if permille is None else checked_int(permille, "ground_clearance: permille", ValueError, 1, 1000)
+        contact = opt["contact"] if contact is None else float(contact)
+        if not isinstance(data, StacData):
+            _, data = io.load_stac_result(data)
+        nb = self.setup.tables.nbody
+        xpos, xquat = np.asarray(data.xpos, dtype=np.float32), np.asarray(data.xquat, dtype=np.float32)
+        if xpos.ndim != 3 or xpos.shape[1:] != (nb, 3) or xquat.shape != (xpos.shape[0], nb, 4) or xpos.shape[0] < 1:
+            raise ValueError(f"ground_clearance: xpos / xquat must be [frames, {nb}, 3 / 4] with at least one frame, got {xpos.shape} / {xquat.shape}")
+        table = self.ground_table(geoms, opt["geom_groups"], track)
+        dev = self.engine.device
+        res = ground.ground_clearance(torch.as_tensor(np.array(xpos)).to(dev), torch.as_tensor(np.array(xquat)).to(dev), table, z_ref)
+        summary = ground.summarize(res, table, z_ref, permille, contact)
+        lz = summary["low_z"]
+        self._log(f"ground_clearance: {summary['n_frames']} frames, {summary['n_included']} of {summary['n_geoms']} geoms included: floor_z "
+                  f"{summary['floor_z']} (permille {permille}); low_z min / median / max {lz['min']} / {lz['median']} / {lz['max']}; "
+                  f"{len(summary['unfitted_below'])} geoms that are not included lie below z = {z_ref:g} in most frames")
+        out = {k: v.cpu().numpy() for k, v in res.items()}
+        out["names"] = list(table.names)
+        out["summary"] = summary
+        return out
+
     def _check_post(self, post, gather):
         """The ``post`` argument of ik_only, checked before any work is done."""
         out = {"continuous": bool(post["continuous"]), "n_frames_per_clip": int(post["n_frames_per_clip"]),
